@@ -10,8 +10,17 @@ data-path collective.  Every third evaluation (= once per SSPRK33 step) is the f
 lh_rhs_stable_dt launch at every N; for N > 1 its one-value result is
 min-all-reduced over RCCL inside the timed region.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs PRE_STEPS untimed steps (where --full runs its first two blocks: the loop
+starts past the device's start-up transient either way), W warm-up steps and the K timed steps, and
+prints the line.  --full adds every measurement beyond that headline: the no-arithmetic stream probe
+and the contract-traffic regime (before the warm-up steps, as they always ran), the device SSPRK33
+stepper and the adaptive-stepping blocks, the all-reduce timing at N > 1, and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed, for comparing two builds on the same
+inputs: the tendency planes of a fixed, seeded sample of rank 0's columns as DIR/dY_<var>.npy
+(columns x levels, the workload's float type) and the stable-step bound as DIR/stable_dt.npy.
 
 With --gpus N > 1 and no launcher in the environment (no WORLD_SIZE) bench.py starts the N
 ranks itself -- a child `python -m torch.distributed.run` spawned BEFORE this process touches the
@@ -65,7 +74,8 @@ def parse():
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse "
                          "the multi-process path on a single GPU)")
     ap.add_argument("--stepper", action="store_true", default=True,
-                    help="also time the device SSPRK33 stepper, both engines (extra JSON fields; default)")
+                    help="with --full, also time the device SSPRK33 stepper, both engines (extra JSON fields; "
+                         "default)")
     ap.add_argument("--no-stepper", dest="stepper", action="store_false")
     ap.add_argument("--no-known-zero", action="store_true",
                     help="LH_TUNE zero=0: read theta_i and clear the d theta_i plane at every launch "
@@ -76,7 +86,15 @@ def parse():
     ap.add_argument("--no-step-events", action="store_true",
                     help="no HIP events between the timed steps (kernel statistics then come from a "
                          "separate back-to-back block)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline loop (stream probe, contract-traffic "
+                         "regime, stepper blocks, all-reduce timing, CPU baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 WORKLOADS = {
@@ -185,6 +203,24 @@ def cpu_baseline(case, seconds):
             else "reference CPU path: unavailable on this host (no julia binary)",
             "sample": f"{reps} RHS evals of the first {sample} columns x {n} levels of the same "
                       f"workload, OpenMP over columns on {threads} threads ({el:.1f} s)"}
+
+
+DUMP_COLUMNS = 16384     # at most 3 planes x 128 levels x 8 B per column: 48 MiB
+PRE_STEPS = 150          # untimed steps of a plain run: ~ the device time of --full's probe + contract blocks
+
+
+def dump_outputs(d, gm, dY, tdt):
+    """The tendencies the last timed step left in dY, for a fixed, seeded sample of this rank's
+    columns, and the stable-step bound of the last fused step (tdt; None when none ran)."""
+    os.makedirs(d, exist_ok=True)
+    ncols = gm.case.ncols
+    cols = np.sort(np.random.default_rng(0).choice(ncols, size=min(ncols, DUMP_COLUMNS), replace=False))
+    out = {"dY_" + k: np.ascontiguousarray(v[cols]) for k, v in gm.tendencies(dY).items()}
+    if tdt is not None:
+        out["stable_dt"] = tdt.cpu().numpy()
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20, "output dump above 64 MiB"
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def planes_streamed(case):
@@ -347,32 +383,33 @@ def main():
     moved_per_cell = (nr + nw) * esize + percol_extra
     bytes_moved = cells * moved_per_cell
 
-    # Ancillary measurements FIRST (order: stream probe, contract-traffic regime, then the W warm-up
-    # steps and the K timed steps): they need the same resident state, and the ~90 launches they issue
-    # bring the device to its sustained clock before the headline loop (a box starts at idle clocks:
+    # --full: ancillary measurements FIRST (order: stream probe, contract-traffic regime, then the W
+    # warm-up steps and the K timed steps): they need the same resident state, and the ~90 launches they
+    # issue bring the device to its sustained clock before the headline loop (a box starts at idle clocks:
     # the first tens of launches of a short run are 10-20 % slower, see per_step_ms).
 
     # the ceiling of this access pattern on these very planes: the library's no-arithmetic probe
     # (reads up to nr planes of Y, writes nw planes of dY; it reports its own plane counts)
     probe = None
-    try:
-        F.check(L.lh_synchronize(ctx), ctx)
-        y_planes = {0: [0, 1], 1: [2], 2: [0, 2, 1]}[case.om.model]      # theta_i last
-        d_planes = {0: [0, 1], 1: [2], 2: [0, 2, 1]}[case.om.model]
-        rp, wp = y_planes[:nr], d_planes[:nw]
-        pm, wm = sum(1 << v for v in rp), sum(1 << v for v in wp)
-        pms = C.c_float()
-        F.check(L.lh_stream_probe(ctx, Y, pm, dY, wm, 40, C.byref(pms)), ctx)
-        probe = {"gbs": cells * esize * (len(rp) + len(wp)) / (pms.value * 1e-3) / 1e9, "ms": pms.value,
-                 "planes_read": len(rp), "planes_written": len(wp)}
-    except Exception as e:      # noqa: BLE001
-        probe = {"error": repr(e)}
+    if a.full:
+        try:
+            F.check(L.lh_synchronize(ctx), ctx)
+            y_planes = {0: [0, 1], 1: [2], 2: [0, 2, 1]}[case.om.model]      # theta_i last
+            d_planes = {0: [0, 1], 1: [2], 2: [0, 2, 1]}[case.om.model]
+            rp, wp = y_planes[:nr], d_planes[:nw]
+            pm, wm = sum(1 << v for v in rp), sum(1 << v for v in wp)
+            pms = C.c_float()
+            F.check(L.lh_stream_probe(ctx, Y, pm, dY, wm, 40, C.byref(pms)), ctx)
+            probe = {"gbs": cells * esize * (len(rp) + len(wp)) / (pms.value * 1e-3) / 1e9, "ms": pms.value,
+                     "planes_read": len(rp), "planes_written": len(wp)}
+        except Exception as e:      # noqa: BLE001
+            probe = {"error": repr(e)}
 
     # The SURVEY 8(d) byte contract as traffic: the same launch with the known-zero planes switched
     # off (theta_i read, d theta_i = 0 stored: LH_TUNE zero=0), timed in THIS process -- both byte
     # regimes from one run, one box, one clock.
     contract = None
-    if not a.no_known_zero and not a.no_contract_regime:
+    if a.full and not a.no_known_zero and not a.no_contract_regime:
         try:
             F.check(L.lh_set_tuning(ctx, b"zero=0"), ctx)
             for _ in range(5):
@@ -395,6 +432,13 @@ def main():
         finally:
             F.check(L.lh_set_tuning(ctx, b""), ctx)
 
+    # A plain run puts as much device time of untimed steps where those blocks stood: launches ~10-50
+    # after start-up run up to 50 % slower (the clock overshoots, then settles), and the headline loop
+    # has always started behind that transient.  Y is never written, so the outputs do not change.
+    if not a.full:
+        for i in range(PRE_STEPS):
+            rhs_step(i)
+
     for i in range(a.warmup):
         rhs_step(i)
     barrier()
@@ -415,6 +459,8 @@ def main():
         wall = float(t.item())
     assert gm.status() == 0, "non-finite tendency during the bench"
     dt_seen = float(tdt.item()) if a.steps >= 3 or a.warmup >= 3 else None
+    if a.dump_outputs and rank == 0:       # before anything below can touch Y or dY again
+        dump_outputs(a.dump_outputs, gm, dY, tdt if dt_seen is not None else None)
 
     # per-step durations inside the timed loop (HIP events on the launch stream)
     stats = {}
@@ -455,7 +501,7 @@ def main():
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         ar_ms = None
-        if native_comm:
+        if native_comm and a.full:
             for _ in range(5):
                 F.check(L.lh_allreduce_min(ctx, tdt.data_ptr()), ctx)
             F.check(L.lh_timer_start(ctx), ctx)
@@ -539,14 +585,15 @@ def main():
                      "valu_is": "PROFILED (same committed PMC passes as traffic): VALU instructions per cell-update, and the "
                                 "fraction of the launch the SIMDs spend issuing them (4 x SQ_ACTIVE_INST_VALU / 1024 SIMDs / "
                                 "GRBM_GUI_ACTIVE per XCD) -- the Float64 kernels are bound by this, not by HBM"},
-        "order": "stream probe (43 launches), contract-traffic regime (65 launches), W warm-up steps, K timed steps, "
-                 "then the optional stepper blocks",
+        "order": ("stream probe (43 launches), contract-traffic regime (65 launches), W warm-up steps, K timed steps, "
+                  "then the optional stepper blocks") if a.full else
+                 f"{PRE_STEPS} untimed steps, W warm-up steps, K timed steps",
         "contract_traffic": contract,
         "ranks": ranks,
         "stable_dt_seen": dt_seen,
         "placement_tuning": placement,
     }
-    if a.stepper:
+    if a.full and a.stepper:
         # lh_step_ssprk33 (3 RHS evaluations + stage updates per step): as the library runs it
         # (persistent column stepper from 3 steps per call on, unless a Dirichlet face makes
         # the fused stages the better engine for a large ensemble), and with the three
@@ -573,7 +620,7 @@ def main():
             F.check(L.lh_set_tuning(ctx, b""), ctx)
         except Exception as e:      # noqa: BLE001
             out["ssprk33_error"] = repr(e)
-    if a.stepper:
+    if a.full and a.stepper:
         # The adaptive time loop as a host would run it, nothing leaving the device: per step
         # lh_rhs_stable_dt (tendency + this rank's step bound; with a communicator the library's RCCL
         # min follows on the same stream) -> lh_step_ssprk33_device_dt (dt read from device memory).
@@ -623,7 +670,7 @@ def main():
             out["adaptive_ssprk33_error"] = repr(e)
     if native_comm:
         F.check(L.lh_comm_destroy(ctx), ctx)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(case, a.cpu_seconds)
     gm.close()
     if rank == 0:

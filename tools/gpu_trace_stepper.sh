@@ -4,8 +4,9 @@
 # usage: tools/gpu_trace_stepper.sh <tag> [bench args]
 TAG=$1; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/trace_$TAG
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-contract-regime $* > $OUT/bench.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-contract-regime $* > $OUT/bench.log 2>&1 || exit 1
 f=$(find $OUT/trace -name "*kernel_stats.csv" | head -1)
 cp $f $OUT/kernel_stats.csv
 python3 - <<PY

@@ -2,8 +2,9 @@
 # PMC pass over a bench run WITH the persistent stepper: VALU / LDS instructions per wave of column_stepper_*
 # usage (GPU box): tools/gpu_valu_count_stepper.sh <tag> [bench flags]
 OUT=$GRAFT_REPO_ROOT/gpurun_out/valu_$1; shift
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES --output-format csv -d $OUT/pmc -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-contract-regime $* > $OUT/bench.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES --output-format csv -d $OUT/pmc -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-contract-regime $* > $OUT/bench.log 2>&1
 python3 - <<PY
 import csv,glob,collections
 acc=collections.defaultdict(lambda: collections.defaultdict(list))
