@@ -354,6 +354,27 @@ int lh_step_ssprk33_device_dt(lh_ctx*, lh_state* Y, const lh_state* Ya, double t
 int lh_step_ssprk33_adaptive(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double courant,
                              double dt_max, int64_t nsteps, void* dt_device_ft, void* elapsed_device_ft);
 
+/* Backward-Euler steps of a Richards model: per step, Newton on
+ * Y - Yn - dt f(Y, t+dt) = 0 with f exactly lh_rhs's tendency, one tridiagonal solve per
+ * column and iteration.  bcv: NULL (current boundary values) or nsteps*4 doubles at t_{n+1}.
+ * tol <= 0 / max_iter <= 0: defaults.  Asynchronous; non-convergence sets status bit 3.
+ * (With a non-NULL bcv the call waits for its launch before it releases the device copy of the
+ * values, as lh_step_ssprk33 does.)
+ * (Build-defined: the reference hands any OrdinaryDiffEq method to DiffEqBase.init,
+ * src/Simulations/simulation.jl:34-73.)  bcv is laid out [nsteps][2 faces][2 components] like one
+ * stage of lh_step_ssprk33's.  A column-step converges when max_i |dY_i| <= tol max(|Y_i|, nu)
+ * (defaults: tol 1e-10 in Float64, 1e-5 in Float32; max_iter 50); one that does not keeps its last
+ * iterate.  Richards models only, without conductivity factors and without a prescribed
+ * atmosphere: anything else is LH_EMODEL.  theta_i is constant through the step. */
+int lh_step_implicit_euler(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
+                           int64_t nsteps, const double* bcv, double tol, int32_t max_iter);
+/* Of the last lh_step_implicit_euler call: the largest iteration count any column needed and
+ * the number of column-steps that did not converge (zeros once a later call was refused).  Synchronises. */
+int lh_implicit_stats(lh_ctx*, int32_t* max_iters, int64_t* unconverged);
+/* Of the last lh_step_implicit_euler call: the Newton iterations summed over all column-steps
+ * (divided by ncols * nsteps: the mean per column-step).  Synchronises. */
+int lh_implicit_iterations(lh_ctx*, int64_t* iterations);
+
 /* Build-defined stable step (the reference uses a fixed user dt):
  * courant*dz^2 / max over owned faces of the face diffusivities
  * ((K_lo+K_hi)/2 * max dpsi/dvl, (kappa_lo+kappa_hi)/2 / min rho_c_s; boundary
@@ -401,7 +422,8 @@ int lh_allreduce_min(lh_ctx*, void* value_device_ft);
  * would have raised DomainError from `^`); bit 1: the Monin-Obukhov system of the
  * prescribed-atmosphere BC had no root in some column; bit 2: a step of
  * lh_step_ssprk33_adaptive found no positive finite step bound (no positive diffusivity anywhere and
- * no dt_max, or a NaN) and was taken with dt = 0; synchronises and clears. */
+ * no dt_max, or a NaN) and was taken with dt = 0; bit 3: an implicit step (lh_step_implicit_euler)
+ * did not converge in some column; synchronises and clears. */
 int lh_get_status(lh_ctx*, uint32_t* flags);
 int lh_synchronize(lh_ctx*);
 /* Streaming ceiling of the column launch on a given set of planes (measurement aid, no

@@ -100,6 +100,8 @@ struct lh_ctx {
     lh_state* scratch_u1 = nullptr;    // SSPRK33 stage state
     lh_state* scratch_u2 = nullptr;    // second stage state (level-segmented launches cannot update U1 in place)
     lh_state* scratch_k1 = nullptr;    // f(Y) of lh_step_ssprk33_adaptive
+    void* d_imp = nullptr;             // lh_step_implicit_euler: three FT planes [nlev][stride] (v_n, c', d')
+    void* d_imp_stats = nullptr;       // ... and its statistics: int32 max iterations, uint64 unconverged, uint64 iterations
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
     Tune tune;
@@ -1083,6 +1085,8 @@ int lh_destroy(lh_ctx* c) {
     if (c->d_zc) (void)hipFree(c->d_zc);
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->d_dt) (void)hipFree(c->d_dt);
+    if (c->d_imp) (void)hipFree(c->d_imp);
+    if (c->d_imp_stats) (void)hipFree(c->d_imp_stats);
     for (int k = 0; k < 3; ++k)
         if (c->d_atm_pc[k]) (void)hipFree(c->d_atm_pc[k]);
     for (int k = 0; k < 2; ++k)
@@ -1698,6 +1702,114 @@ int lh_step_ssprk33_adaptive(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
         }
     }
     LH_HIP(c, hipGetLastError());
+    return LH_OK;
+}
+
+int lh_step_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                           const double* bcv, double tol, int32_t max_iter) {
+    (void)t; // boundary values of t_{n+1} come through bcv or lh_set_bc, as for lh_step_ssprk33
+    if (!c) return LH_EINVAL;
+    // the statistics describe THIS call from here on, also when it is refused below
+    if (c->d_imp_stats) LH_HIP(c, hipMemsetAsync(c->d_imp_stats, 0, 24, c->stream));
+    if (nsteps < 0 || !(dt > 0)) return fail(c, LH_EINVAL, "lh_step_implicit_euler: need nsteps >= 0 and dt > 0");
+    Range r_("lh:step_implicit_euler");
+    if (c->cfg.model != LH_MODEL_RICHARDS)
+        return fail(c, LH_EMODEL, "lh_step_implicit_euler: Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)");
+    if (c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE)
+        return fail(c, LH_EMODEL, "lh_step_implicit_euler: conductivity factors other than NoEffect are not supported");
+    // (validate_model refuses a prescribed atmosphere on any model but the coupled one already; kept so
+    // that this path stays closed to it should that change)
+    if (c->hp.atmos_on) return fail(c, LH_EMODEL, "lh_step_implicit_euler: a prescribed-atmosphere top is not supported");
+    int rc = validate_model(c);
+    if (rc) return rc;
+    if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
+    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
+    (void)hipSetDevice(c->device);
+    const bool f64 = c->cfg.dtype == LH_F64;
+    if (!(tol > 0)) tol = f64 ? 1e-10 : 1e-5;
+    if (max_iter <= 0) max_iter = 50;
+    const size_t plane = size_t(c->cfg.nlev) * size_t(c->stride) * c->esize;
+    if (!c->d_imp) LH_HIP(c, hipMalloc(&c->d_imp, 3 * plane));
+    if (!c->d_imp_stats) {
+        LH_HIP(c, hipMalloc(&c->d_imp_stats, 24));
+        LH_HIP(c, hipMemsetAsync(c->d_imp_stats, 0, 24, c->stream));
+    }
+    if (nsteps == 0) return LH_OK;
+    if ((rc = materialize(c, Y, ~0u))) return rc;
+    void* d_bcv = nullptr;
+    if (bcv) { // [nsteps][2][2] doubles -> FT on the device
+        const size_t nv = size_t(nsteps) * 4;
+        std::vector<char> tmp(nv * c->esize);
+        for (size_t k = 0; k < nv; ++k) {
+            if (f64) reinterpret_cast<double*>(tmp.data())[k] = bcv[k];
+            else reinterpret_cast<float*>(tmp.data())[k] = float(bcv[k]);
+        }
+        LH_HIP(c, hipMalloc(&d_bcv, nv * c->esize));
+        hipError_t e = hipMemcpyAsync(d_bcv, tmp.data(), nv * c->esize, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // tmp is pageable host memory
+        if (e != hipSuccess) {
+            (void)hipFree(d_bcv);
+            return fail(c, LH_ENODEVICE, "boundary-value upload failed: %s", hipGetErrorString(e));
+        }
+    }
+    const bool noice = c->tune.zero != 0 && (Y->zero_mask & LH_MASK(LH_VAR_THETA_I));
+    auto go = [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        ImplicitArgs<FT> A;
+        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
+        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+        A.yn = static_cast<FT*>(c->d_imp);
+        A.cp = A.yn + size_t(c->cfg.nlev) * size_t(c->stride);
+        A.dp = A.cp + size_t(c->cfg.nlev) * size_t(c->stride);
+        A.bcv = static_cast<const FT*>(d_bcv);
+        A.dt = FT(dt);
+        A.tol = FT(tol);
+        A.max_iter = max_iter;
+        A.nsteps = nsteps;
+        A.max_iters = static_cast<int32_t*>(c->d_imp_stats);
+        A.unconverged = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->d_imp_stats) + 8);
+        A.total_iters = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->d_imp_stats) + 16);
+        launch_implicit_euler<FT>(P, A, any_percol(c), noice, c->math, c->stream);
+    };
+    if (f64) go(double(0));
+    else go(float(0));
+    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
+    hipError_t e = hipGetLastError();
+    if (d_bcv) { // the launch reads it: wait before releasing
+        const hipError_t e2 = hipStreamSynchronize(c->stream);
+        (void)hipFree(d_bcv);
+        if (e == hipSuccess) e = e2;
+    }
+    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "implicit Euler launch failed: %s", hipGetErrorString(e));
+    return LH_OK;
+}
+
+int lh_implicit_iterations(lh_ctx* c, int64_t* iterations) {
+    if (!c || !iterations) return fail(c, LH_EINVAL, "lh_implicit_iterations: NULL argument");
+    *iterations = 0;
+    if (!c->d_imp_stats) return LH_OK; // no implicit step yet
+    (void)hipSetDevice(c->device);
+    uint64_t u = 0;
+    LH_HIP(c, hipMemcpyAsync(&u, static_cast<char*>(c->d_imp_stats) + 16, 8, hipMemcpyDeviceToHost, c->stream));
+    LH_HIP(c, hipStreamSynchronize(c->stream));
+    *iterations = int64_t(u);
+    return LH_OK;
+}
+
+int lh_implicit_stats(lh_ctx* c, int32_t* max_iters, int64_t* unconverged) {
+    if (!c || !max_iters || !unconverged) return fail(c, LH_EINVAL, "lh_implicit_stats: NULL argument");
+    *max_iters = 0;
+    *unconverged = 0;
+    if (!c->d_imp_stats) return LH_OK; // no implicit step yet
+    (void)hipSetDevice(c->device);
+    char buf[16];
+    LH_HIP(c, hipMemcpyAsync(buf, c->d_imp_stats, 16, hipMemcpyDeviceToHost, c->stream));
+    LH_HIP(c, hipStreamSynchronize(c->stream));
+    memcpy(max_iters, buf, 4);
+    uint64_t u;
+    memcpy(&u, buf + 8, 8);
+    *unconverged = int64_t(u);
     return LH_OK;
 }
 

@@ -114,4 +114,21 @@ struct Planes {
     FT* v[4];
 };
 
+// lh_step_implicit_euler's launch (lh_implicit.hpp)
+template <typename FT>
+struct ImplicitArgs {
+    FT* y;               // vartheta_l plane of Y: the iterate
+    const FT* ti;        // theta_i plane (not read by the kernels that know it zero)
+    FT* yn;              // scratch planes [nlev][stride]: v_n, c', d'
+    FT* cp;
+    FT* dp;
+    const FT* bcv;       // [nsteps][2 faces][2 components] boundary values at t_{n+1}, or nullptr
+    FT dt, tol;
+    int32_t max_iter;
+    int64_t nsteps;
+    int32_t* max_iters;          // largest iteration count of any column-step
+    unsigned long long* unconverged; // column-steps that did not converge
+    unsigned long long* total_iters; // Newton iterations over all column-steps
+};
+
 } // namespace lh

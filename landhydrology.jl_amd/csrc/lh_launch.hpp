@@ -71,6 +71,10 @@ void launch_broadcast_profile(FT* plane, const FT* prof, int64_t ncols, int64_t 
 // one thread: dt = min(dt, dt_max), elapsed += dt (lh_step_ssprk33_adaptive)
 template <typename FT>
 void launch_dt_prepare(FT* dt, FT dt_max, FT* elapsed, uint32_t* status, hipStream_t s);
+// nsteps backward-Euler steps of a Richards model in one launch (lh_implicit.hpp)
+template <typename FT>
+void launch_implicit_euler(const DevParams<FT>& P, const ImplicitArgs<FT>& A, bool percol, bool noice, int math,
+                           hipStream_t s);
 template <typename FT>
 void launch_convert(FT* dst, const double* src, int64_t n, hipStream_t s);
 

@@ -429,6 +429,32 @@ function step_ssprk33_adaptive!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, cour
 end
 
 """
+    step_implicit_euler!(ens, Y, Ya, t, dt, nsteps; bcv = nothing, tol = 0.0, max_iter = 0) -> (max_iters, unconverged, iterations)
+
+`nsteps` backward-Euler steps of a Richards ensemble (lh_step_implicit_euler): per step Newton on
+`Y - Yn - dt f(Y)` with `f` exactly `rhs!`'s tendency and one tridiagonal solve per column and
+iteration.  `bcv`: `nothing` or `nsteps * 4` boundary values at `t_{n+1}` ([step][face][component]).
+`tol <= 0` / `max_iter <= 0`: the library's defaults.  Returns lh_implicit_stats of the call and the
+Newton iterations summed over its column-steps (lh_implicit_iterations).
+"""
+function step_implicit_euler!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt, nsteps;
+                              bcv = nothing, tol = 0.0, max_iter = 0)
+    set_bcs!(ens, t)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    check(ens.ctx, ccall((:lh_step_implicit_euler, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Int64, Ptr{Float64}, Float64, Int32),
+                         ens.ctx, Y.handle, ya, t, dt, nsteps, vals, tol, max_iter))
+    mi = Ref{Int32}(0)
+    nu = Ref{Int64}(0)
+    check(ens.ctx, ccall((:lh_implicit_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}),
+                         ens.ctx, mi, nu))
+    total = Ref{Int64}(0)
+    check(ens.ctx, ccall((:lh_implicit_iterations, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, total))
+    return (mi[], nu[], total[])
+end
+
+"""
     tune_placement!(ens, Y, Ya, dY = nothing; max_candidates = 0, move_input = true)
 
 Let the library place the state written by `rhs!` (`dY` given) or the SSPRK33 stage state

@@ -918,6 +918,66 @@ class SSPRK33:
     """OrdinaryDiffEq.SSPRK33 marker (the only stepper the reference's tests use)."""
 
 
+class ImplicitEuler:
+    """OrdinaryDiffEq.ImplicitEuler marker: backward Euler with Newton and one tridiagonal solve per
+    column and iteration (lh_step_implicit_euler).  Richards models without conductivity factors
+    and without a prescribed atmosphere.  tol / max_iter: None = the library's defaults."""
+
+    def __init__(self, tol=None, max_iter=None):
+        self.tol = tol
+        self.max_iter = max_iter
+
+
+def _check_implicit_scope(model):
+    """NotImplementedError for what lh_step_implicit_euler refuses (LH_EMODEL)."""
+    if not (isinstance(model.energy_model, PrescribedTemperatureModel) and
+            isinstance(model.hydrology_model, SoilHydrologyModel)):
+        raise NotImplementedError("ImplicitEuler is provided for Richards models only "
+                                  "(SoilHydrologyModel + PrescribedTemperatureModel)")
+    hm = model.hydrology_model
+    if not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
+        raise NotImplementedError("ImplicitEuler supports the NoEffect conductivity factors only")
+    bcs = model.boundary_conditions
+    if bcs is not None and isinstance(bcs.top, PrescribedAtmosForcing):
+        raise NotImplementedError("ImplicitEuler does not support a prescribed-atmosphere top")
+
+
+def _implicit_bcv(model, be, t, dt, nsteps):
+    """[nsteps][2][2] boundary values at t_{n+1} = t + (k+1) dt of every scalar Dirichlet closure
+    (None when nothing depends on time)."""
+    if not _time_dependent(model):
+        return None
+    vals = np.zeros((nsteps, 2, 2))
+    for (f, c), (kind, v) in be.bc_values(model, t).items():
+        if np.ndim(v) == 0:
+            vals[:, f, c] = float(v)
+    for k in range(nsteps):
+        for (f, c), (kind, v) in be.bc_values(model, t + (k + 1) * dt).items():
+            if kind == F.LH_BC_DIRICHLET and np.ndim(v) == 0:
+                vals[k, f, c] = float(v)
+    return np.ascontiguousarray(vals)
+
+
+def step_implicit(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0, nsteps: int = 1,
+                  tol=None, max_iter=None):
+    """Build extension: `nsteps` backward-Euler steps of `Y` (lh_step_implicit_euler): per step Newton on
+    Y - Yn - dt f(Y) = 0 with f exactly make_rhs's tendency.  Time-dependent Dirichlet closures are
+    evaluated at t_{n+1} of every step (per-column values at `t`).  Returns
+    (largest Newton iteration count of any column-step, number of column-steps that did not converge)."""
+    _check_implicit_scope(model)
+    be = model._backend()
+    L = F.lib()
+    ya = Ya.handle if isinstance(Ya, FieldVector) else None
+    bcv = _implicit_bcv(model, be, t, dt, int(nsteps))
+    be.set_bcs(model, t)
+    F.check(L.lh_step_implicit_euler(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
+                                     bcv.ctypes.data_as(C.POINTER(C.c_double)) if bcv is not None else None,
+                                     float(tol or 0.0), int(max_iter or 0)), be.ctx)
+    mi, un = C.c_int32(), C.c_int64()
+    F.check(L.lh_implicit_stats(be.ctx, C.byref(mi), C.byref(un)), be.ctx)
+    return int(mi.value), int(un.value)
+
+
 class _Solution:
     def __init__(self):
         self.t = []
@@ -946,8 +1006,11 @@ class Simulation:
 
     def __init__(self, model, method, *, Y_init, dt, tspan, Ya_init, callbacks=None, saveat=None,
                  **kwargs):
-        if not isinstance(method, SSPRK33):
-            raise NotImplementedError("only SSPRK33 is provided on the device")
+        if isinstance(method, ImplicitEuler):
+            _check_implicit_scope(model)
+        elif not isinstance(method, SSPRK33):
+            raise NotImplementedError("only SSPRK33 and ImplicitEuler are provided on the device")
+        self.method = method
         if Y_init is None:
             # simulation.jl:50 references an undefined variable here:
             # the reference cannot run this branch either.
@@ -1029,6 +1092,13 @@ def _advance_refreshing_aux(sim: Simulation, nsteps: int):
 def _advance(sim: Simulation, nsteps: int):
     it = sim.integrator
     model = sim.model
+    if isinstance(getattr(sim, "method", None), ImplicitEuler):
+        if nsteps > 0:
+            m = sim.method
+            step_implicit(model, it.u, it.p, it.t, it.dt, nsteps, m.tol, m.max_iter)
+            it._nsteps_done += nsteps
+            it.t = it.t + nsteps * it.dt
+        return
     be = model._backend()
     L = F.lib()
     ya = it.p.handle if isinstance(it.p, FieldVector) else None
