@@ -375,6 +375,37 @@ int lh_implicit_stats(lh_ctx*, int32_t* max_iters, int64_t* unconverged);
  * (divided by ncols * nsteps: the mean per column-step).  Synchronises. */
 int lh_implicit_iterations(lh_ctx*, int64_t* iterations);
 
+/* TR-BDF2 of a Richards model from t0 to t1: L-stable, second order, two
+ * stages of the form Y - w - d h f(Y) = 0 (d = (2 - sqrt 2)/2), each solved by
+ * lh_step_implicit_euler's safeguarded Newton with one tridiagonal solve per iteration.  Every
+ * column carries its own step h and its own accept/reject history (no collective): the error
+ * estimate (I - d h J)^-1 (b1 z_n + b2 z_g + b3 z_1) of Hosea & Shampine is measured in
+ * E = sqrt(mean_i (e_i / (abstol + reltol max(|Y_n,i|, |Y_1,i|)))^2); E <= 1 accepts, and
+ * h <- h clamp(0.9 E^(-1/3), 0.2, 5); a stage whose Newton does not converge within 10 iterations
+ * rejects the step and h <- h/4.  The last step lands on t1 exactly.  A column fails when h falls
+ * below 1e-10 (t1 - t0) or after 100000 attempted steps in one call: it keeps its last accepted
+ * state (at an earlier time) and sets status bit 4.
+ * dt: the initial step (flags LH_TRBDF2_FIXED: the fixed step, no error control, Newton with
+ * lh_step_implicit_euler's defaults; non-convergence sets status bit 3 and the step is kept).
+ * abstol, reltol: each one that is 0 takes its own default, 1e-6 and 1e-3 (OrdinaryDiffEq's).
+ * dt_cols_device_ft: NULL or ncols FT values in device memory: on entry each column's initial step
+ * (<= 0: dt), on exit the controller's proposal for the next call, or 0 for a failed column.  With
+ * LH_TRBDF2_FIXED the entries are not read (every column steps by dt) and receive dt.
+ * bcv: NULL (lh_set_bc's values) or 8 doubles [t0 | t1][2 faces][2 components], interpolated
+ * linearly at every stage time.  Richards models only, without conductivity factors and without a
+ * prescribed atmosphere: anything else is LH_EMODEL.  Asynchronous. */
+#define LH_TRBDF2_FIXED 1u
+int lh_integrate_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
+                        double abstol, double reltol, uint32_t flags, void* dt_cols_device_ft,
+                        const double* bcv);
+/* Of the last lh_integrate_trbdf2 call, LH_TRBDF2_NSTATS counters (zeros once a later call was
+ * refused): accepted steps, rejected steps, Newton iterations (summed over stages and columns), the
+ * largest number of attempted steps of any column, failed columns, wave_steps (the sum over waves of
+ * 64 x the wave's largest step count: what the slowest lane of each wave costs) and, in fixed-step
+ * mode, unconverged stages.  Synchronises. */
+#define LH_TRBDF2_NSTATS 7
+int lh_trbdf2_stats(lh_ctx*, int64_t* stats);
+
 /* Build-defined stable step (the reference uses a fixed user dt):
  * courant*dz^2 / max over owned faces of the face diffusivities
  * ((K_lo+K_hi)/2 * max dpsi/dvl, (kappa_lo+kappa_hi)/2 / min rho_c_s; boundary
@@ -423,7 +454,9 @@ int lh_allreduce_min(lh_ctx*, void* value_device_ft);
  * prescribed-atmosphere BC had no root in some column; bit 2: a step of
  * lh_step_ssprk33_adaptive found no positive finite step bound (no positive diffusivity anywhere and
  * no dt_max, or a NaN) and was taken with dt = 0; bit 3: an implicit step (lh_step_implicit_euler)
- * did not converge in some column; synchronises and clears. */
+ * did not converge in some column (also the fixed-step mode of lh_integrate_trbdf2); bit 4: a column
+ * of lh_integrate_trbdf2 failed (its step fell below the floor or it hit the step cap) and did not
+ * reach t1; synchronises and clears. */
 int lh_get_status(lh_ctx*, uint32_t* flags);
 int lh_synchronize(lh_ctx*);
 /* Streaming ceiling of the column launch on a given set of planes (measurement aid, no

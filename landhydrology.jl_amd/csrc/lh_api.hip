@@ -102,6 +102,9 @@ struct lh_ctx {
     lh_state* scratch_k1 = nullptr;    // f(Y) of lh_step_ssprk33_adaptive
     void* d_imp = nullptr;             // lh_step_implicit_euler: three FT planes [nlev][stride] (v_n, c', d')
     void* d_imp_stats = nullptr;       // ... and its statistics: int32 max iterations, uint64 unconverged, uint64 iterations
+    void* d_tr = nullptr;              // lh_integrate_trbdf2: six FT planes [nlev][stride] (Y_n, f_n, Y_gamma, w, c', d')
+    void* d_tr_stats = nullptr;        // ... and its LH_TRBDF2_NSTATS uint64 counters
+    void* d_tr_f = nullptr;            // ... two more planes when the error solve reuses stage 2's factorisation
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
     Tune tune;
@@ -346,6 +349,9 @@ void parse_tune(Tune& tu, const char* t) {
     if ((q = strstr(t, "zero=")) && sscanf(q + 5, "%d", &v) == 1 && (v == 0 || v == 1)) tu.zero = v;
     if ((q = strstr(t, "xcd=")) && sscanf(q + 4, "%d", &v) == 1 && (v == 0 || v == 1)) tu.xcd = v;
     if ((q = strstr(t, "vgfast=")) && sscanf(q + 7, "%d", &v) == 1 && (v == 0 || v == 1)) tu.vgfast = v;
+    if ((q = strstr(t, "trk=")) && sscanf(q + 4, "%d", &v) == 1 && v >= 1 && v <= 10000) tu.trk = v;
+    if ((q = strstr(t, "trn=")) && sscanf(q + 4, "%d", &v) == 1 && v >= 1 && v <= 100) tu.trn = v;
+    if ((q = strstr(t, "trf=")) && sscanf(q + 4, "%d", &v) == 1 && (v == 0 || v == 1)) tu.trf = v;
     if ((q = strstr(t, "block=")) && sscanf(q + 6, "%d", &v) == 1 && v >= 64 && v <= 1024 && v % 64 == 0) tu.block = v;
     if ((q = strstr(t, "cpl=")) && sscanf(q + 4, "%d", &v) == 1) tu.cpl = v;
     if ((q = strstr(t, "pf=")) && sscanf(q + 3, "%d", &v) == 1) tu.pf = v;
@@ -1087,6 +1093,9 @@ int lh_destroy(lh_ctx* c) {
     if (c->d_dt) (void)hipFree(c->d_dt);
     if (c->d_imp) (void)hipFree(c->d_imp);
     if (c->d_imp_stats) (void)hipFree(c->d_imp_stats);
+    if (c->d_tr) (void)hipFree(c->d_tr);
+    if (c->d_tr_stats) (void)hipFree(c->d_tr_stats);
+    if (c->d_tr_f) (void)hipFree(c->d_tr_f);
     for (int k = 0; k < 3; ++k)
         if (c->d_atm_pc[k]) (void)hipFree(c->d_atm_pc[k]);
     for (int k = 0; k < 2; ++k)
@@ -1810,6 +1819,111 @@ int lh_implicit_stats(lh_ctx* c, int32_t* max_iters, int64_t* unconverged) {
     uint64_t u;
     memcpy(&u, buf + 8, 8);
     *unconverged = int64_t(u);
+    return LH_OK;
+}
+
+// lh_integrate_trbdf2's defaults (LH_TUNE trk= / trn= override the Newton pair, and
+// trf=1 selects the error solve with stage 2's factorisation in tuning builds)
+#define LH_TRBDF2_ABSTOL_DEFAULT 1e-6
+#define LH_TRBDF2_RELTOL_DEFAULT 1e-3
+#define LH_TRBDF2_NEWTON_KAPPA 0.01 // stage Newton test: max |delta| / (atol + rtol |Y|) <= this ...
+#define LH_TRBDF2_NEWTON_MAX 10     // ... within this many iterations, else the step is rejected
+
+int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
+                        double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    if (!c) return LH_EINVAL;
+    const size_t nstat = LH_TRBDF2_NSTATS * sizeof(uint64_t);
+    // the statistics describe THIS call from here on, also when it is refused below
+    if (c->d_tr_stats) LH_HIP(c, hipMemsetAsync(c->d_tr_stats, 0, nstat, c->stream));
+    if (!std::isfinite(t0) || !std::isfinite(t1) || !(t1 >= t0))
+        return fail(c, LH_EINVAL, "lh_integrate_trbdf2: need finite t0 <= t1");
+    if (!std::isfinite(dt) || !(dt > 0)) return fail(c, LH_EINVAL, "lh_integrate_trbdf2: need a finite dt > 0");
+    if (!std::isfinite(abstol) || !std::isfinite(reltol) || abstol < 0 || reltol < 0)
+        return fail(c, LH_EINVAL, "lh_integrate_trbdf2: tolerances must be finite and >= 0");
+    if (flags & ~LH_TRBDF2_FIXED) return fail(c, LH_EINVAL, "lh_integrate_trbdf2: unknown flags 0x%x", flags);
+    if (bcv)
+        for (int k = 0; k < 8; ++k)
+            if (!std::isfinite(bcv[k])) return fail(c, LH_EINVAL, "lh_integrate_trbdf2: non-finite boundary value");
+    Range r_("lh:integrate_trbdf2");
+    if (c->cfg.model != LH_MODEL_RICHARDS)
+        return fail(c, LH_EMODEL, "lh_integrate_trbdf2: Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)");
+    if (c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE)
+        return fail(c, LH_EMODEL, "lh_integrate_trbdf2: conductivity factors other than NoEffect are not supported");
+    if (c->hp.atmos_on) return fail(c, LH_EMODEL, "lh_integrate_trbdf2: a prescribed-atmosphere top is not supported");
+    int rc = validate_model(c);
+    if (rc) return rc;
+    if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
+    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
+    (void)hipSetDevice(c->device);
+    const bool f64 = c->cfg.dtype == LH_F64;
+    const bool fixed = (flags & LH_TRBDF2_FIXED) != 0;
+    // each tolerance that is 0 takes its own default (OrdinaryDiffEq's)
+    if (!(abstol > 0)) abstol = LH_TRBDF2_ABSTOL_DEFAULT;
+    if (!(reltol > 0)) reltol = LH_TRBDF2_RELTOL_DEFAULT;
+#ifdef LH_TUNING_VARIANTS
+    const bool reuse = c->tune.trf > 0; // (measured slower than re-forming J at Y_1: tuning builds only)
+#else
+    const bool reuse = false;
+#endif
+    const size_t plane = size_t(c->cfg.nlev) * size_t(c->stride) * c->esize;
+    if (!c->d_tr) LH_HIP(c, hipMalloc(&c->d_tr, 6 * plane));
+    if (reuse && !c->d_tr_f) LH_HIP(c, hipMalloc(&c->d_tr_f, 2 * plane));
+    if (!c->d_tr_stats) {
+        LH_HIP(c, hipMalloc(&c->d_tr_stats, nstat));
+        LH_HIP(c, hipMemsetAsync(c->d_tr_stats, 0, nstat, c->stream));
+    }
+    if (t1 == t0) return LH_OK;
+    if ((rc = materialize(c, Y, ~0u))) return rc;
+    const bool noice = c->tune.zero != 0 && (Y->zero_mask & LH_MASK(LH_VAR_THETA_I));
+    auto go = [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        Trbdf2Args<FT> A;
+        const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
+        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+        A.yn = static_cast<FT*>(c->d_tr);
+        A.fn = A.yn + pl;
+        A.yg = A.fn + pl;
+        A.w = A.yg + pl;
+        A.cp = A.w + pl;
+        A.dp = A.cp + pl;
+        A.dt_cols = static_cast<FT*>(dt_cols_device_ft);
+        A.t0 = t0;
+        A.t1 = t1;
+        A.dt = dt;
+        A.abstol = abstol;
+        A.reltol = reltol;
+        A.has_bcv = bcv != nullptr;
+        for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
+        A.fixed = fixed;
+        A.tol = FT(f64 ? 1e-10 : 1e-5); // (fixed mode: lh_step_implicit_euler's defaults)
+        A.max_iter = 50;
+        A.kappa = FT(c->tune.trk > 0 ? 1e-4 * c->tune.trk : LH_TRBDF2_NEWTON_KAPPA);
+        A.newton_max = c->tune.trn > 0 ? c->tune.trn : LH_TRBDF2_NEWTON_MAX;
+        A.reuse = reuse;
+        A.fa = reuse ? static_cast<FT*>(c->d_tr_f) : nullptr;
+        A.fden = reuse ? A.fa + pl : nullptr;
+        A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
+        launch_trbdf2<FT>(P, A, any_percol(c), noice, c->math, c->stream);
+    };
+    if (f64) go(double(0));
+    else go(float(0));
+    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "TR-BDF2 launch failed: %s", hipGetErrorString(e));
+    return LH_OK;
+}
+
+int lh_trbdf2_stats(lh_ctx* c, int64_t* stats) {
+    if (!c || !stats) return fail(c, LH_EINVAL, "lh_trbdf2_stats: NULL argument");
+    for (int k = 0; k < LH_TRBDF2_NSTATS; ++k) stats[k] = 0;
+    if (!c->d_tr_stats) return LH_OK; // no TR-BDF2 call yet
+    (void)hipSetDevice(c->device);
+    uint64_t u[LH_TRBDF2_NSTATS];
+    LH_HIP(c, hipMemcpyAsync(u, c->d_tr_stats, sizeof(u), hipMemcpyDeviceToHost, c->stream));
+    LH_HIP(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < LH_TRBDF2_NSTATS; ++k) stats[k] = int64_t(u[k]);
     return LH_OK;
 }
 

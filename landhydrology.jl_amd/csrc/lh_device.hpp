@@ -131,4 +131,35 @@ struct ImplicitArgs {
     unsigned long long* total_iters; // Newton iterations over all column-steps
 };
 
+// lh_integrate_trbdf2's launch (lh_implicit.hpp)
+template <typename FT>
+struct Trbdf2Args {
+    FT* y;               // vartheta_l plane of Y: the column's state, and the stage iterates
+    const FT* ti;        // theta_i plane (not read by the kernels that know it zero)
+    FT* yn;              // scratch planes [nlev][stride]: Y_n, f_n, Y_gamma, the stage's w, c', d'
+    FT* fn;
+    FT* yg;
+    FT* w;
+    FT* cp;
+    FT* dp;
+    FT* dt_cols;         // [ncols] per-column step in / proposal out (0: failed), or nullptr
+    double t0, t1, dt;   // the call's interval; dt: the initial (adaptive) or the fixed step
+    double abstol, reltol;
+    double bcv[8];       // [t0 | t1][2 faces][2 components], linear in between (has_bcv)
+    int32_t has_bcv;
+    int32_t fixed;       // LH_TRBDF2_FIXED: steps of dt, no error control, backward Euler's Newton test
+    FT tol;              // (fixed) Newton tolerance and cap, as lh_step_implicit_euler
+    int32_t max_iter;
+    FT kappa;            // (adaptive) stage Newton test max |delta| / (atol + rtol |Y|) <= kappa ...
+    int32_t newton_max;  // ... within newton_max iterations, else the step is rejected
+    int32_t reuse;       // error solve with stage 2's last factorisation (fa, fden, cp) instead of J re-formed at Y_1
+    FT* fa;              // (reuse) two more scratch planes: a_i and the pivots of that factorisation
+    FT* fden;
+    unsigned long long* stats; // accepted, rejected, Newton iterations, max steps, failed, wave_steps, unconverged
+};
+// one column's counters of a call (reduced over the wave)
+struct Trbdf2ColStats {
+    unsigned accepted = 0, rejected = 0, iters = 0, steps = 0, failed = 0, unconv = 0;
+};
+
 } // namespace lh

@@ -1,4 +1,6 @@
-// lh_implicit.hpp -- backward-Euler steps of the Richards model on gfx950 (lh_step_implicit_euler).
+// lh_implicit.hpp -- backward-Euler steps (lh_step_implicit_euler) and adaptive TR-BDF2
+// (lh_integrate_trbdf2, below) of the Richards model on gfx950.  Both solve stage equations
+// Y - w - coef f(Y) = 0 with the same Newton (newton_stage); backward Euler's is w = v_n, coef = dt.
 //
 // Per step and column, Newton on R(v) = v - v_n - dt f(v) = 0, where f is EXACTLY the tendency of
 // rhs_kernel (the same water_closures, face expressions and boundary_fluxes, in the same order), and
@@ -13,7 +15,8 @@
 // The Jacobian is approximate (slopes in Float32, water_slopes); R always uses the exact f.
 #pragma once
 #include "lh_closures.hpp"
-// (included after lh_kernels_impl.hpp: grid_for, stage_math_tables, fmin_ft / fmax_ft; ImplicitArgs is in lh_device.hpp)
+// (included after lh_kernels_impl.hpp: grid_for, stage_math_tables, fmin_ft / fmax_ft; ImplicitArgs and
+// Trbdf2Args are in lh_device.hpp)
 
 namespace lh {
 
@@ -27,6 +30,11 @@ namespace lh {
 // previous one, the next update is scaled by half the current factor (down to 1/16); after a step that
 // did shrink the factor doubles back towards 1
 #define LH_IMPLICIT_STALL 0.9
+// TR-BDF2 (lh_integrate_trbdf2)
+// (the stage's Newton test max |delta| / (atol + rtol |Y|) <= kappa and its iteration cap are Trbdf2Args
+// fields: defaults and measurements in lh_api.hip and DESIGN section 4.13)
+#define LH_TRBDF2_MAX_STEPS 100000    // attempted steps per column and call before the column fails
+#define LH_TRBDF2_HMIN_FRAC 1e-10     // a column whose h falls below this x (t1 - t0) fails
 
 // d K_r / d vl (relative conductivity) and d(-psi) / d vl of one cell, in Float32 whatever FT is:
 // they only enter the Jacobian.  With t = S^(1/m), w = 1 - t, inner = 1 - w^m:
@@ -84,32 +92,185 @@ constexpr int implicit_threads() {
     return M::uses_tables ? 512 : 256; // (the Float64 tables take 48 KiB of LDS per workgroup)
 }
 
+// The column's constants of one solve: ColC, the K and conductance scales of rhs_kernel's
+// instantiation, the safeguard's bound
+template <typename FT, typename M, bool PERCOL, bool NOICE>
+struct ColumnSolve {
+    static constexpr bool RELK = M::is_production; // K without Ksat, as rhs_kernel carries it
+    ColC<FT> c;
+    FT Ksc, cgw, dmax, floor_r;
+    __device__ __forceinline__ ColumnSolve(const M& mm, const DevParams<FT>& P, int64_t col) {
+        c = make_colc<FT, M>(P, col, PERCOL);
+        if (!NOICE) finish_colc<FT, M>(mm, c);
+        Ksc = RELK ? c.Ksat : FT(1);
+        cgw = RELK ? c.cgw : P.cg2;
+        dmax = FT(LH_IMPLICIT_DMAX_FRAC) * (c.nu - c.theta_r);
+        floor_r = c.theta_r;
+    }
+};
+
+// One upward sweep over a column at the iterate y: the closures of cell i+1 in a rolling window of two
+// cells, the face fluxes exactly as rhs_kernel forms them, and f_i = F_lo - F_hi.  row(idx, v_i, f_i)
+// returns R_i; with JAC the sweep also forms row i of J = I - coef df/dv and eliminates forward
+// (c'_i, d'_i of J x = -R to cp, dp); without it, row only sees f (the tendency).
+// With STORE the sweep also keeps a_i and the pivot den_i (planes sa, sden): with cp they are the whole
+// factorisation, for TR-BDF2's error solve at the end of stage 2 (Trbdf2Args::reuse).
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool JAC, typename Row, bool STORE = false>
+__device__ __forceinline__ void column_sweep_up(const M& mm, const DevParams<FT>& P,
+                                                const ColumnSolve<FT, M, PERCOL, NOICE>& S, const FaceState<FT>& fsb,
+                                                const FaceState<FT>& fst, int64_t col, const FT* y, const FT* ti,
+                                                FT ti_b, FT coef, FT* cp, FT* dp, Row&& row, FT* sa = nullptr,
+                                                FT* sden = nullptr) {
+    constexpr bool RELK = ColumnSolve<FT, M, PERCOL, NOICE>::RELK;
+    constexpr bool vgf = VGF && M::uses_tables;
+    const ColC<FT>& c = S.c;
+    const FT Ksc = S.Ksc, cgw = S.cgw;
+    const int n = P.nlev;
+    const int64_t stride = P.stride;
+    const FT T = FT(288); // (read by nothing: no conductivity factors on this path)
+    auto closures = [&](FT v, FT tiv, FT& K, FT& np, FT& dK, FT& dn) {
+        water_closures<FT, M, false, true, false, NOICE, RELK, false, true>(mm, P, c, v, tiv, T, K, np, nullptr, vgf);
+        if constexpr (JAC) {
+            float dkr, dnf;
+            water_slopes<FT, NOICE>(c, v, tiv, np, dkr, dnf);
+            dK = FT(dkr) * (RELK ? FT(1) : c.Ksat); // in the units of K
+            dn = FT(dnf);
+        }
+    };
+    int64_t idx = col;
+    FT v = y[idx];
+    FT K, np, dK = FT(0), dn = FT(0);
+    closures(v, NOICE ? FT(0) : ti_b, K, np, dK, dn);
+    FT Flo, dFlo_lo = FT(0), dFlo_c = FT(0);
+    {
+        FT fe, fw;
+        boundary_fluxes_from<FT, MODEL_RICHARDS>(P, fsb, FACE_BOTTOM, col, T, K * Ksc, -np, fe, fw);
+        Flo = fw * P.inv_dz;
+        if constexpr (JAC) dFlo_c = boundary_flux_slope<FT>(P, fsb, FACE_BOTTOM, dK * Ksc, dn) * P.inv_dz;
+    }
+    FT cp_prev = FT(0), dp_prev = FT(0);
+    for (int i = 0; i < n; ++i) {
+        FT Fhi, dFhi_c = FT(0), dFhi_u = FT(0);
+        FT vu = FT(0), tiu = FT(0), Ku = FT(0), npu = FT(0), dKu = FT(0), dnu = FT(0);
+        const int64_t idu = idx + stride;
+        if (i + 1 < n) {
+            vu = y[idu];
+            tiu = NOICE ? FT(0) : ti[idu];
+            closures(vu, tiu, Ku, npu, dKu, dnu);
+            // rhs_kernel's interior face: -(K_lo + K_hi) ((npsi_lo - npsi_hi) + dz) cgw
+            const FT h = head_difference(npu, np, P.dz);
+            const FT Ks = K + Ku;
+            Fhi = -Ks * (h * cgw);
+            if constexpr (JAC) {
+                dFhi_c = -cgw * (dK * h + Ks * dn);
+                dFhi_u = -cgw * (dKu * h - Ks * dnu);
+            }
+        } else {
+            FT fe, fw;
+            boundary_fluxes_from<FT, MODEL_RICHARDS>(P, fst, FACE_TOP, col, T, K * Ksc, -np, fe, fw);
+            Fhi = fw * P.inv_dz;
+            if constexpr (JAC) dFhi_c = boundary_flux_slope<FT>(P, fst, FACE_TOP, dK * Ksc, dn) * P.inv_dz;
+        }
+        const FT R = row(idx, v, Flo - Fhi); // f_i = F_lo - F_hi, rhs_kernel's emit
+        if constexpr (JAC) {
+            const FT a = -coef * dFlo_lo;
+            const FT b = FT(1) - coef * (dFlo_c - dFhi_c);
+            const FT cc = coef * dFhi_u;
+            const FT den = b - a * cp_prev;
+            const FT cpi = cc / den;
+            const FT dpi = (-R - a * dp_prev) / den;
+            cp[idx] = cpi;
+            dp[idx] = dpi;
+            if constexpr (STORE) {
+                sa[idx] = a;
+                sden[idx] = den;
+            }
+            cp_prev = cpi;
+            dp_prev = dpi;
+        }
+        // slide the window: the face above becomes the face below
+        Flo = Fhi;
+        dFlo_lo = dFhi_c;
+        dFlo_c = dFhi_u;
+        v = vu; K = Ku; np = npu; dK = dKu; dn = dnu;
+        idx = idu;
+    }
+}
+
+// The Newton solve of one stage equation Y - w - coef f(Y) = 0 in one column: backward Euler's
+// (w = v_n, coef = dt) and both TR-BDF2 stages'.  y holds the initial guess and receives the iterate;
+// with WFIRST the first upward sweep copies y into w (backward Euler's v_n).  Convergence, per column:
+// backward Euler's max_i |delta_i| <= tol max(|v_i|, nu), or with ADAPT
+// max_i |delta_i| / (atol + rtol |v_i|) <= kappa.  Returns the iteration count.
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool WFIRST, bool ADAPT, bool STORE = false>
+__device__ __forceinline__ int newton_stage(const M& mm, const DevParams<FT>& P,
+                                            const ColumnSolve<FT, M, PERCOL, NOICE>& S, const FaceState<FT>& fsb,
+                                            const FaceState<FT>& fst, int64_t col, FT* y, const FT* ti, FT ti_b,
+                                            FT* w, FT* cp, FT* dp, FT coef, FT tol, FT atol, FT rtol, int max_iter,
+                                            bool& conv, FT kappa = FT(0), FT* sa = nullptr, FT* sden = nullptr) {
+    const ColC<FT>& c = S.c;
+    const int n = P.nlev;
+    const FT dmax = S.dmax, floor_r = S.floor_r;
+    conv = false;
+    int it = 0;
+    FT lam = FT(1);                 // step length of the safeguard (see LH_IMPLICIT_STALL)
+    FT dprev = FT(INFINITY);        // largest |Newton step| of the previous iteration
+    while (it < max_iter && !conv) {
+        // ---------------- upward sweep
+        auto row = [&](int64_t idx, FT v, FT f) {
+            FT vn;
+            if (WFIRST && it == 0) { vn = v; w[idx] = v; } else vn = w[idx];
+            return (v - vn) - coef * f;
+        };
+        column_sweep_up<FT, M, PERCOL, NOICE, VGF, true, decltype(row)&, STORE>(mm, P, S, fsb, fst, col, y, ti, ti_b,
+                                                                               coef, cp, dp, row, sa, sden);
+        // ---------------- downward sweep
+        FT dnext = FT(0);
+        bool ok = true;
+        FT dbig = FT(0);
+        for (int i = n - 1; i >= 0; --i) {
+            const int64_t id = int64_t(i) * P.stride + col;
+            const FT d = dp[id] - cp[id] * dnext; // (c'_{n-1} = 0)
+            dnext = d;
+            const FT vo = y[id];
+            const FT du = fmin_ft(fmax_ft(lam * d, -dmax), dmax);
+            FT vnew = vo + du;
+            const FT fl = floor_r + FT(0.5) * (vo - floor_r);
+            if (vo > floor_r) vnew = vnew < fl ? fl : vnew; // at most half way down to theta_r
+            else vnew = vnew < vo ? vo : vnew;              // (at or below it already: no further)
+            // the saturation kink: a cell that crosses nu_eff from below stops on it (psi' has no
+            // bound just below, and a Newton step across it oscillates)
+            const FT nue = NOICE ? c.nu : c.nu - ti[id];
+            if (vo < nue && vnew > nue) vnew = nue;
+            y[id] = vnew;
+            // judged on the Newton step itself: a step the safeguard cut short is not convergence
+            const FT av = vnew < FT(0) ? -vnew : vnew;
+            const FT ad = d < FT(0) ? -d : d;
+            if (ADAPT) ok = ok && (ad <= kappa * (atol + rtol * av));
+            else ok = ok && (ad <= tol * fmax_ft(av, c.nu));
+            dbig = ad > dbig ? ad : dbig;
+        }
+        conv = ok;
+        // a Newton step that has not shrunk (a cycle across the saturation kink): shorten the next
+        // one; while the steps shrink, full steps again -- near the solution every step is a full
+        // Newton step and the convergence stays quadratic
+        lam = (dbig > FT(LH_IMPLICIT_STALL) * dprev) ? fmax_ft(FT(0.5) * lam, FT(1.0 / 16)) : fmin_ft(FT(2) * lam, FT(1));
+        dprev = dbig;
+        ++it;
+    }
+    return it;
+}
+
 // One column (lane) through all steps of the call: the column's largest iteration count, its
 // unconverged steps and its total iterations are returned for the launch's statistics.
 template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF>
 __device__ __forceinline__ void implicit_column(const M& mm, DevParams<FT> P, const ImplicitArgs<FT>& A, int64_t col,
                                                 int& my_max, unsigned long long& unconv, unsigned long long& total) {
-    constexpr bool RELK = M::is_production; // K without Ksat, as rhs_kernel carries it
     constexpr bool vgf = VGF && M::uses_tables;
-    ColC<FT> c = make_colc<FT, M>(P, col, PERCOL);
-    if (!NOICE) finish_colc<FT, M>(mm, c);
-    const FT Ksc = RELK ? c.Ksat : FT(1);
-    const FT cgw = RELK ? c.cgw : P.cg2;
+    const ColumnSolve<FT, M, PERCOL, NOICE> S(mm, P, col);
     const int n = P.nlev;
     const int64_t stride = P.stride;
     const FT T = FT(288); // (read by nothing: no conductivity factors on this path)
-    const FT dt = A.dt;
-    const FT dmax = FT(LH_IMPLICIT_DMAX_FRAC) * (c.nu - c.theta_r);
-    const FT floor_r = c.theta_r;
-
-    auto closures = [&](FT v, FT tiv, FT& K, FT& np, FT& dK, FT& dn) {
-        water_closures<FT, M, false, true, false, NOICE, RELK, false, true>(mm, P, c, v, tiv, T, K, np, nullptr, vgf);
-        float dkr, dnf;
-        water_slopes<FT, NOICE>(c, v, tiv, np, dkr, dnf);
-        dK = FT(dkr) * (RELK ? FT(1) : c.Ksat); // in the units of K
-        dn = FT(dnf);
-    };
-
     for (int64_t s = 0; s < A.nsteps; ++s) {
         if (A.bcv) {
             const FT* b = A.bcv + s * 4;
@@ -123,101 +284,11 @@ __device__ __forceinline__ void implicit_column(const M& mm, DevParams<FT> P, co
         // boundary_fluxes_from, so the fluxes are bitwise its own
         const FT ti_b = NOICE ? FT(0) : A.ti[col];
         const FT ti_t = NOICE ? FT(0) : A.ti[int64_t(n - 1) * stride + col];
-        const FaceState<FT> fsb = face_state<FT, M, MODEL_RICHARDS, false, NOICE>(mm, P, c, FACE_BOTTOM, col, FT(0), ti_b, T, vgf);
-        const FaceState<FT> fst = face_state<FT, M, MODEL_RICHARDS, false, NOICE>(mm, P, c, FACE_TOP, col, FT(0), ti_t, T, vgf);
-        bool conv = false;
-        int it = 0;
-        FT lam = FT(1);                 // step length of the safeguard (see LH_IMPLICIT_STALL)
-        FT dprev = FT(INFINITY);        // largest |Newton step| of the previous iteration
-        while (it < A.max_iter && !conv) {
-            // ---------------- upward sweep
-            int64_t idx = col;
-            FT v = A.y[idx];
-            FT tic = NOICE ? FT(0) : ti_b;
-            FT vn;
-            if (it == 0) { vn = v; A.yn[idx] = v; } else vn = A.yn[idx];
-            FT K, np, dK, dn;
-            closures(v, tic, K, np, dK, dn);
-            FT Flo, dFlo_lo = FT(0), dFlo_c;
-            {
-                FT fe, fw;
-                boundary_fluxes_from<FT, MODEL_RICHARDS>(P, fsb, FACE_BOTTOM, col, T, K * Ksc, -np, fe, fw);
-                Flo = fw * P.inv_dz;
-                dFlo_c = boundary_flux_slope<FT>(P, fsb, FACE_BOTTOM, dK * Ksc, dn) * P.inv_dz;
-            }
-            FT cp_prev = FT(0), dp_prev = FT(0);
-            for (int i = 0; i < n; ++i) {
-                FT Fhi, dFhi_c, dFhi_u = FT(0);
-                FT vu = FT(0), vnu = FT(0), tiu = FT(0), Ku = FT(0), npu = FT(0), dKu = FT(0), dnu = FT(0);
-                const int64_t idu = idx + stride;
-                if (i + 1 < n) {
-                    vu = A.y[idu];
-                    tiu = NOICE ? FT(0) : A.ti[idu];
-                    if (it == 0) { vnu = vu; A.yn[idu] = vu; } else vnu = A.yn[idu];
-                    closures(vu, tiu, Ku, npu, dKu, dnu);
-                    // rhs_kernel's interior face: -(K_lo + K_hi) ((npsi_lo - npsi_hi) + dz) cgw
-                    const FT h = head_difference(npu, np, P.dz);
-                    const FT Ks = K + Ku;
-                    Fhi = -Ks * (h * cgw);
-                    dFhi_c = -cgw * (dK * h + Ks * dn);
-                    dFhi_u = -cgw * (dKu * h - Ks * dnu);
-                } else {
-                    FT fe, fw;
-                    boundary_fluxes_from<FT, MODEL_RICHARDS>(P, fst, FACE_TOP, col, T, K * Ksc, -np, fe, fw);
-                    Fhi = fw * P.inv_dz;
-                    dFhi_c = boundary_flux_slope<FT>(P, fst, FACE_TOP, dK * Ksc, dn) * P.inv_dz;
-                }
-                const FT R = (v - vn) - dt * (Flo - Fhi); // f_i = F_lo - F_hi, rhs_kernel's emit
-                const FT a = -dt * dFlo_lo;
-                const FT b = FT(1) - dt * (dFlo_c - dFhi_c);
-                const FT cc = dt * dFhi_u;
-                const FT den = b - a * cp_prev;
-                const FT cpi = cc / den;
-                const FT dpi = (-R - a * dp_prev) / den;
-                A.cp[idx] = cpi;
-                A.dp[idx] = dpi;
-                cp_prev = cpi;
-                dp_prev = dpi;
-                // slide the window: the face above becomes the face below
-                Flo = Fhi;
-                dFlo_lo = dFhi_c;
-                dFlo_c = dFhi_u;
-                v = vu; vn = vnu; K = Ku; np = npu; dK = dKu; dn = dnu;
-                idx = idu;
-            }
-            // ---------------- downward sweep
-            FT dnext = FT(0);
-            bool ok = true;
-            FT dbig = FT(0);
-            for (int i = n - 1; i >= 0; --i) {
-                const int64_t id = int64_t(i) * stride + col;
-                const FT d = A.dp[id] - A.cp[id] * dnext; // (c'_{n-1} = 0)
-                dnext = d;
-                const FT vo = A.y[id];
-                const FT du = fmin_ft(fmax_ft(lam * d, -dmax), dmax);
-                FT vnew = vo + du;
-                const FT fl = floor_r + FT(0.5) * (vo - floor_r);
-                if (vo > floor_r) vnew = vnew < fl ? fl : vnew; // at most half way down to theta_r
-                else vnew = vnew < vo ? vo : vnew;              // (at or below it already: no further)
-                // the saturation kink: a cell that crosses nu_eff from below stops on it (psi' has no
-                // bound just below, and a Newton step across it oscillates)
-                const FT nue = NOICE ? c.nu : c.nu - A.ti[id];
-                if (vo < nue && vnew > nue) vnew = nue;
-                A.y[id] = vnew;
-                // judged on the Newton step itself: a step the safeguard cut short is not convergence
-                const FT scale = fmax_ft(vnew < FT(0) ? -vnew : vnew, c.nu);
-                const FT ad = d < FT(0) ? -d : d;
-                ok = ok && (ad <= A.tol * scale);
-                dbig = ad > dbig ? ad : dbig;
-            }
-            conv = ok;
-            // a Newton step that has not shrunk (a cycle across the saturation kink): shorten the next
-            // one; while the steps shrink, full steps again -- near the solution every step is a full
-            // Newton step and the convergence stays quadratic
-            lam = (dbig > FT(LH_IMPLICIT_STALL) * dprev) ? fmax_ft(FT(0.5) * lam, FT(1.0 / 16)) : fmin_ft(FT(2) * lam, FT(1));
-            dprev = dbig;
-            ++it;
-        }
+        const FaceState<FT> fsb = face_state<FT, M, MODEL_RICHARDS, false, NOICE>(mm, P, S.c, FACE_BOTTOM, col, FT(0), ti_b, T, vgf);
+        const FaceState<FT> fst = face_state<FT, M, MODEL_RICHARDS, false, NOICE>(mm, P, S.c, FACE_TOP, col, FT(0), ti_t, T, vgf);
+        bool conv;
+        const int it = newton_stage<FT, M, PERCOL, NOICE, VGF, true, false>(
+            mm, P, S, fsb, fst, col, A.y, A.ti, ti_b, A.yn, A.cp, A.dp, A.dt, A.tol, FT(0), FT(0), A.max_iter, conv);
         my_max = it > my_max ? it : my_max;
         total += unsigned(it);
         if (!conv) ++unconv;
@@ -277,7 +348,255 @@ void launch_implicit_euler(const DevParams<FT>& P, const ImplicitArgs<FT>& A, bo
 #undef LH_IE
 }
 
-#define LH_INSTANTIATE_IMPLICIT(FT) \
-    template void launch_implicit_euler<FT>(const DevParams<FT>&, const ImplicitArgs<FT>&, bool, bool, int, hipStream_t);
+// ---------------------------------------------------------------------------------------------------
+// TR-BDF2 (lh_integrate_trbdf2): per column and step, with gamma = 2 - sqrt(2),
+// d = gamma/2, h the column's step and f the tendency above,
+//   stage 1 (trapezoid): Y_g - w1 - d h f(Y_g) = 0,  w1 = Y_n + d h f_n               at t + gamma h
+//   stage 2 (BDF2):      Y_1 - w2 - d h f(Y_1) = 0,  w2 = (Y_g - (1-gamma)^2 Y_n) / (gamma (2-gamma))  at t + h
+// both solved by newton_stage.  The stage derivatives come from the converged stage equations,
+// z = (Y - w) / d, and f_{n+1} = z_1 / h is the next step's f_n (first same as last).  Error estimate
+// (Hosea & Shampine 1996): e = (I - d h J(Y_1))^-1 (b1 h f_n + b2 z_g + b3 z_1), one more upward sweep
+// at Y_1 and a back substitution that only accumulates the norm
+//   E = sqrt(mean_i (e_i / (atol + rtol max(|Y_n,i|, |Y_1,i|)))^2);
+// accepted when E <= 1, h <- h clamp(0.9 E^(-1/3), 0.2, 5); a stage whose Newton does not converge in
+// A.newton_max iterations rejects the step with h <- h/4.  Each lane carries its own t and h
+// (double) and its own accept/reject history: no collective.
+
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF>
+__device__ __forceinline__ void trbdf2_column(const M& mm, DevParams<FT> P, const Trbdf2Args<FT>& A, int64_t col,
+                                              Trbdf2ColStats& st) {
+    constexpr bool vgf = VGF && M::uses_tables;
+    const ColumnSolve<FT, M, PERCOL, NOICE> S(mm, P, col);
+    const int n = P.nlev;
+    const int64_t stride = P.stride;
+    const FT T = FT(288);
+    const double gam = 2.0 - 1.4142135623730951, dg = 0.5 * gam;
+    const FT c_yn = FT((1.0 - gam) * (1.0 - gam)), c_w2 = FT(1.0 / (gam * (2.0 - gam)));
+    const FT b1 = FT((1.0 - 1.4142135623730951) / 3.0), b2 = FT(1.0 / 3.0), b3 = FT((1.4142135623730951 - 2.0) / 3.0);
+    const FT inv_d = FT(1.0 / dg);
+    const FT atol = FT(A.abstol), rtol = FT(A.reltol);
+    const FT ti_b = NOICE ? FT(0) : A.ti[col];
+    const FT ti_t = NOICE ? FT(0) : A.ti[int64_t(n - 1) * stride + col];
+    FaceState<FT> fsb, fst;
+    // boundary values at time t: linear in t between the call's two ends (or lh_set_bc's constants), and
+    // the Dirichlet face states of them
+    auto faces_at = [&](double t) {
+        if (A.has_bcv) {
+            const double s = A.t1 > A.t0 ? (t - A.t0) / (A.t1 - A.t0) : 1.0;
+            P.bc_value[FACE_BOTTOM][COMP_ENERGY] = FT(A.bcv[0] + (A.bcv[4] - A.bcv[0]) * s);
+            P.bc_value[FACE_BOTTOM][COMP_HYDROLOGY] = FT(A.bcv[1] + (A.bcv[5] - A.bcv[1]) * s);
+            P.bc_value[FACE_TOP][COMP_ENERGY] = FT(A.bcv[2] + (A.bcv[6] - A.bcv[2]) * s);
+            P.bc_value[FACE_TOP][COMP_HYDROLOGY] = FT(A.bcv[3] + (A.bcv[7] - A.bcv[3]) * s);
+        }
+        fsb = face_state<FT, M, MODEL_RICHARDS, false, NOICE>(mm, P, S.c, FACE_BOTTOM, col, FT(0), ti_b, T, vgf);
+        fst = face_state<FT, M, MODEL_RICHARDS, false, NOICE>(mm, P, S.c, FACE_TOP, col, FT(0), ti_t, T, vgf);
+    };
+    FT* const y = A.y;
+    FT* const yn = A.yn;
+    FT* const fn = A.fn;
+    FT* const yg = A.yg;
+    FT* const w = A.w;
+    const FT tol = A.tol;
+    const int max_iter = A.fixed ? A.max_iter : A.newton_max;
+    const FT kappa = A.kappa;
+    // f_n of the first step: one tendency sweep at (Y, t0)
+    faces_at(A.t0);
+    column_sweep_up<FT, M, PERCOL, NOICE, VGF, false>(mm, P, S, fsb, fst, col, y, A.ti, ti_b, FT(0), nullptr, nullptr,
+                                                      [&](int64_t idx, FT, FT f) { fn[idx] = f; return FT(0); });
+    double t = A.t0;
+    double h = A.dt;
+    if (A.dt_cols && !A.fixed) { // (fixed mode: steps of exactly dt, whatever the buffer holds)
+        const double h0 = double(A.dt_cols[col]);
+        if (h0 > 0) h = h0;
+    }
+    const double hmin = LH_TRBDF2_HMIN_FRAC * (A.t1 - A.t0);
+    bool failed = false;
+    unsigned steps = 0;
+    auto restore = [&]() { // back to the last accepted state
+        for (int i = 0; i < n; ++i) {
+            const int64_t id = int64_t(i) * stride + col;
+            y[id] = yn[id];
+        }
+    };
+    while (t < A.t1) {
+        if (steps >= LH_TRBDF2_MAX_STEPS) { failed = true; break; }
+        ++steps;
+        double hh = h;
+        bool clip = false;
+        if (t + hh * (1.0 + 1e-10) >= A.t1) { hh = A.t1 - t; clip = true; } // land on t1 exactly
+        const FT dh = FT(dg * hh);
+        // stage 1: Y_n and w1 = Y_n + d h f_n; the guess is Y_n
+        for (int i = 0; i < n; ++i) {
+            const int64_t id = int64_t(i) * stride + col;
+            const FT v = y[id];
+            yn[id] = v;
+            w[id] = v + dh * fn[id];
+        }
+        faces_at(t + gam * hh);
+        bool conv;
+        int it = newton_stage<FT, M, PERCOL, NOICE, VGF, false, true>(mm, P, S, fsb, fst, col, y, A.ti, ti_b, w, A.cp,
+                                                                       A.dp, dh, tol, atol, rtol, max_iter, conv, kappa);
+        st.iters += unsigned(it);
+        bool newton_ok = conv;
+        if (!conv && A.fixed) ++st.unconv;
+        if (conv || A.fixed) {
+            // stage 2: Y_g and w2; the guess is Y_g
+            for (int i = 0; i < n; ++i) {
+                const int64_t id = int64_t(i) * stride + col;
+                const FT v = y[id];
+                yg[id] = v;
+                w[id] = (v - c_yn * yn[id]) * c_w2;
+            }
+            faces_at(t + hh);
+#ifdef LH_TUNING_VARIANTS
+            if (A.reuse) // (keeps the factorisation of the last iteration for the error solve)
+                it = newton_stage<FT, M, PERCOL, NOICE, VGF, false, true, true>(
+                    mm, P, S, fsb, fst, col, y, A.ti, ti_b, w, A.cp, A.dp, dh, tol, atol, rtol, max_iter, conv, kappa,
+                    A.fa, A.fden);
+            else
+#endif
+                it = newton_stage<FT, M, PERCOL, NOICE, VGF, false, true>(mm, P, S, fsb, fst, col, y, A.ti, ti_b, w,
+                                                                           A.cp, A.dp, dh, tol, atol, rtol, max_iter,
+                                                                           conv, kappa);
+            st.iters += unsigned(it);
+            newton_ok = conv;
+            if (!conv && A.fixed) ++st.unconv;
+        }
+        double fac = 0.25; // (a stage that did not converge)
+        bool accept = A.fixed != 0;
+        if (!A.fixed && newton_ok) {
+            // the error estimate: rhs b1 h f_n + b2 z_g + b3 z_1 and J re-formed at Y_1 (the stage-2 face
+            // states).  Tuning builds can instead reuse the factorisation of stage 2's last Newton iteration
+            // (A.reuse, LH_TUNE trf=1): two more planes and no closures in the sweep, measured 4-8 % slower
+            // 
+            const FT hf = FT(hh);
+            auto rhs = [&](int64_t idx, FT v) {
+                const FT f0 = fn[idx], v0 = yn[idx];
+                const FT zg = (yg[idx] - (v0 + dh * f0)) * inv_d;
+                const FT z1 = (v - w[idx]) * inv_d;
+                return b1 * (hf * f0) + b2 * zg + b3 * z1;
+            };
+#ifdef LH_TUNING_VARIANTS
+            if (A.reuse) {
+                FT dprev = FT(0);
+                for (int i = 0; i < n; ++i) {
+                    const int64_t id = int64_t(i) * stride + col;
+                    const FT dpi = (rhs(id, y[id]) - A.fa[id] * dprev) / A.fden[id];
+                    A.dp[id] = dpi;
+                    dprev = dpi;
+                }
+            } else
+#endif
+            {
+                column_sweep_up<FT, M, PERCOL, NOICE, VGF, true>(
+                    mm, P, S, fsb, fst, col, y, A.ti, ti_b, dh, A.cp, A.dp,
+                    [&](int64_t idx, FT v, FT) { return -rhs(idx, v); }); // (R = -rhs: the sweep solves J e = -R)
+            }
+            FT enext = FT(0);
+            double sum = 0.0;
+            for (int i = n - 1; i >= 0; --i) {
+                const int64_t id = int64_t(i) * stride + col;
+                const FT e = A.dp[id] - A.cp[id] * enext;
+                enext = e;
+                const FT a0 = yn[id] < FT(0) ? -yn[id] : yn[id];
+                const FT a1 = y[id] < FT(0) ? -y[id] : y[id];
+                const double q = double(e) / double(atol + rtol * (a0 > a1 ? a0 : a1));
+                sum += q * q;
+            }
+            const double E = sqrt(sum / n);
+            fac = 0.9 * pow(E, -1.0 / 3.0);
+            fac = fac != fac ? 0.2 : fmin(fmax(fac, 0.2), 5.0);
+            accept = E <= 1.0;
+        }
+        if (accept) {
+            ++st.accepted;
+            t = clip ? A.t1 : t + hh; // (assigned: the column lands on t1 exactly)
+            if (!A.fixed) h = (clip && fac >= 1.0) ? fmax(hh * fac, h) : hh * fac;
+            if (t < A.t1) { // f_{n+1} = z_1 / h for the next step
+                const FT inv_dh = FT(1.0 / (dg * hh));
+                for (int i = 0; i < n; ++i) {
+                    const int64_t id = int64_t(i) * stride + col;
+                    fn[id] = (y[id] - w[id]) * inv_dh;
+                }
+            }
+        } else {
+            ++st.rejected;
+            restore();
+            h = hh * fac;
+            if (!(h >= hmin)) { failed = true; break; }
+        }
+    }
+    st.steps = steps;
+    st.failed = failed ? 1u : 0u;
+    if (A.dt_cols) A.dt_cols[col] = failed ? FT(0) : FT(h);
+}
+
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF>
+__global__ void __launch_bounds__(implicit_threads<M>())
+trbdf2_kernel(const DevParams<FT> P, const Trbdf2Args<FT> A) {
+    __shared__ double s_tab[M::uses_tables ? MATH_TAB_DOUBLES : 2];
+    const M mm(stage_math_tables<M>(P.math_tab, s_tab)); // (every thread)
+    const int64_t col = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    Trbdf2ColStats st;
+    if (col < P.ncols) trbdf2_column<FT, M, PERCOL, NOICE, VGF>(mm, P, A, col, st);
+    // (every lane of the wave gets here, those past the last column with zeros): one atomic per counter and wave
+    unsigned long long acc = st.accepted, rej = st.rejected, its = st.iters, fl = st.failed, un = st.unconv;
+    unsigned long long mx = st.steps;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        acc += __shfl_xor(acc, off, 64);
+        rej += __shfl_xor(rej, off, 64);
+        its += __shfl_xor(its, off, 64);
+        fl += __shfl_xor(fl, off, 64);
+        un += __shfl_xor(un, off, 64);
+        const unsigned long long o = __shfl_xor(mx, off, 64);
+        mx = o > mx ? o : mx;
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        unsigned long long* s = A.stats;
+        atomicAdd(s + 0, acc);
+        atomicAdd(s + 1, rej);
+        atomicAdd(s + 2, its);
+        if (mx > __atomic_load_n(s + 3, __ATOMIC_RELAXED)) atomicMax(s + 3, mx);
+        if (fl) {
+            atomicOr(P.status, 16u);
+            atomicAdd(s + 4, fl);
+        }
+        atomicAdd(s + 5, 64ull * mx);
+        if (un) {
+            atomicOr(P.status, 8u);
+            atomicAdd(s + 6, un);
+        }
+    }
+}
+
+template <typename FT>
+void launch_trbdf2(const DevParams<FT>& P, const Trbdf2Args<FT>& A, bool percol, bool noice, int math, hipStream_t s) {
+    const bool ni = noice && math != MATH_LIBM;
+    const bool robust = P.vg_fast_all == 0;
+#define LH_TR(MATH, PC, NI, VG)                                                                      \
+    hipLaunchKernelGGL((trbdf2_kernel<FT, MATH, PC, NI, VG>), grid_for(P.ncols, implicit_threads<MATH>()), \
+                       dim3(implicit_threads<MATH>()), 0, s, P, A)
+#define LH_TR_PC(MATH, NI, VG)                 \
+    do {                                       \
+        if (percol) LH_TR(MATH, true, NI, VG); \
+        else LH_TR(MATH, false, NI, VG);       \
+    } while (0)
+    if (math == MATH_LIBM) {
+        LH_TR_PC(MathLibm<FT>, false, false);
+    } else if (sizeof(FT) == 8 && robust) {
+        if (ni) LH_TR_PC(MathFast<FT>, true, false);
+        else LH_TR_PC(MathFast<FT>, false, false);
+    } else {
+        if (ni) LH_TR_PC(MathFast<FT>, true, true);
+        else LH_TR_PC(MathFast<FT>, false, true);
+    }
+#undef LH_TR_PC
+#undef LH_TR
+}
+
+#define LH_INSTANTIATE_IMPLICIT(FT)                                                                                  \
+    template void launch_implicit_euler<FT>(const DevParams<FT>&, const ImplicitArgs<FT>&, bool, bool, int, hipStream_t); \
+    template void launch_trbdf2<FT>(const DevParams<FT>&, const Trbdf2Args<FT>&, bool, bool, int, hipStream_t);
 
 } // namespace lh

@@ -30,6 +30,9 @@ struct Tune {
     int place_mem = 0;  // lh_tune_placement: transient memory bound, percent of free memory (0 = 25)
     int zero = 1;    // use the states' known-zero plane bits (0: always read theta_i and store d theta_i = 0)
     int vgfast = 1;  // Float64: integer-exponent 2^(.) in the water closures when every column allows it (0: v_ldexp form always)
+    // lh_integrate_trbdf2: the stage Newton test kappa in units of 1e-4, its iteration
+    // cap, and (tuning builds) the error solve's matrix (0: J re-formed at Y_1, 1: stage 2's last factorisation)
+    int trk = 0, trn = 0, trf = 0;
 };
 
 // mode 0: tendency into `out`; 4: tendency + step bound; 1..3, 5: fused SSPRK33 stages (see rhs_kernel)
@@ -75,6 +78,9 @@ void launch_dt_prepare(FT* dt, FT dt_max, FT* elapsed, uint32_t* status, hipStre
 template <typename FT>
 void launch_implicit_euler(const DevParams<FT>& P, const ImplicitArgs<FT>& A, bool percol, bool noice, int math,
                            hipStream_t s);
+// TR-BDF2 of a Richards model over [t0, t1], per-column step control, in one launch (lh_implicit.hpp)
+template <typename FT>
+void launch_trbdf2(const DevParams<FT>& P, const Trbdf2Args<FT>& A, bool percol, bool noice, int math, hipStream_t s);
 template <typename FT>
 void launch_convert(FT* dst, const double* src, int64_t n, hipStream_t s);
 

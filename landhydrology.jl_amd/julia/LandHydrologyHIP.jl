@@ -455,6 +455,34 @@ function step_implicit_euler!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt, ns
 end
 
 """
+    integrate_trbdf2!(ens, Y, Ya, t0, t1, dt; abstol = 0.0, reltol = 0.0, adaptive = true,
+                      dt_cols = C_NULL, bcv = nothing) -> stats
+
+TR-BDF2 of a Richards ensemble from `t0` to `t1` in one call (lh_integrate_trbdf2): the
+`OrdinaryDiffEq.TRBDF2()` of `Simulation`, every column with its own step and error control.
+`dt`: the initial step (`adaptive = false`: the fixed step).  A tolerance of 0 takes its own default
+(`abstol` 1e-6, `reltol` 1e-3).
+`dt_cols`: `C_NULL` or a device pointer to `ncols` FT steps (in: initial steps, out: proposals, 0 for a
+column that failed and set status bit 4; with `adaptive = false` not read, and dt on exit).  `bcv`: `nothing` or 8 boundary values
+[t0 | t1][face][component], linear in between.  Returns the 7 counters of lh_trbdf2_stats
+(accepted, rejected, Newton iterations, max steps, failed, wave_steps, unconverged).
+"""
+function integrate_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, t1, dt; abstol = 0.0, reltol = 0.0,
+                           adaptive = true, dt_cols = C_NULL, bcv = nothing)
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    flags = adaptive ? UInt32(0) : UInt32(1)
+    check(ens.ctx, ccall((:lh_integrate_trbdf2, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, UInt32,
+                          Ptr{Cvoid}, Ptr{Float64}),
+                         ens.ctx, Y.handle, ya, t0, t1, dt, abstol, reltol, flags, dt_cols, vals))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
     tune_placement!(ens, Y, Ya, dY = nothing; max_candidates = 0, move_input = true)
 
 Let the library place the state written by `rhs!` (`dY` given) or the SSPRK33 stage state

@@ -928,18 +928,32 @@ class ImplicitEuler:
         self.max_iter = max_iter
 
 
-def _check_implicit_scope(model):
-    """NotImplementedError for what lh_step_implicit_euler refuses (LH_EMODEL)."""
+class TRBDF2:
+    """OrdinaryDiffEq.TRBDF2 marker: L-stable, second-order TR-BDF2 with per-column error control
+    (lh_integrate_trbdf2).  abstol / reltol: None = OrdinaryDiffEq's defaults (1e-6, 1e-3), each on its
+    own: TRBDF2(reltol=1e-5) keeps abstol 1e-6.
+    adaptive=False: steps of exactly the Simulation's dt, no error control.  The Simulation's dt is the
+    initial step and the interval at which Dirichlet closures are sampled; a model without them runs a
+    whole saveat chunk per library call.  Same scope as ImplicitEuler."""
+
+    def __init__(self, abstol=None, reltol=None, adaptive=True):
+        self.abstol = abstol
+        self.reltol = reltol
+        self.adaptive = adaptive
+
+
+def _check_implicit_scope(model, name="ImplicitEuler"):
+    """NotImplementedError for what lh_step_implicit_euler and lh_integrate_trbdf2 refuse (LH_EMODEL)."""
     if not (isinstance(model.energy_model, PrescribedTemperatureModel) and
             isinstance(model.hydrology_model, SoilHydrologyModel)):
-        raise NotImplementedError("ImplicitEuler is provided for Richards models only "
+        raise NotImplementedError(f"{name} is provided for Richards models only "
                                   "(SoilHydrologyModel + PrescribedTemperatureModel)")
     hm = model.hydrology_model
     if not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
-        raise NotImplementedError("ImplicitEuler supports the NoEffect conductivity factors only")
+        raise NotImplementedError(f"{name} supports the NoEffect conductivity factors only")
     bcs = model.boundary_conditions
     if bcs is not None and isinstance(bcs.top, PrescribedAtmosForcing):
-        raise NotImplementedError("ImplicitEuler does not support a prescribed-atmosphere top")
+        raise NotImplementedError(f"{name} does not support a prescribed-atmosphere top")
 
 
 def _implicit_bcv(model, be, t, dt, nsteps):
@@ -978,6 +992,88 @@ def step_implicit(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, d
     return int(mi.value), int(un.value)
 
 
+def _trbdf2_bcv(model, be, t0, t1):
+    """[t0 | t1][2][2] boundary values of every scalar Dirichlet closure at the two ends of a call (None
+    when nothing depends on time)."""
+    if not _time_dependent(model):
+        return None
+    vals = np.zeros((2, 2, 2))
+    for k, t in enumerate((t0, t1)):
+        for (f, c), (kind, v) in be.bc_values(model, t).items():
+            if np.ndim(v) == 0:
+                vals[k, f, c] = float(v)
+    return np.ascontiguousarray(vals)
+
+
+TRBDF2_ABSTOL, TRBDF2_RELTOL = 1e-6, 1e-3   # OrdinaryDiffEq's defaults (the library's for a 0)
+
+
+def _trbdf2_tolerances(abstol, reltol):
+    """(abstol, reltol) with each None replaced by its own default; negative or non-finite values are
+    passed on for the library to refuse (LH_EINVAL)."""
+    return (TRBDF2_ABSTOL if abstol is None else float(abstol),
+            TRBDF2_RELTOL if reltol is None else float(reltol))
+
+
+def integrate_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
+                     dt: float = 1.0, abstol=None, reltol=None, adaptive=True, dt_cols=None):
+    """Build extension: TR-BDF2 of `Y` from t0 to t1 in one library call (lh_integrate_trbdf2), every
+    column with its own step.  `dt`: the initial step (adaptive) or the step (adaptive=False).
+    Time-dependent Dirichlet closures are evaluated at t0 and t1 and interpolated linearly in between
+    (per-column values at t0).  abstol / reltol: None = 1e-6 / 1e-3, each on its own.  `dt_cols`: None or a
+    device tensor of ncols steps in the model's FT, read as the initial steps (<= 0: dt) and overwritten by
+    the next proposals (0: failed column); with adaptive=False it is not read and receives dt.
+    Returns lh_trbdf2_stats as a dict."""
+    _check_implicit_scope(model, "TRBDF2")
+    be = model._backend()
+    L = F.lib()
+    ya = Ya.handle if isinstance(Ya, FieldVector) else None
+    bcv = _trbdf2_bcv(model, be, t0, t1)
+    be.set_bcs(model, t0)
+    ptr = None
+    if dt_cols is not None:
+        import torch
+        ft = torch.float64 if np.dtype(model.domain.FT) == np.float64 else torch.float32
+        if dt_cols.dtype != ft or not dt_cols.is_cuda or dt_cols.numel() != model.domain.ncolumns \
+                or not dt_cols.is_contiguous():
+            raise ValueError("dt_cols must be a contiguous device tensor of ncolumns values in the model's FT")
+        torch.cuda.synchronize(dt_cols.device)   # (written on torch's stream, read on the library's)
+        ptr = C.c_void_p(dt_cols.data_ptr())
+    flags = 0 if adaptive else F.LH_TRBDF2_FIXED
+    abstol, reltol = _trbdf2_tolerances(abstol, reltol)
+    F.check(L.lh_integrate_trbdf2(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol, reltol, flags, ptr,
+                                  bcv.ctypes.data_as(C.POINTER(C.c_double)) if bcv is not None else None), be.ctx)
+    st = (C.c_int64 * F.LH_TRBDF2_NSTATS)()
+    F.check(L.lh_trbdf2_stats(be.ctx, st), be.ctx)
+    keys = ("accepted", "rejected", "newton_iterations", "max_steps", "failed", "wave_steps", "unconverged")
+    return dict(zip(keys, (int(x) for x in st)))
+
+
+def _advance_trbdf2(sim, t1):
+    """The Simulation's TR-BDF2 from it.t to t1: one library call per dt interval when Dirichlet closures
+    depend on time, one for the whole interval otherwise; the per-column step proposals carry over."""
+    it, m, model = sim.integrator, sim.method, sim.model
+    if t1 <= it.t:
+        return
+    if getattr(it, "_dt_cols", None) is None:
+        import torch
+        be = model._backend()
+        ft = torch.float64 if np.dtype(model.domain.FT) == np.float64 else torch.float32
+        it._dt_cols = torch.zeros(model.domain.ncolumns, dtype=ft, device=torch.device("cuda", be.device_index()))
+        it.trbdf2_stats = dict(accepted=0, rejected=0, newton_iterations=0, max_steps=0, failed=0, wave_steps=0,
+                               unconverged=0)
+    if _time_dependent(model):
+        n = max(1, int(round((t1 - it.t) / it.dt)))
+        ends = [it.t + (k + 1) * it.dt for k in range(n - 1)] + [t1]
+    else:
+        ends = [t1]
+    for te in ends:
+        st = integrate_trbdf2(model, it.u, it.p, it.t, te, it.dt, m.abstol, m.reltol, m.adaptive, it._dt_cols)
+        for k, v in st.items():
+            it.trbdf2_stats[k] += v   # (max_steps: the sum over calls of each call's largest count)
+        it.t = te
+
+
 class _Solution:
     def __init__(self):
         self.t = []
@@ -988,6 +1084,7 @@ class _Integrator:
     def __init__(self, model, Y, Ya, t0, tf, dt, saveat):
         self.model, self.u, self.p = model, Y, Ya
         self.t, self.tf, self.dt = float(t0), float(tf), float(dt)
+        self.t0 = float(t0)
         self.saveat = saveat
         self.sol = _Solution()
         self._nsteps_done = 0
@@ -1008,8 +1105,10 @@ class Simulation:
                  **kwargs):
         if isinstance(method, ImplicitEuler):
             _check_implicit_scope(model)
+        elif isinstance(method, TRBDF2):
+            _check_implicit_scope(model, "TRBDF2")
         elif not isinstance(method, SSPRK33):
-            raise NotImplementedError("only SSPRK33 and ImplicitEuler are provided on the device")
+            raise NotImplementedError("only SSPRK33, ImplicitEuler and TRBDF2 are provided on the device")
         self.method = method
         if Y_init is None:
             # simulation.jl:50 references an undefined variable here:
@@ -1098,6 +1197,13 @@ def _advance(sim: Simulation, nsteps: int):
             step_implicit(model, it.u, it.p, it.t, it.dt, nsteps, m.tol, m.max_iter)
             it._nsteps_done += nsteps
             it.t = it.t + nsteps * it.dt
+        return
+    if isinstance(getattr(sim, "method", None), TRBDF2):
+        if nsteps > 0:
+            # (the end of a chunk of nsteps intervals of dt, as the fixed-step methods reach it)
+            _advance_trbdf2(sim, it.tf if it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
+                            else it.t0 + (it._nsteps_done + nsteps) * it.dt)
+            it._nsteps_done += nsteps
         return
     be = model._backend()
     L = F.lib()
