@@ -140,13 +140,57 @@ int fail(lh_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-#define LH_HIP(ctx, call)                                                                    \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? LH_ENOMEM : LH_ENODEVICE,           \
-                        "%s failed: %s", #call, hipGetErrorString(e_));                      \
+// LH_OK, or the error of a HIP call: lh_last_error names the call as the source writes it
+int hip_status(lh_ctx* ctx, hipError_t e, const char* call) {
+    if (e == hipSuccess) return LH_OK;
+    return fail(ctx, e == hipErrorOutOfMemory ? LH_ENOMEM : LH_ENODEVICE, "%s failed: %s", call, hipGetErrorString(e));
+}
+#define LH_HIP(ctx, call)                                      \
+    do {                                                       \
+        if (int rc_ = hip_status(ctx, (call), #call)) return rc_; \
     } while (0)
+
+// f(FT(0)) for the context's working type: how every entry point picks its <double> or <float> instantiation
+template <typename F>
+inline auto with_ft(const lh_ctx* c, F&& f) {
+    return c->cfg.dtype == LH_F64 ? f(double(0)) : f(float(0));
+}
+
+// a transient device allocation, released on every way out of its scope
+struct DeviceBuffer {
+    void* p = nullptr;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// n boundary values (doubles) rounded to the working type and uploaded into `buf`
+int upload_boundary_values(lh_ctx* c, const double* bcv, size_t n, DeviceBuffer& buf) {
+    std::vector<char> tmp(n * c->esize);
+    for (size_t k = 0; k < n; ++k) {
+        if (c->cfg.dtype == LH_F64) reinterpret_cast<double*>(tmp.data())[k] = bcv[k];
+        else reinterpret_cast<float*>(tmp.data())[k] = float(bcv[k]);
+    }
+    if (int rc = hip_status(c, hipMalloc(&buf.p, n * c->esize), "hipMalloc(&d_bcv, nv * c->esize)")) return rc;
+    hipError_t e = hipMemcpyAsync(buf.p, tmp.data(), n * c->esize, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // tmp is pageable host memory
+    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "boundary-value upload failed: %s", hipGetErrorString(e));
+    return LH_OK;
+}
+
+// The launch error of a call that may have handed `buf` to its kernel: the launch reads it, so wait
+// before the buffer is released
+hipError_t launch_error(lh_ctx* c, const DeviceBuffer& buf) {
+    hipError_t e = hipGetLastError();
+    if (buf.p) {
+        const hipError_t e2 = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = e2;
+    }
+    return e;
+}
 
 // In-place min all-reduce of one FT value over the attached communicator, enqueued on the
 // context's stream behind whatever produced the value (no host round trip).
@@ -469,12 +513,11 @@ int materialize(lh_ctx* c, const lh_state* cs, uint32_t vars) {
     const uint32_t todo = s->stale_mask & s->profile_mask & vars;
     for (int i = 0; i < LH_NVARS && todo; ++i)
         if (todo >> i & 1u) {
-            if (c->cfg.dtype == LH_F64)
-                launch_broadcast_profile<double>(static_cast<double*>(s->plane[i]), static_cast<const double*>(s->profile[i]),
-                                                 c->cfg.ncols, c->stride, c->cfg.nlev, c->stream);
-            else
-                launch_broadcast_profile<float>(static_cast<float*>(s->plane[i]), static_cast<const float*>(s->profile[i]),
-                                                c->cfg.ncols, c->stride, c->cfg.nlev, c->stream);
+            with_ft(c, [&](auto ft) {
+                using FT = decltype(ft);
+                launch_broadcast_profile<FT>(static_cast<FT*>(s->plane[i]), static_cast<const FT*>(s->profile[i]),
+                                             c->cfg.ncols, c->stride, c->cfg.nlev, c->stream);
+            });
             LH_HIP(c, hipGetLastError());
         }
     s->stale_mask &= ~todo;
@@ -694,21 +737,10 @@ int run_column_stepper(lh_ctx* c, lh_state* Y, const lh_state* Ya, double dt, co
                        int64_t nsteps, const double* bcv) {
     if (nsteps <= 0) return LH_OK;
     Range r_("lh:column_stepper");
-    void* d_bcv = nullptr;
-    if (bcv) { // [nsteps][3][2][2] doubles -> FT on the device
-        const size_t nv = size_t(nsteps) * 12;
-        std::vector<char> tmp(nv * c->esize);
-        for (size_t k = 0; k < nv; ++k) {
-            if (c->cfg.dtype == LH_F64) reinterpret_cast<double*>(tmp.data())[k] = bcv[k];
-            else reinterpret_cast<float*>(tmp.data())[k] = float(bcv[k]);
-        }
-        LH_HIP(c, hipMalloc(&d_bcv, nv * c->esize));
-        hipError_t e = hipMemcpyAsync(d_bcv, tmp.data(), nv * c->esize, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // tmp is pageable host memory
-        if (e != hipSuccess) {
-            (void)hipFree(d_bcv);
-            return fail(c, LH_ENODEVICE, "boundary-value upload failed: %s", hipGetErrorString(e));
-        }
+    DeviceBuffer d_bcv; // [nsteps][3][2][2] doubles -> FT on the device
+    if (bcv) {
+        const int rc = upload_boundary_values(c, bcv, size_t(nsteps) * 12, d_bcv);
+        if (rc) return rc;
     }
     const bool factors = c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE;
     const lh_state* ti_src = c->cfg.model == LH_MODEL_HEAT ? Ya : Y;
@@ -717,26 +749,15 @@ int run_column_stepper(lh_ctx* c, lh_state* Y, const lh_state* Ya, double dt, co
         int rc;
         if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~aux_profile_vars(c, Ya)))) return rc;
     }
-    if (c->cfg.dtype == LH_F64) {
-        DevParams<double> P = make_params<double>(c);
-        set_aux_profiles<double>(c, Ya, P);
-        launch_column_stepper<double>(P, planes_of<double>(Y), planes_of<double>(Ya), dt,
-                                      static_cast<const double*>(dt_device), nsteps,
-                                      static_cast<const double*>(d_bcv), factors, any_percol(c), noice, c->stream);
-    } else {
-        DevParams<float> P = make_params<float>(c);
-        set_aux_profiles<float>(c, Ya, P);
-        launch_column_stepper<float>(P, planes_of<float>(Y), planes_of<float>(Ya), float(dt),
-                                     static_cast<const float*>(dt_device), nsteps,
-                                     static_cast<const float*>(d_bcv), factors, any_percol(c), noice, c->stream);
-    }
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        set_aux_profiles<FT>(c, Ya, P);
+        launch_column_stepper<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), FT(dt), static_cast<const FT*>(dt_device),
+                                  nsteps, static_cast<const FT*>(d_bcv.p), factors, any_percol(c), noice, c->stream);
+    });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
-    hipError_t e = hipGetLastError();
-    if (d_bcv) { // the launch reads it: wait before releasing
-        const hipError_t e2 = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_bcv);
-        if (e == hipSuccess) e = e2;
-    }
+    const hipError_t e = launch_error(c, d_bcv);
     if (e != hipSuccess) return fail(c, LH_ENODEVICE, "column stepper launch failed: %s", hipGetErrorString(e));
     return LH_OK;
 }
@@ -770,8 +791,7 @@ int upload_percol(lh_ctx* c, void** slot, const double* host) {
         return fail(c, LH_ENOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
     }
     LH_HIP(c, hipMemcpyAsync(tmp, host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (c->cfg.dtype == LH_F64) launch_convert<double>(static_cast<double*>(*slot), tmp, n, c->stream);
-    else launch_convert<float>(static_cast<float*>(*slot), tmp, n, c->stream);
+    with_ft(c, [&](auto ft) { launch_convert<decltype(ft)>(static_cast<decltype(ft)*>(*slot), tmp, n, c->stream); });
     LH_HIP(c, hipStreamSynchronize(c->stream));
     (void)hipFree(tmp);
     return LH_OK;
@@ -1225,17 +1245,13 @@ int lh_atmos_surface_fluxes(lh_ctx* c, int64_t n, const double* vl, const double
         e = hipMemcpyAsync(d_in + size_t(k) * n, src[k], size_t(n) * sizeof(double), hipMemcpyHostToDevice, c->stream);
     std::vector<char> out(size_t(n) * 2 * es);
     if (e == hipSuccess) {
-        if (c->cfg.dtype == LH_F64) {
-            double* f = reinterpret_cast<double*>(d_ft);
-            launch_convert<double>(f, d_in, 3 * n, c->stream);
-            launch_atmos_flux<double>(make_params<double>(c), make_atmos_params<double>(c), n, false, false, f, f + n, f + 2 * n,
-                                      f + 3 * n, f + 4 * n, c->stream);
-        } else {
-            float* f = reinterpret_cast<float*>(d_ft);
-            launch_convert<float>(f, d_in, 3 * n, c->stream);
-            launch_atmos_flux<float>(make_params<float>(c), make_atmos_params<float>(c), n, false, false, f, f + n, f + 2 * n,
-                                     f + 3 * n, f + 4 * n, c->stream);
-        }
+        with_ft(c, [&](auto ft) {
+            using FT = decltype(ft);
+            FT* f = reinterpret_cast<FT*>(d_ft);
+            launch_convert<FT>(f, d_in, 3 * n, c->stream);
+            launch_atmos_flux<FT>(make_params<FT>(c), make_atmos_params<FT>(c), n, false, false, f, f + n, f + 2 * n,
+                                  f + 3 * n, f + 4 * n, c->stream);
+        });
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out.data(), d_ft + size_t(n) * 3 * es, size_t(n) * 2 * es, hipMemcpyDeviceToHost, c->stream);
@@ -1243,15 +1259,10 @@ int lh_atmos_surface_fluxes(lh_ctx* c, int64_t n, const double* vl, const double
     cleanup();
     if (e != hipSuccess || e2 != hipSuccess)
         return fail(c, LH_ENODEVICE, "lh_atmos_surface_fluxes failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    for (int64_t i = 0; i < n; ++i) {
-        if (c->cfg.dtype == LH_F64) {
-            heat[i] = reinterpret_cast<const double*>(out.data())[i];
-            water[i] = reinterpret_cast<const double*>(out.data())[n + i];
-        } else {
-            heat[i] = reinterpret_cast<const float*>(out.data())[i];
-            water[i] = reinterpret_cast<const float*>(out.data())[n + i];
-        }
-    }
+    with_ft(c, [&](auto ft) {
+        const auto* o = reinterpret_cast<const decltype(ft)*>(out.data());
+        for (int64_t i = 0; i < n; ++i) heat[i] = o[i], water[i] = o[n + i];
+    });
     return LH_OK;
 }
 
@@ -1329,10 +1340,10 @@ static int transfer(lh_ctx* c, lh_state* s, int32_t var, void* host, int64_t ls,
     else if (span != ncols * int64_t(nlev)) // gaps in the user layout keep their contents
         e = hipMemcpyAsync(tmp, host, size_t(span) * es, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        if (c->cfg.dtype == LH_F64)
-            launch_strided_copy<double>(reinterpret_cast<double*>(plane), c->stride, static_cast<double*>(tmp), ls, cs, ncols, nlev, upload, c->stream);
-        else
-            launch_strided_copy<float>(reinterpret_cast<float*>(plane), c->stride, static_cast<float*>(tmp), ls, cs, ncols, nlev, upload, c->stream);
+        with_ft(c, [&](auto ft) {
+            using FT = decltype(ft);
+            launch_strided_copy<FT>(reinterpret_cast<FT*>(plane), c->stride, static_cast<FT*>(tmp), ls, cs, ncols, nlev, upload, c->stream);
+        });
         e = hipGetLastError();
     }
     if (e == hipSuccess && !upload) e = hipMemcpyAsync(host, tmp, size_t(span) * es, hipMemcpyDeviceToHost, c->stream);
@@ -1374,8 +1385,10 @@ int lh_state_fill(lh_ctx* c, lh_state* s, int32_t var, double value) {
     if (var < 0 || var >= LH_NVARS || !(s->mask & (1u << var))) return fail(c, LH_ESTATE, "state has no variable %d", var);
     (void)hipSetDevice(c->device);
     const int64_t n = int64_t(c->cfg.nlev) * c->stride;
-    if (c->cfg.dtype == LH_F64) launch_fill<double>(static_cast<double*>(s->plane[var]), n, value, c->stream);
-    else launch_fill<float>(static_cast<float*>(s->plane[var]), n, float(value), c->stream);
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        launch_fill<FT>(static_cast<FT*>(s->plane[var]), n, FT(value), c->stream);
+    });
     LH_HIP(c, hipGetLastError());
     mark_written(s, 1u << var);
     if (value == 0.0 && !std::signbit(value)) mark_zero(s, var);
@@ -1477,8 +1490,7 @@ int lh_rhs(lh_ctx* c, double t, const lh_state* Y, const lh_state* Ya, lh_state*
     if ((rc = check_state(c, dY, pm, "dY"))) return rc;
     if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
     (void)hipSetDevice(c->device);
-    return c->cfg.dtype == LH_F64 ? do_rhs<double>(c, Y, Ya, nullptr, dY, 0.0, 0, nullptr)
-                                  : do_rhs<float>(c, Y, Ya, nullptr, dY, 0.0, 0, nullptr);
+    return with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, Y, Ya, nullptr, dY, 0.0, 0, nullptr); });
 }
 
 int lh_rhs_stable_dt(lh_ctx* c, double t, const lh_state* Y, const lh_state* Ya, lh_state* dY,
@@ -1493,9 +1505,7 @@ int lh_rhs_stable_dt(lh_ctx* c, double t, const lh_state* Y, const lh_state* Ya,
     if ((rc = check_state(c, dY, pm, "dY"))) return rc;
     if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
     (void)hipSetDevice(c->device);
-    rc = c->cfg.dtype == LH_F64
-             ? do_rhs<double>(c, Y, Ya, nullptr, dY, courant, 4, nullptr, nullptr, dt_device_ft)
-             : do_rhs<float>(c, Y, Ya, nullptr, dY, courant, 4, nullptr, nullptr, dt_device_ft);
+    rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, Y, Ya, nullptr, dY, courant, 4, nullptr, nullptr, dt_device_ft); });
     if (rc) return rc;
     return allreduce_min(c, dt_device_ft); // the global minimum when a communicator is attached
 }
@@ -1513,8 +1523,7 @@ int lh_boundary_fluxes(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double 
     (void)hipSetDevice(c->device);
     if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u))) return rc;
     Range r_("lh:boundary_fluxes");
-    return c->cfg.dtype == LH_F64 ? boundary_fluxes_impl<double>(c, Y, Ya, face, f_energy, f_water)
-                                  : boundary_fluxes_impl<float>(c, Y, Ya, face, f_energy, f_water);
+    return with_ft(c, [&](auto ft) { return boundary_fluxes_impl<decltype(ft)>(c, Y, Ya, face, f_energy, f_water); });
 }
 
 int lh_diagnostics(lh_ctx* c, const lh_state* Y, const lh_state* Ya, lh_state* out) {
@@ -1527,13 +1536,11 @@ int lh_diagnostics(lh_ctx* c, const lh_state* Y, const lh_state* Ya, lh_state* o
     if ((rc = check_state(c, out, 0xFu, "diagnostic"))) return rc;
     (void)hipSetDevice(c->device);
     if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u))) return rc;
-    if (c->cfg.dtype == LH_F64) {
-        DevParams<double> P = make_params<double>(c);
-        launch_diag<double>(P, planes_of<double>(Y), planes_of<double>(Ya), planes_of<double>(out), any_percol(c), c->math, c->stream);
-    } else {
-        DevParams<float> P = make_params<float>(c);
-        launch_diag<float>(P, planes_of<float>(Y), planes_of<float>(Ya), planes_of<float>(out), any_percol(c), c->math, c->stream);
-    }
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        launch_diag<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), planes_of<FT>(out), any_percol(c), c->math, c->stream);
+    });
     LH_HIP(c, hipGetLastError());
     mark_written(out, ~0u);
     return LH_OK;
@@ -1571,8 +1578,7 @@ int lh_step_ssprk33(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double
             // (U2 is U1 itself unless the launch is level-segmented)
             const lh_state* in = stage == 0 ? Y : (stage == 1 ? U1 : U2);
             lh_state* out = stage == 2 ? Y : (stage == 1 ? U2 : U1);
-            int r = c->cfg.dtype == LH_F64 ? do_rhs<double>(c, in, Ya, Y, out, dt, stage + 1, ov)
-                                           : do_rhs<float>(c, in, Ya, Y, out, dt, stage + 1, ov);
+            int r = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, in, Ya, Y, out, dt, stage + 1, ov); });
             if (r) return r;
         }
         return LH_OK;
@@ -1632,8 +1638,7 @@ int lh_ssprk33_stage(lh_ctx* c, int32_t stage, lh_state* Y, lh_state* U, const l
     // stage 1: U = Y + dt f(Y); 2: U = (3Y + U + dt f(U))/4; 3: Y = (Y + 2U + 2dt f(U))/3
     const lh_state* in = stage == 1 ? Y : U;
     lh_state* out = stage == 3 ? Y : U;
-    return c->cfg.dtype == LH_F64 ? do_rhs<double>(c, in, Ya, Y, out, dt, stage, bc_values, nullptr, nullptr, true)
-                                  : do_rhs<float>(c, in, Ya, Y, out, dt, stage, bc_values, nullptr, nullptr, true);
+    return with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, in, Ya, Y, out, dt, stage, bc_values, nullptr, nullptr, true); });
 }
 
 int lh_step_ssprk33_device_dt(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t,
@@ -1655,8 +1660,7 @@ int lh_step_ssprk33_device_dt(lh_ctx* c, lh_state* Y, const lh_state* Ya, double
         const double* ov = bcv ? bcv + stage * 4 : nullptr;
         const lh_state* in = stage == 0 ? Y : (stage == 1 ? U1 : U2);
         lh_state* out = stage == 2 ? Y : (stage == 1 ? U2 : U1);
-        rc = c->cfg.dtype == LH_F64 ? do_rhs<double>(c, in, Ya, Y, out, 0.0, stage + 1, ov, dt_device_ft)
-                                    : do_rhs<float>(c, in, Ya, Y, out, 0.0, stage + 1, ov, dt_device_ft);
+        rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, in, Ya, Y, out, 0.0, stage + 1, ov, dt_device_ft); });
         if (rc) return rc;
     }
     return LH_OK;
@@ -1678,7 +1682,6 @@ int lh_step_ssprk33_adaptive(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
     if (!c->scratch_u1 && (rc = state_alloc(c, pm & ~LH_MASK(LH_VAR_THETA_I), &c->scratch_u1))) return rc;
     lh_state* K1 = c->scratch_k1;
     lh_state* U1 = c->scratch_u1;
-    const bool f64 = c->cfg.dtype == LH_F64;
     // With a prescribed atmosphere the surface fluxes of a stage come from the stage state's top
     // cells, which MODE 5 never stores: that model takes the four-launch sequence.
     const bool three = !c->hp.atmos_on;
@@ -1686,26 +1689,24 @@ int lh_step_ssprk33_adaptive(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
     if (!three && (rc = second_stage_state(c, &U2))) return rc;
     for (int64_t s = 0; s < nsteps; ++s) {
         // f(Y) and the step bound of Y in one launch; the global minimum with a communicator
-        rc = f64 ? do_rhs<double>(c, Y, Ya, nullptr, K1, courant, 4, nullptr, nullptr, dt_device_ft)
-                 : do_rhs<float>(c, Y, Ya, nullptr, K1, courant, 4, nullptr, nullptr, dt_device_ft);
+        rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, Y, Ya, nullptr, K1, courant, 4, nullptr, nullptr, dt_device_ft); });
         if (rc) return rc;
         if ((rc = allreduce_min(c, dt_device_ft))) return rc;
-        if (f64) launch_dt_prepare<double>(static_cast<double*>(dt_device_ft), dt_max, static_cast<double*>(elapsed_device_ft), c->d_status, c->stream);
-        else launch_dt_prepare<float>(static_cast<float*>(dt_device_ft), float(dt_max), static_cast<float*>(elapsed_device_ft), c->d_status, c->stream);
+        with_ft(c, [&](auto ft) {
+            using FT = decltype(ft);
+            launch_dt_prepare<FT>(static_cast<FT*>(dt_device_ft), FT(dt_max), static_cast<FT*>(elapsed_device_ft), c->d_status, c->stream);
+        });
         if (three) {
             // stage 2 from (Y, k1): U1 = Y + dt k1 formed in registers; then stage 3
-            rc = f64 ? do_rhs<double>(c, K1, Ya, Y, U1, 0.0, 5, nullptr, dt_device_ft)
-                     : do_rhs<float>(c, K1, Ya, Y, U1, 0.0, 5, nullptr, dt_device_ft);
+            rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, K1, Ya, Y, U1, 0.0, 5, nullptr, dt_device_ft); });
             if (rc) return rc;
-            rc = f64 ? do_rhs<double>(c, U1, Ya, Y, Y, 0.0, 3, nullptr, dt_device_ft)
-                     : do_rhs<float>(c, U1, Ya, Y, Y, 0.0, 3, nullptr, dt_device_ft);
+            rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, U1, Ya, Y, Y, 0.0, 3, nullptr, dt_device_ft); });
             if (rc) return rc;
         } else {
             for (int stage = 0; stage < 3; ++stage) {
                 const lh_state* in = stage == 0 ? Y : (stage == 1 ? U1 : U2);
                 lh_state* out = stage == 2 ? Y : (stage == 1 ? U2 : U1);
-                rc = f64 ? do_rhs<double>(c, in, Ya, Y, out, 0.0, stage + 1, nullptr, dt_device_ft)
-                         : do_rhs<float>(c, in, Ya, Y, out, 0.0, stage + 1, nullptr, dt_device_ft);
+                rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, in, Ya, Y, out, 0.0, stage + 1, nullptr, dt_device_ft); });
                 if (rc) return rc;
             }
         }
@@ -1714,112 +1715,118 @@ int lh_step_ssprk33_adaptive(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
     return LH_OK;
 }
 
+// ---- what lh_step_implicit_euler and lh_integrate_trbdf2 share on the host
+
+// Both refuse the same configurations and states, in this order (`who`: the entry point, for lh_last_error)
+static int implicit_refusals(lh_ctx* c, const char* who, const lh_state* Y, const lh_state* Ya) {
+    if (c->cfg.model != LH_MODEL_RICHARDS)
+        return fail(c, LH_EMODEL, "%s: Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)", who);
+    if (c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE)
+        return fail(c, LH_EMODEL, "%s: conductivity factors other than NoEffect are not supported", who);
+    // (validate_model refuses a prescribed atmosphere on any model but the coupled one already; kept so
+    // that this path stays closed to it should that change)
+    if (c->hp.atmos_on) return fail(c, LH_EMODEL, "%s: a prescribed-atmosphere top is not supported", who);
+    int rc = validate_model(c);
+    if (rc) return rc;
+    if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
+    return check_state(c, Ya, aux_mask(c), "Ya");
+}
+
+// The helpers below take the buffer's name and size as the entry points write them (`name`, `size`), so that a
+// failure reads in lh_last_error as the call on that buffer: "hipMalloc(&c->d_tr, 6 * plane) failed: ..."
+static int named_status(lh_ctx* c, hipError_t e, const char* fmt, const char* name, const char* size) {
+    char call[160];
+    snprintf(call, sizeof call, fmt, name, size);
+    return hip_status(c, e, call);
+}
+// A statistics block describes one call from its first line on, also when the call is refused: zeroed
+// here if it exists ...
+static int zero_stats(lh_ctx* c, void* d_stats, size_t bytes, const char* name, const char* size) {
+    if (!d_stats) return LH_OK;
+    return named_status(c, hipMemsetAsync(d_stats, 0, bytes, c->stream), "hipMemsetAsync(%s, 0, %s, c->stream)", name, size);
+}
+// ... and allocated (zeroed) on the first call that gets as far as needing it, like the scratch planes
+static int ensure_scratch(lh_ctx* c, void** slot, size_t bytes, const char* name, const char* size, bool zeroed = false) {
+    if (*slot) return LH_OK;
+    if (int rc = named_status(c, hipMalloc(slot, bytes), "hipMalloc(&%s, %s)", name, size)) return rc;
+    return zeroed ? zero_stats(c, *slot, bytes, name, size) : LH_OK;
+}
+// ... and read back: zeros before the first call
+static int read_stats(lh_ctx* c, const void* d_stats, void* host, size_t bytes, const char* name) {
+    memset(host, 0, bytes);
+    if (!d_stats) return LH_OK;
+    (void)hipSetDevice(c->device);
+    if (int rc = named_status(c, hipMemcpyAsync(host, d_stats, bytes, hipMemcpyDeviceToHost, c->stream),
+                              "hipMemcpyAsync(host, %s, %s, hipMemcpyDeviceToHost, c->stream)", name, "bytes"))
+        return rc;
+    LH_HIP(c, hipStreamSynchronize(c->stream));
+    return LH_OK;
+}
+// theta_i known zero (the state's zero bits): the kernels that do not read the plane
+static bool implicit_noice(const lh_ctx* c, const lh_state* Y) {
+    return c->tune.zero != 0 && (Y->zero_mask & LH_MASK(LH_VAR_THETA_I));
+}
+
 int lh_step_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
                            const double* bcv, double tol, int32_t max_iter) {
     (void)t; // boundary values of t_{n+1} come through bcv or lh_set_bc, as for lh_step_ssprk33
     if (!c) return LH_EINVAL;
-    // the statistics describe THIS call from here on, also when it is refused below
-    if (c->d_imp_stats) LH_HIP(c, hipMemsetAsync(c->d_imp_stats, 0, 24, c->stream));
+    int rc = zero_stats(c, c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24");
+    if (rc) return rc;
     if (nsteps < 0 || !(dt > 0)) return fail(c, LH_EINVAL, "lh_step_implicit_euler: need nsteps >= 0 and dt > 0");
     Range r_("lh:step_implicit_euler");
-    if (c->cfg.model != LH_MODEL_RICHARDS)
-        return fail(c, LH_EMODEL, "lh_step_implicit_euler: Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)");
-    if (c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE)
-        return fail(c, LH_EMODEL, "lh_step_implicit_euler: conductivity factors other than NoEffect are not supported");
-    // (validate_model refuses a prescribed atmosphere on any model but the coupled one already; kept so
-    // that this path stays closed to it should that change)
-    if (c->hp.atmos_on) return fail(c, LH_EMODEL, "lh_step_implicit_euler: a prescribed-atmosphere top is not supported");
-    int rc = validate_model(c);
-    if (rc) return rc;
-    if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
-    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
+    if ((rc = implicit_refusals(c, "lh_step_implicit_euler", Y, Ya))) return rc;
     (void)hipSetDevice(c->device);
-    const bool f64 = c->cfg.dtype == LH_F64;
-    if (!(tol > 0)) tol = f64 ? 1e-10 : 1e-5;
+    if (!(tol > 0)) tol = c->cfg.dtype == LH_F64 ? 1e-10 : 1e-5;
     if (max_iter <= 0) max_iter = 50;
-    const size_t plane = size_t(c->cfg.nlev) * size_t(c->stride) * c->esize;
-    if (!c->d_imp) LH_HIP(c, hipMalloc(&c->d_imp, 3 * plane));
-    if (!c->d_imp_stats) {
-        LH_HIP(c, hipMalloc(&c->d_imp_stats, 24));
-        LH_HIP(c, hipMemsetAsync(c->d_imp_stats, 0, 24, c->stream));
-    }
+    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+    if ((rc = ensure_scratch(c, &c->d_imp, 3 * pl * c->esize, "c->d_imp", "3 * plane"))) return rc;
+    if ((rc = ensure_scratch(c, &c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24", true))) return rc;
     if (nsteps == 0) return LH_OK;
     if ((rc = materialize(c, Y, ~0u))) return rc;
-    void* d_bcv = nullptr;
-    if (bcv) { // [nsteps][2][2] doubles -> FT on the device
-        const size_t nv = size_t(nsteps) * 4;
-        std::vector<char> tmp(nv * c->esize);
-        for (size_t k = 0; k < nv; ++k) {
-            if (f64) reinterpret_cast<double*>(tmp.data())[k] = bcv[k];
-            else reinterpret_cast<float*>(tmp.data())[k] = float(bcv[k]);
-        }
-        LH_HIP(c, hipMalloc(&d_bcv, nv * c->esize));
-        hipError_t e = hipMemcpyAsync(d_bcv, tmp.data(), nv * c->esize, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // tmp is pageable host memory
-        if (e != hipSuccess) {
-            (void)hipFree(d_bcv);
-            return fail(c, LH_ENODEVICE, "boundary-value upload failed: %s", hipGetErrorString(e));
-        }
-    }
-    const bool noice = c->tune.zero != 0 && (Y->zero_mask & LH_MASK(LH_VAR_THETA_I));
-    auto go = [&](auto ft) {
+    DeviceBuffer d_bcv; // [nsteps][2][2] doubles -> FT on the device
+    if (bcv && (rc = upload_boundary_values(c, bcv, size_t(nsteps) * 4, d_bcv))) return rc;
+    with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
+        ImplicitStats* const st = static_cast<ImplicitStats*>(c->d_imp_stats); // (device memory: addresses only)
         ImplicitArgs<FT> A;
         A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
         A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
         A.yn = static_cast<FT*>(c->d_imp);
-        A.cp = A.yn + size_t(c->cfg.nlev) * size_t(c->stride);
-        A.dp = A.cp + size_t(c->cfg.nlev) * size_t(c->stride);
-        A.bcv = static_cast<const FT*>(d_bcv);
+        A.cp = A.yn + pl;
+        A.dp = A.cp + pl;
+        A.bcv = static_cast<const FT*>(d_bcv.p);
         A.dt = FT(dt);
         A.tol = FT(tol);
         A.max_iter = max_iter;
         A.nsteps = nsteps;
-        A.max_iters = static_cast<int32_t*>(c->d_imp_stats);
-        A.unconverged = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->d_imp_stats) + 8);
-        A.total_iters = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->d_imp_stats) + 16);
-        launch_implicit_euler<FT>(P, A, any_percol(c), noice, c->math, c->stream);
-    };
-    if (f64) go(double(0));
-    else go(float(0));
+        A.max_iters = &st->max_iters;
+        A.unconverged = &st->unconverged;
+        A.total_iters = &st->total_iters;
+        launch_implicit_euler<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+    });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
-    hipError_t e = hipGetLastError();
-    if (d_bcv) { // the launch reads it: wait before releasing
-        const hipError_t e2 = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_bcv);
-        if (e == hipSuccess) e = e2;
-    }
+    const hipError_t e = launch_error(c, d_bcv);
     if (e != hipSuccess) return fail(c, LH_ENODEVICE, "implicit Euler launch failed: %s", hipGetErrorString(e));
     return LH_OK;
 }
 
 int lh_implicit_iterations(lh_ctx* c, int64_t* iterations) {
     if (!c || !iterations) return fail(c, LH_EINVAL, "lh_implicit_iterations: NULL argument");
-    *iterations = 0;
-    if (!c->d_imp_stats) return LH_OK; // no implicit step yet
-    (void)hipSetDevice(c->device);
-    uint64_t u = 0;
-    LH_HIP(c, hipMemcpyAsync(&u, static_cast<char*>(c->d_imp_stats) + 16, 8, hipMemcpyDeviceToHost, c->stream));
-    LH_HIP(c, hipStreamSynchronize(c->stream));
-    *iterations = int64_t(u);
-    return LH_OK;
+    ImplicitStats st;
+    const int rc = read_stats(c, c->d_imp_stats, &st, sizeof st, "c->d_imp_stats");
+    *iterations = int64_t(st.total_iters);
+    return rc;
 }
 
 int lh_implicit_stats(lh_ctx* c, int32_t* max_iters, int64_t* unconverged) {
     if (!c || !max_iters || !unconverged) return fail(c, LH_EINVAL, "lh_implicit_stats: NULL argument");
-    *max_iters = 0;
-    *unconverged = 0;
-    if (!c->d_imp_stats) return LH_OK; // no implicit step yet
-    (void)hipSetDevice(c->device);
-    char buf[16];
-    LH_HIP(c, hipMemcpyAsync(buf, c->d_imp_stats, 16, hipMemcpyDeviceToHost, c->stream));
-    LH_HIP(c, hipStreamSynchronize(c->stream));
-    memcpy(max_iters, buf, 4);
-    uint64_t u;
-    memcpy(&u, buf + 8, 8);
-    *unconverged = int64_t(u);
-    return LH_OK;
+    ImplicitStats st;
+    const int rc = read_stats(c, c->d_imp_stats, &st, sizeof st, "c->d_imp_stats");
+    *max_iters = st.max_iters;
+    *unconverged = int64_t(st.unconverged);
+    return rc;
 }
 
 // lh_integrate_trbdf2's defaults (LH_TUNE trk= / trn= override the Newton pair, and
@@ -1833,8 +1840,8 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
                         double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
     if (!c) return LH_EINVAL;
     const size_t nstat = LH_TRBDF2_NSTATS * sizeof(uint64_t);
-    // the statistics describe THIS call from here on, also when it is refused below
-    if (c->d_tr_stats) LH_HIP(c, hipMemsetAsync(c->d_tr_stats, 0, nstat, c->stream));
+    int rc = zero_stats(c, c->d_tr_stats, nstat, "c->d_tr_stats", "nstat");
+    if (rc) return rc;
     if (!std::isfinite(t0) || !std::isfinite(t1) || !(t1 >= t0))
         return fail(c, LH_EINVAL, "lh_integrate_trbdf2: need finite t0 <= t1");
     if (!std::isfinite(dt) || !(dt > 0)) return fail(c, LH_EINVAL, "lh_integrate_trbdf2: need a finite dt > 0");
@@ -1845,17 +1852,8 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
         for (int k = 0; k < 8; ++k)
             if (!std::isfinite(bcv[k])) return fail(c, LH_EINVAL, "lh_integrate_trbdf2: non-finite boundary value");
     Range r_("lh:integrate_trbdf2");
-    if (c->cfg.model != LH_MODEL_RICHARDS)
-        return fail(c, LH_EMODEL, "lh_integrate_trbdf2: Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)");
-    if (c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE)
-        return fail(c, LH_EMODEL, "lh_integrate_trbdf2: conductivity factors other than NoEffect are not supported");
-    if (c->hp.atmos_on) return fail(c, LH_EMODEL, "lh_integrate_trbdf2: a prescribed-atmosphere top is not supported");
-    int rc = validate_model(c);
-    if (rc) return rc;
-    if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
-    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
+    if ((rc = implicit_refusals(c, "lh_integrate_trbdf2", Y, Ya))) return rc;
     (void)hipSetDevice(c->device);
-    const bool f64 = c->cfg.dtype == LH_F64;
     const bool fixed = (flags & LH_TRBDF2_FIXED) != 0;
     // each tolerance that is 0 takes its own default (OrdinaryDiffEq's)
     if (!(abstol > 0)) abstol = LH_TRBDF2_ABSTOL_DEFAULT;
@@ -1865,21 +1863,16 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
 #else
     const bool reuse = false;
 #endif
-    const size_t plane = size_t(c->cfg.nlev) * size_t(c->stride) * c->esize;
-    if (!c->d_tr) LH_HIP(c, hipMalloc(&c->d_tr, 6 * plane));
-    if (reuse && !c->d_tr_f) LH_HIP(c, hipMalloc(&c->d_tr_f, 2 * plane));
-    if (!c->d_tr_stats) {
-        LH_HIP(c, hipMalloc(&c->d_tr_stats, nstat));
-        LH_HIP(c, hipMemsetAsync(c->d_tr_stats, 0, nstat, c->stream));
-    }
+    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+    if ((rc = ensure_scratch(c, &c->d_tr, 6 * pl * c->esize, "c->d_tr", "6 * plane"))) return rc;
+    if (reuse && (rc = ensure_scratch(c, &c->d_tr_f, 2 * pl * c->esize, "c->d_tr_f", "2 * plane"))) return rc;
+    if ((rc = ensure_scratch(c, &c->d_tr_stats, nstat, "c->d_tr_stats", "nstat", true))) return rc;
     if (t1 == t0) return LH_OK;
     if ((rc = materialize(c, Y, ~0u))) return rc;
-    const bool noice = c->tune.zero != 0 && (Y->zero_mask & LH_MASK(LH_VAR_THETA_I));
-    auto go = [&](auto ft) {
+    with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
         Trbdf2Args<FT> A;
-        const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
         A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
         A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
         A.yn = static_cast<FT*>(c->d_tr);
@@ -1897,7 +1890,7 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
         A.has_bcv = bcv != nullptr;
         for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
         A.fixed = fixed;
-        A.tol = FT(f64 ? 1e-10 : 1e-5); // (fixed mode: lh_step_implicit_euler's defaults)
+        A.tol = FT(sizeof(FT) == 8 ? 1e-10 : 1e-5); // (fixed mode: lh_step_implicit_euler's defaults)
         A.max_iter = 50;
         A.kappa = FT(c->tune.trk > 0 ? 1e-4 * c->tune.trk : LH_TRBDF2_NEWTON_KAPPA);
         A.newton_max = c->tune.trn > 0 ? c->tune.trn : LH_TRBDF2_NEWTON_MAX;
@@ -1905,10 +1898,8 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
         A.fa = reuse ? static_cast<FT*>(c->d_tr_f) : nullptr;
         A.fden = reuse ? A.fa + pl : nullptr;
         A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
-        launch_trbdf2<FT>(P, A, any_percol(c), noice, c->math, c->stream);
-    };
-    if (f64) go(double(0));
-    else go(float(0));
+        launch_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+    });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, LH_ENODEVICE, "TR-BDF2 launch failed: %s", hipGetErrorString(e));
@@ -1917,14 +1908,10 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
 
 int lh_trbdf2_stats(lh_ctx* c, int64_t* stats) {
     if (!c || !stats) return fail(c, LH_EINVAL, "lh_trbdf2_stats: NULL argument");
-    for (int k = 0; k < LH_TRBDF2_NSTATS; ++k) stats[k] = 0;
-    if (!c->d_tr_stats) return LH_OK; // no TR-BDF2 call yet
-    (void)hipSetDevice(c->device);
     uint64_t u[LH_TRBDF2_NSTATS];
-    LH_HIP(c, hipMemcpyAsync(u, c->d_tr_stats, sizeof(u), hipMemcpyDeviceToHost, c->stream));
-    LH_HIP(c, hipStreamSynchronize(c->stream));
+    const int rc = read_stats(c, c->d_tr_stats, u, sizeof u, "c->d_tr_stats");
     for (int k = 0; k < LH_TRBDF2_NSTATS; ++k) stats[k] = int64_t(u[k]);
-    return LH_OK;
+    return rc;
 }
 
 int lh_stable_dt_device(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double courant, void* d_out) {
@@ -1936,13 +1923,11 @@ int lh_stable_dt_device(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double
     if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
     (void)hipSetDevice(c->device);
     if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u))) return rc;
-    if (c->cfg.dtype == LH_F64) {
-        DevParams<double> P = make_params<double>(c);
-        launch_stable_dt<double>(P, planes_of<double>(Y), planes_of<double>(Ya), courant, d_out, any_percol(c), c->stream);
-    } else {
-        DevParams<float> P = make_params<float>(c);
-        launch_stable_dt<float>(P, planes_of<float>(Y), planes_of<float>(Ya), float(courant), d_out, any_percol(c), c->stream);
-    }
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        launch_stable_dt<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), FT(courant), d_out, any_percol(c), c->stream);
+    });
     LH_HIP(c, hipGetLastError());
     return allreduce_min(c, d_out); // the global minimum when a communicator is attached
 }
@@ -1951,18 +1936,13 @@ int lh_stable_dt(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double couran
     if (!c || !dt_host) return fail(c, LH_EINVAL, "lh_stable_dt: NULL argument");
     int rc = lh_stable_dt_device(c, Y, Ya, courant, c->d_dt);
     if (rc) return rc;
-    if (c->cfg.dtype == LH_F64) {
-        double v;
-        LH_HIP(c, hipMemcpyAsync(&v, c->d_dt, 8, hipMemcpyDeviceToHost, c->stream));
+    return with_ft(c, [&](auto ft) {
+        decltype(ft) v;
+        LH_HIP(c, hipMemcpyAsync(&v, c->d_dt, sizeof v, hipMemcpyDeviceToHost, c->stream));
         LH_HIP(c, hipStreamSynchronize(c->stream));
         *dt_host = v;
-    } else {
-        float v;
-        LH_HIP(c, hipMemcpyAsync(&v, c->d_dt, 4, hipMemcpyDeviceToHost, c->stream));
-        LH_HIP(c, hipStreamSynchronize(c->stream));
-        *dt_host = v;
-    }
-    return LH_OK;
+        return int(LH_OK);
+    });
 }
 
 int lh_get_status(lh_ctx* c, uint32_t* flags) {
@@ -1994,7 +1974,6 @@ int lh_tune_placement(lh_ctx* c, lh_state* Y, const lh_state* Ya, lh_state* dY, 
     if (flags & ~uint32_t(LH_PLACE_MOVE_INPUT)) return fail(c, LH_EINVAL, "lh_tune_placement: unknown flag bits");
     (void)hipSetDevice(c->device);
     if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u)) || (rc = materialize(c, dY, ~0u))) return rc;
-    const bool f64 = c->cfg.dtype == LH_F64;
     lh_state* written = dY;
     if (!dY && (use_column_stepper(c, 1) || segment_length(c) > 0)) { // no stage state in HBM, or a cache-resident one
         if (ms_before) *ms_before = 0;
@@ -2007,16 +1986,13 @@ int lh_tune_placement(lh_ctx* c, lh_state* Y, const lh_state* Ya, lh_state* dY, 
     }
     auto run = [&]() -> int {
         if (dY) // the tendency launch of lh_rhs / lh_rhs_stable_dt
-            return f64 ? do_rhs<double>(c, Y, Ya, nullptr, dY, 0.0, 0, nullptr)
-                       : do_rhs<float>(c, Y, Ya, nullptr, dY, 0.0, 0, nullptr);
+            return with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, Y, Ya, nullptr, dY, 0.0, 0, nullptr); });
         // stages 1 and 2 with dt = 0 stream the same planes as a step and leave Y untouched
         // (U1 = Y + 0 f(Y); U1 = (3Y + U1 + 0 f(U1))/4)
         lh_state* U1 = c->scratch_u1;
-        int r = f64 ? do_rhs<double>(c, Y, Ya, Y, U1, 0.0, 1, nullptr)
-                    : do_rhs<float>(c, Y, Ya, Y, U1, 0.0, 1, nullptr);
+        int r = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, Y, Ya, Y, U1, 0.0, 1, nullptr); });
         if (r) return r;
-        return f64 ? do_rhs<double>(c, U1, Ya, Y, U1, 0.0, 2, nullptr)
-                   : do_rhs<float>(c, U1, Ya, Y, U1, 0.0, 2, nullptr);
+        return with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, U1, Ya, Y, U1, 0.0, 2, nullptr); });
     };
     // The written planes matter most (two write streams in an unlucky relative position cost
     // ~12 %; reads hardly care): first the written state as a whole, then each of its planes
@@ -2126,15 +2102,12 @@ int lh_stream_probe(lh_ctx* c, const lh_state* in, uint32_t read_mask, lh_state*
     const double touched = double(c->cfg.nlev) * double(c->stride) * double(c->esize) * (nr + nw);
     const bool nt = c->tune.nt >= 0 ? c->tune.nt != 0 : touched > 192.0 * 1024 * 1024; // as launch_rhs_model
     auto go = [&]() {
-        if (c->cfg.dtype == LH_F64) {
-            Planes<double> pi, po;
-            for (int k = 0; k < 4; ++k) pi.v[k] = static_cast<double*>(rp[k]), po.v[k] = static_cast<double*>(wp[k]);
-            launch_stream_probe<double>(c->cfg.ncols, c->stride, c->cfg.nlev, c->tune.xcd, pi, nr, po, nw, nt, c->stream);
-        } else {
-            Planes<float> pi, po;
-            for (int k = 0; k < 4; ++k) pi.v[k] = static_cast<float*>(rp[k]), po.v[k] = static_cast<float*>(wp[k]);
-            launch_stream_probe<float>(c->cfg.ncols, c->stride, c->cfg.nlev, c->tune.xcd, pi, nr, po, nw, nt, c->stream);
-        }
+        with_ft(c, [&](auto ft) {
+            using FT = decltype(ft);
+            Planes<FT> pi, po;
+            for (int k = 0; k < 4; ++k) pi.v[k] = static_cast<FT*>(rp[k]), po.v[k] = static_cast<FT*>(wp[k]);
+            launch_stream_probe<FT>(c->cfg.ncols, c->stride, c->cfg.nlev, c->tune.xcd, pi, nr, po, nw, nt, c->stream);
+        });
     };
     mark_written(out, write_mask);
     for (int r = 0; r < 3; ++r) go();

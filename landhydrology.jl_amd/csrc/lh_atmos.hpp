@@ -28,6 +28,7 @@
 //       there either.
 #pragma once
 #include "lh_closures.hpp"
+#include "lh_dispatch.hpp"
 
 namespace lh {
 
@@ -213,8 +214,9 @@ template <typename FT>
 void launch_atmos_flux(const DevParams<FT>& P, const AtmosParams<FT>& A, int64_t n, bool from_state, bool percol,
                        const FT* vl, const FT* ti, const FT* third, FT* out_heat, FT* out_water, hipStream_t s) {
     dim3 g((unsigned)((n + 255) / 256)), b(256);
-    if (percol) hipLaunchKernelGGL((atmos_flux_kernel<FT, true>), g, b, 0, s, P, A, n, from_state, vl, ti, third, out_heat, out_water);
-    else hipLaunchKernelGGL((atmos_flux_kernel<FT, false>), g, b, 0, s, P, A, n, from_state, vl, ti, third, out_heat, out_water);
+    with_bool(percol, [&](auto pc) {
+        hipLaunchKernelGGL((atmos_flux_kernel<FT, decltype(pc)::value>), g, b, 0, s, P, A, n, from_state, vl, ti, third, out_heat, out_water);
+    });
 }
 
 } // namespace lh

@@ -131,6 +131,14 @@ struct ImplicitArgs {
     unsigned long long* total_iters; // Newton iterations over all column-steps
 };
 
+// lh_step_implicit_euler's statistics of one call: the device block ImplicitArgs' three counters point
+// into, and what the host reads back
+struct ImplicitStats {
+    int32_t max_iters;
+    unsigned long long unconverged, total_iters;
+};
+static_assert(sizeof(ImplicitStats) == 24, "one int32 (padded) and two 64-bit counters");
+
 // lh_integrate_trbdf2's launch (lh_implicit.hpp)
 template <typename FT>
 struct Trbdf2Args {

@@ -21,6 +21,7 @@
 //     float: v_log_f32 / v_exp_f32 (hardware, ~1 ulp each).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "lh_dispatch.hpp"
 
 namespace lh {
 
@@ -269,5 +270,12 @@ template <> struct MathFast<float> {
 // fused multiply-add in the working type (plain __builtin_fma is the double one)
 __device__ __forceinline__ double fma_ft(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_ft(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// f(type_c<M>{}) for the math policy of a launch: MathLibm (parity debugging) or the production MathFast
+template <typename FT, typename F>
+inline void with_math(bool libm, F&& f) {
+    if (libm) f(type_c<MathLibm<FT>>{});
+    else f(type_c<MathFast<FT>>{});
+}
 
 } // namespace lh

@@ -14,9 +14,8 @@
 // v_n lives in a third scratch plane, written by the first upward sweep of the step.
 // The Jacobian is approximate (slopes in Float32, water_slopes); R always uses the exact f.
 #pragma once
-#include "lh_closures.hpp"
-// (included after lh_kernels_impl.hpp: grid_for, stage_math_tables, fmin_ft / fmax_ft; ImplicitArgs and
-// Trbdf2Args are in lh_device.hpp)
+#include "lh_kernels_impl.hpp" // grid_for, stage_math_tables, fmin_ft / fmax_ft; with it lh_closures.hpp, lh_launch.hpp,
+                               // lh_dispatch.hpp (with_bool), lh_fastmath.hpp (with_math) and lh_device.hpp (ImplicitArgs, Trbdf2Args)
 
 namespace lh {
 
@@ -91,6 +90,34 @@ template <typename M>
 constexpr int implicit_threads() {
     return M::uses_tables ? 512 : 256; // (the Float64 tables take 48 KiB of LDS per workgroup)
 }
+
+// Which <M, PERCOL, NOICE, VGF> of implicit_euler_kernel / trbdf2_kernel exist: every one of the production
+// math (noice_exists, no conductivity factors here), and one per PERCOL of MathLibm, which reads theta_i
+// and has no tables for VGF to mean anything -- it is spelled NOICE = false, VGF = false.
+template <typename M>
+constexpr bool implicit_variant_exists(bool noice, bool vgf) { return M::is_production || (!noice && !vgf); }
+
+// f(type_c<M>, PERCOL, NOICE, VGF) for the variant a launch of either kernel takes
+template <typename FT, typename F>
+inline void with_implicit_variant(const DevParams<FT>& P, bool percol, bool noice, int math, F&& f) {
+    const bool libm = math == MATH_LIBM;
+    const bool ni = noice && !libm;
+    // clay-like Float64 ensembles: the v_ldexp form, as rhs_kernel.  (The Float32 VGF = false kernels are
+    // instantiated and never chosen: MathFast<float> has no tables, they are the VGF = true code.)
+    const bool vg = !libm && !(sizeof(FT) == 8 && P.vg_fast_all == 0);
+    with_math<FT>(libm, [&](auto m) { with_bool(percol, [&](auto pc) { with_bool(ni, [&](auto i) { with_bool(vg, [&](auto v) {
+        if constexpr (implicit_variant_exists<typename decltype(m)::type>(decltype(i)::value, decltype(v)::value)) f(m, pc, i, v);
+    }); }); }); });
+}
+
+// The opening both kernels share: the math tables staged in LDS (every thread of the workgroup) ...
+template <typename M>
+__device__ __forceinline__ M implicit_math(const double* math_tab) {
+    __shared__ double s_tab[M::uses_tables ? MATH_TAB_DOUBLES : 2];
+    return M(stage_math_tables<M>(math_tab, s_tab));
+}
+// ... and the column this lane owns
+__device__ __forceinline__ int64_t implicit_lane_column() { return int64_t(blockIdx.x) * blockDim.x + threadIdx.x; }
 
 // The column's constants of one solve: ColC, the K and conductance scales of rhs_kernel's
 // instantiation, the safeguard's bound
@@ -298,9 +325,8 @@ __device__ __forceinline__ void implicit_column(const M& mm, DevParams<FT> P, co
 template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF>
 __global__ void __launch_bounds__(implicit_threads<M>())
 implicit_euler_kernel(const DevParams<FT> P, const ImplicitArgs<FT> A) {
-    __shared__ double s_tab[M::uses_tables ? MATH_TAB_DOUBLES : 2];
-    const M mm(stage_math_tables<M>(P.math_tab, s_tab)); // (every thread)
-    const int64_t col = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const M mm = implicit_math<M>(P.math_tab);
+    const int64_t col = implicit_lane_column();
     int my_max = 0;
     unsigned long long unconv = 0, total = 0;
     if (col < P.ncols) implicit_column<FT, M, PERCOL, NOICE, VGF>(mm, P, A, col, my_max, unconv, total);
@@ -325,27 +351,11 @@ implicit_euler_kernel(const DevParams<FT> P, const ImplicitArgs<FT> A) {
 template <typename FT>
 void launch_implicit_euler(const DevParams<FT>& P, const ImplicitArgs<FT>& A, bool percol, bool noice, int math,
                            hipStream_t s) {
-    const bool ni = noice && math != MATH_LIBM;
-    const bool robust = P.vg_fast_all == 0;
-#define LH_IE(MATH, PC, NI, VG)                                                                          \
-    hipLaunchKernelGGL((implicit_euler_kernel<FT, MATH, PC, NI, VG>), grid_for(P.ncols, implicit_threads<MATH>()), \
-                       dim3(implicit_threads<MATH>()), 0, s, P, A)
-#define LH_IE_PC(MATH, NI, VG)                 \
-    do {                                       \
-        if (percol) LH_IE(MATH, true, NI, VG); \
-        else LH_IE(MATH, false, NI, VG);       \
-    } while (0)
-    if (math == MATH_LIBM) {
-        LH_IE_PC(MathLibm<FT>, false, false);
-    } else if (sizeof(FT) == 8 && robust) { // clay-like ensembles: the v_ldexp form, as rhs_kernel
-        if (ni) LH_IE_PC(MathFast<FT>, true, false);
-        else LH_IE_PC(MathFast<FT>, false, false);
-    } else {
-        if (ni) LH_IE_PC(MathFast<FT>, true, true);
-        else LH_IE_PC(MathFast<FT>, false, true);
-    }
-#undef LH_IE_PC
-#undef LH_IE
+    with_implicit_variant(P, percol, noice, math, [&](auto m, auto pc, auto ni, auto vg) {
+        using M = typename decltype(m)::type;
+        hipLaunchKernelGGL((implicit_euler_kernel<FT, M, decltype(pc)::value, decltype(ni)::value, decltype(vg)::value>),
+                           grid_for(P.ncols, implicit_threads<M>()), dim3(implicit_threads<M>()), 0, s, P, A);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -534,9 +544,8 @@ __device__ __forceinline__ void trbdf2_column(const M& mm, DevParams<FT> P, cons
 template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF>
 __global__ void __launch_bounds__(implicit_threads<M>())
 trbdf2_kernel(const DevParams<FT> P, const Trbdf2Args<FT> A) {
-    __shared__ double s_tab[M::uses_tables ? MATH_TAB_DOUBLES : 2];
-    const M mm(stage_math_tables<M>(P.math_tab, s_tab)); // (every thread)
-    const int64_t col = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const M mm = implicit_math<M>(P.math_tab);
+    const int64_t col = implicit_lane_column();
     Trbdf2ColStats st;
     if (col < P.ncols) trbdf2_column<FT, M, PERCOL, NOICE, VGF>(mm, P, A, col, st);
     // (every lane of the wave gets here, those past the last column with zeros): one atomic per counter and wave
@@ -572,27 +581,11 @@ trbdf2_kernel(const DevParams<FT> P, const Trbdf2Args<FT> A) {
 
 template <typename FT>
 void launch_trbdf2(const DevParams<FT>& P, const Trbdf2Args<FT>& A, bool percol, bool noice, int math, hipStream_t s) {
-    const bool ni = noice && math != MATH_LIBM;
-    const bool robust = P.vg_fast_all == 0;
-#define LH_TR(MATH, PC, NI, VG)                                                                      \
-    hipLaunchKernelGGL((trbdf2_kernel<FT, MATH, PC, NI, VG>), grid_for(P.ncols, implicit_threads<MATH>()), \
-                       dim3(implicit_threads<MATH>()), 0, s, P, A)
-#define LH_TR_PC(MATH, NI, VG)                 \
-    do {                                       \
-        if (percol) LH_TR(MATH, true, NI, VG); \
-        else LH_TR(MATH, false, NI, VG);       \
-    } while (0)
-    if (math == MATH_LIBM) {
-        LH_TR_PC(MathLibm<FT>, false, false);
-    } else if (sizeof(FT) == 8 && robust) {
-        if (ni) LH_TR_PC(MathFast<FT>, true, false);
-        else LH_TR_PC(MathFast<FT>, false, false);
-    } else {
-        if (ni) LH_TR_PC(MathFast<FT>, true, true);
-        else LH_TR_PC(MathFast<FT>, false, true);
-    }
-#undef LH_TR_PC
-#undef LH_TR
+    with_implicit_variant(P, percol, noice, math, [&](auto m, auto pc, auto ni, auto vg) {
+        using M = typename decltype(m)::type;
+        hipLaunchKernelGGL((trbdf2_kernel<FT, M, decltype(pc)::value, decltype(ni)::value, decltype(vg)::value>),
+                           grid_for(P.ncols, implicit_threads<M>()), dim3(implicit_threads<M>()), 0, s, P, A);
+    });
 }
 
 #define LH_INSTANTIATE_IMPLICIT(FT)                                                                                  \

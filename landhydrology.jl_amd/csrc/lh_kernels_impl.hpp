@@ -12,6 +12,7 @@
 #pragma once
 #include "lh_closures.hpp"
 #include "lh_launch.hpp"
+#include "lh_dispatch.hpp"
 #include "lh_atmos.hpp"
 #include <type_traits>
 
@@ -282,6 +283,32 @@ __device__ __forceinline__ bool finite(FT x) {
 // VGF (Float64 production math): every column of the context has m = 1 - 1/n >= LH_VG_FAST_MIN_M, so the
 // water closures put the exponents of their 2^(.) in place by integer addition (water_closures_log); the
 // host decides (DevParams::vg_fast_all), clay-like ensembles run the VGF = false instantiation.
+//
+// Which variants exist.  The launchers instantiate the combinations these predicates allow and no other;
+// rhs_kernel, the two column steppers and the implicit kernels (lh_implicit.hpp) share the first two.
+// NOICE: MathLibm is the parity-debugging policy and always reads theta_i, and the impedance factor is a
+// function of theta_i, so a launch with conductivity factors reads the plane whatever its zero bit says.
+template <typename M>
+constexpr bool noice_exists(bool factors) { return M::is_production && !factors; }
+// VGF = false: the integer-exponent form it switches off lives in the table-driven 2^(.) of the water
+// closures, which only the Float64 production math of a water model has.
+template <typename M, int MODEL>
+constexpr bool robust_vg_exists() { return M::uses_tables && MODEL != MODEL_HEAT; }
+// ... and clay-like ensembles are rare: they get the production launch shape with plain access, nothing else.
+template <typename CFG>
+constexpr bool robust_shape_exists() { return !CFG::NT && !CFG::SEG; }
+// MODE: MathLibm checks the tendency itself (mode 0); the fused stages and the step bound have no such build.
+template <typename M, int MODE>
+constexpr bool rhs_mode_exists() { return M::is_production || MODE == 0; }
+#ifdef LH_TUNING_VARIANTS
+// tuning builds (LH_TUNE cpl= pf= nt=): the launch shapes worth measuring -- plain access only for one
+// column per lane, prefetch deeper than 2 only there too
+constexpr bool tuning_shape_exists(int cpl, int pf, bool nt) {
+    if (pf < 1) return false;
+    if (!nt) return cpl == 1 && pf <= 2;
+    return (cpl == 1 && pf <= 4) || ((cpl == 2 || cpl == 4) && pf <= 2);
+}
+#endif
 template <typename FT, int MODEL, bool FACTORS, bool PERCOL, typename CFG, typename M, int MODE, bool NOICE = false, bool VGF = true>
 __global__ void __launch_bounds__((rhs_max_threads<M, rhs_waves_per_simd<FT, MODEL, FACTORS, PERCOL, M, CFG::PF, MODE, NOICE, CFG::CPL>()>()),
                                   (rhs_min_waves<M, rhs_waves_per_simd<FT, MODEL, FACTORS, PERCOL, M, CFG::PF, MODE, NOICE, CFG::CPL>()>()))
@@ -1585,45 +1612,41 @@ __global__ void init_bits_kernel(typename Bits<FT>::type* p) {
 }
 
 // ------------------------------------------------------------- launchers
+// Every launcher normalises its run-time flags, turns them into constants with with_bool / with_int
+// (lh_dispatch.hpp) and instantiates exactly the combinations the *_exists predicates beside the
+// kernels allow.
 
 static inline dim3 grid_for(int64_t work, int block) {
     return dim3((unsigned)((work + block - 1) / block));
 }
 
-template <typename FT, int MODEL, bool FACTORS, bool PERCOL, typename CFG, typename M, bool NOICE, bool VGF = true>
+using model_list = int_list<MODEL_RICHARDS, MODEL_HEAT, MODEL_COUPLED>; // (with_int: any other value is the coupled model)
+
+template <typename FT, int MODEL, bool FACTORS, bool PERCOL, typename CFG, typename M, bool NOICE, bool VGF>
 static void launch_rhs_mode(const DevParams<FT>& P, const Planes<FT>& in, const Planes<FT>& aux,
                             const Planes<FT>& base, const Planes<FT>& out, FT dt, const FT* dt_dev,
                             int mode, int block_req, hipStream_t s) {
-    // workgroup size: the kernel's own (see rhs_max_threads) unless LH_TUNE block= asks for less
-    const int mode_k = M::is_production ? mode : 0;
-    int kmax = 256;
-#define LH_KMAX(MD) case MD: kmax = rhs_max_threads<M, rhs_waves_per_simd<FT, MODEL, FACTORS, PERCOL, M, CFG::PF, MD, NOICE && M::is_production, CFG::CPL>()>(); break;
-    switch (mode_k) { LH_KMAX(0) LH_KMAX(1) LH_KMAX(2) LH_KMAX(3) LH_KMAX(4) LH_KMAX(5) }
-#undef LH_KMAX
-    const int block = (block_req > 0 && block_req <= kmax) ? block_req : kmax;
-    const int64_t lanes = (P.ncols + CFG::CPL - 1) / CFG::CPL;
-    dim3 g = grid_for(lanes, block), b(block);
-    if (CFG::SEG) g.y = (unsigned)((P.nlev + P.seg_len - 1) / P.seg_len);
-    // dynamic LDS: one word per thread for the mode-4 reduction
-    // (+ two level arrays for level-uniform prescribed fields of Ya where the kernel can take them)
-    constexpr bool MAY_PROF = (MODEL == MODEL_HEAT) || (MODEL == MODEL_RICHARDS && FACTORS);
-    const unsigned dyn = (unsigned)((mode == 4 ? (((size_t)block * sizeof(float) + 15) & ~(size_t)15) : 0) +
-                                    (MAY_PROF ? 2 * (size_t)P.nlev * sizeof(FT) : 0));
-    if constexpr (!M::is_production) { // MathLibm: tendency only (the other modes are never instantiated)
-        hipLaunchKernelGGL((rhs_kernel<FT, MODEL, FACTORS, PERCOL, CFG, M, 0, false>), g, b, dyn, s, P, in, aux, base, out, dt, dt_dev);
-    } else {
-        switch (mode) {
-            case 0: hipLaunchKernelGGL((rhs_kernel<FT, MODEL, FACTORS, PERCOL, CFG, M, 0, NOICE, VGF>), g, b, dyn, s, P, in, aux, base, out, dt, dt_dev); break;
-            case 1: hipLaunchKernelGGL((rhs_kernel<FT, MODEL, FACTORS, PERCOL, CFG, M, 1, NOICE, VGF>), g, b, dyn, s, P, in, aux, base, out, dt, dt_dev); break;
-            case 2: hipLaunchKernelGGL((rhs_kernel<FT, MODEL, FACTORS, PERCOL, CFG, M, 2, NOICE, VGF>), g, b, dyn, s, P, in, aux, base, out, dt, dt_dev); break;
-            case 3: hipLaunchKernelGGL((rhs_kernel<FT, MODEL, FACTORS, PERCOL, CFG, M, 3, NOICE, VGF>), g, b, dyn, s, P, in, aux, base, out, dt, dt_dev); break;
-            case 5: hipLaunchKernelGGL((rhs_kernel<FT, MODEL, FACTORS, PERCOL, CFG, M, 5, NOICE, VGF>), g, b, dyn, s, P, in, aux, base, out, dt, dt_dev); break;
-            default: // 4: tendency + stable-step bound; the minimum starts at +inf
+    // (mode 4 last: the list's default)
+    with_int(int_list<0, 1, 2, 3, 5, 4>{}, M::is_production ? mode : 0, [&](auto md) {
+        constexpr int MODE = decltype(md)::value;
+        if constexpr (rhs_mode_exists<M, MODE>()) {
+            constexpr auto kernel = rhs_kernel<FT, MODEL, FACTORS, PERCOL, CFG, M, MODE, NOICE, VGF>;
+            // workgroup size: the kernel's own (see rhs_max_threads) unless LH_TUNE block= asks for less
+            constexpr int kmax = rhs_max_threads<M, rhs_waves_per_simd<FT, MODEL, FACTORS, PERCOL, M, CFG::PF, MODE, NOICE, CFG::CPL>()>();
+            const int block = (block_req > 0 && block_req <= kmax) ? block_req : kmax;
+            const int64_t lanes = (P.ncols + CFG::CPL - 1) / CFG::CPL;
+            dim3 g = grid_for(lanes, block), b(block);
+            if (CFG::SEG) g.y = (unsigned)((P.nlev + P.seg_len - 1) / P.seg_len);
+            // dynamic LDS: one word per thread for the mode-4 reduction
+            // (+ two level arrays for level-uniform prescribed fields of Ya where the kernel can take them)
+            constexpr bool MAY_PROF = (MODEL == MODEL_HEAT) || (MODEL == MODEL_RICHARDS && FACTORS);
+            const unsigned dyn = (unsigned)((MODE == 4 ? (((size_t)block * sizeof(float) + 15) & ~(size_t)15) : 0) +
+                                            (MAY_PROF ? 2 * (size_t)P.nlev * sizeof(FT) : 0));
+            if (MODE == 4) // tendency + stable-step bound; the minimum starts at +inf
                 hipLaunchKernelGGL((init_bits_kernel<FT>), dim3(1), dim3(1), 0, s, reinterpret_cast<typename Bits<FT>::type*>(P.dt_out));
-                hipLaunchKernelGGL((rhs_kernel<FT, MODEL, FACTORS, PERCOL, CFG, M, 4, NOICE, VGF>), g, b, dyn, s, P, in, aux, base, out, dt, dt_dev);
-                break;
+            hipLaunchKernelGGL(kernel, g, b, dyn, s, P, in, aux, base, out, dt, dt_dev);
         }
-    }
+    });
 }
 
 template <typename FT, int MODEL, typename M>
@@ -1632,20 +1655,22 @@ static void launch_rhs_model(const DevParams<FT>& P, const Planes<FT>& in, const
                              int mode, bool factors, bool percol, bool noice, const Tune& tune, hipStream_t s) {
     using CFG = typename DefaultCfg<FT>::type;
     const int block = tune.block; // 0: the kernel's own workgroup size
+    const bool ni = noice && noice_exists<M>(factors);
 #ifdef LH_TUNING_VARIANTS
     // tuning builds: alternative columns-per-lane / prefetch depth for the plain tendency kernels
+    // (always VGF = true, whatever vg_fast_all says)
     if (!factors && !percol && mode == 0 && M::is_production && (tune.cpl > 0 || tune.pf > 0)) {
         const bool ntv = tune.nt >= 0 ? tune.nt != 0 : true;
         const int cplv = tune.cpl > 0 ? tune.cpl : CFG::CPL, pfv = tune.pf > 0 ? tune.pf : CFG::PF;
-#define LH_TRY(C, F, N)                                                                            \
-    if (cplv == C && pfv == F && ntv == N) {                                                       \
-        if (noice) launch_rhs_mode<FT, MODEL, false, false, KCfg<C, F, N>, M, true>(P, in, aux, base, out, dt, dt_dev, 0, block, s); \
-        else launch_rhs_mode<FT, MODEL, false, false, KCfg<C, F, N>, M, false>(P, in, aux, base, out, dt, dt_dev, 0, block, s); \
-        return;                                                                                    \
-    }
-        LH_TRY(1, 1, true) LH_TRY(1, 2, true) LH_TRY(1, 3, true) LH_TRY(1, 4, true)
-        LH_TRY(2, 1, true) LH_TRY(2, 2, true) LH_TRY(1, 1, false) LH_TRY(1, 2, false) LH_TRY(4, 1, true) LH_TRY(4, 2, true)
-#undef LH_TRY
+        if (tuning_shape_exists(cplv, pfv, ntv)) {
+            with_int(int_list<1, 2, 4>{}, cplv, [&](auto c) { with_int(int_list<1, 2, 3, 4>{}, pfv, [&](auto f) { with_bool(ntv, [&](auto n) { with_bool(ni, [&](auto i) {
+                constexpr int C = decltype(c)::value, F = decltype(f)::value;
+                constexpr bool N = decltype(n)::value, NI = decltype(i)::value;
+                if constexpr (tuning_shape_exists(C, F, N) && (!NI || noice_exists<M>(false)))
+                    launch_rhs_mode<FT, MODEL, false, false, KCfg<C, F, N>, M, NI, true>(P, in, aux, base, out, dt, dt_dev, 0, block, s);
+            }); }); }); });
+            return;
+        }
     }
 #endif
     // Nontemporal access when the launch streams more than the 256 MiB Infinity
@@ -1654,39 +1679,24 @@ static void launch_rhs_model(const DevParams<FT>& P, const Planes<FT>& in, const
     const int nplanes = (MODEL == MODEL_COUPLED) ? 6 : (MODEL == MODEL_RICHARDS ? 4 : 4);
     const double touched = double(P.nlev) * double(P.stride) * sizeof(FT) * nplanes;
     const bool nt = tune.nt >= 0 ? tune.nt != 0 : touched > 192.0 * 1024 * 1024;
-    using CFGN = KCfg<CFG::CPL, CFG::PF, true>;
-    using CFGP = KCfg<CFG::CPL, CFG::PF, false>;
-    using CFGS = KCfg<CFG::CPL, CFG::PF, false, true>; // level-segmented (small ensembles: cache-resident)
+    // level-segmented (small ensembles: cache-resident)
     const bool seg = M::is_production && P.seg_len > 0 && P.seg_len < P.nlev;
-    // the no-ice kernels exist for the production math without conductivity factors
-    const bool ni = noice && M::is_production && !factors;
     // clay-like ensembles (some column with m < LH_VG_FAST_MIN_M): the log-domain closures, one launch
     // shape (plain access, unsegmented) -- the Float64 water kernels only
-    constexpr bool has_robust = M::uses_tables && MODEL != MODEL_HEAT;
-    const bool robust = has_robust && P.vg_fast_all == 0;
-#define LH_GO3(F, PC, NI)                                                                             \
-    do {                                                                                              \
-        if constexpr (has_robust) {                                                                   \
-            if (robust) {                                                                             \
-                launch_rhs_mode<FT, MODEL, F, PC, CFGP, M, NI, false>(P, in, aux, base, out, dt, dt_dev, mode, block, s); \
-                break;                                                                                \
-            }                                                                                         \
-        }                                                                                             \
-        if (seg) launch_rhs_mode<FT, MODEL, F, PC, CFGS, M, NI>(P, in, aux, base, out, dt, dt_dev, mode, block, s); \
-        else if (nt) launch_rhs_mode<FT, MODEL, F, PC, CFGN, M, NI>(P, in, aux, base, out, dt, dt_dev, mode, block, s); \
-        else launch_rhs_mode<FT, MODEL, F, PC, CFGP, M, NI>(P, in, aux, base, out, dt, dt_dev, mode, block, s);   \
-    } while (0)
-    if (factors) {
-        if (percol) LH_GO3(true, true, false);
-        else LH_GO3(true, false, false);
-    } else if (ni) {
-        if (percol) LH_GO3(false, true, true);
-        else LH_GO3(false, false, true);
-    } else {
-        if (percol) LH_GO3(false, true, false);
-        else LH_GO3(false, false, false);
-    }
-#undef LH_GO3
+    const bool robust = robust_vg_exists<M, MODEL>() && P.vg_fast_all == 0;
+    enum { PLAIN, NONTEMPORAL, SEGMENTED };
+    const int shape = robust ? PLAIN : seg ? SEGMENTED : nt ? NONTEMPORAL : PLAIN;
+    with_bool(factors, [&](auto f) { with_bool(percol, [&](auto pc) { with_bool(ni, [&](auto i) { with_bool(!robust, [&](auto vg) {
+        with_int(int_list<NONTEMPORAL, SEGMENTED, PLAIN>{}, shape, [&](auto sh) {
+            constexpr bool F = decltype(f)::value, PC = decltype(pc)::value, NI = decltype(i)::value, VG = decltype(vg)::value;
+            constexpr int SH = decltype(sh)::value;
+            using C = KCfg<CFG::CPL, CFG::PF, SH == NONTEMPORAL, SH == SEGMENTED>;
+            // (the rules of the normalisation above once more: ni, robust and shape never take the other
+            // values at run time, the guard only keeps those combinations un-instantiated)
+            if constexpr ((!NI || noice_exists<M>(F)) && (VG || (robust_vg_exists<M, MODEL>() && robust_shape_exists<C>())))
+                launch_rhs_mode<FT, MODEL, F, PC, C, M, NI, VG>(P, in, aux, base, out, dt, dt_dev, mode, block, s);
+        });
+    }); }); }); });
 }
 
 // All rhs_kernel variants of one model.  Each (FT, MODEL) pair is instantiated in its own
@@ -1698,10 +1708,9 @@ void launch_rhs_for_model(const DevParams<FT>& P, const Planes<FT>& in, const Pl
                           hipStream_t s) {
     // MathLibm is a parity-debugging policy for the tendency itself (mode 0);
     // the fused SSPRK33 stages and mode 4 always run the production math.
-    if (math == MATH_LIBM && mode == 0)
-        launch_rhs_model<FT, MODEL, MathLibm<FT>>(P, in, aux, base, out, dt, dt_dev, mode, factors, percol, false, tune, s);
-    else
-        launch_rhs_model<FT, MODEL, MathFast<FT>>(P, in, aux, base, out, dt, dt_dev, mode, factors, percol, noice, tune, s);
+    with_math<FT>(math == MATH_LIBM && mode == 0, [&](auto m) {
+        launch_rhs_model<FT, MODEL, typename decltype(m)::type>(P, in, aux, base, out, dt, dt_dev, mode, factors, percol, noice, tune, s);
+    });
 }
 
 // Columns (= waves) per workgroup of column_stepper_wave_kernel.  Whole multiples of 4, so the four
@@ -1758,44 +1767,27 @@ void launch_column_stepper_for_model(const DevParams<FT>& P, const Planes<FT>& Y
     const size_t tile_words = (size_t)tiles * (size_t)P.nlev;
     const size_t dyn_col = (ex_words > tile_words ? ex_words : tile_words) * sizeof(FT);
     using M = MathFast<FT>;
-    constexpr bool has_robust = M::uses_tables && MODEL != MODEL_HEAT; // (as launch_rhs_model)
-    const bool robust = has_robust && P.vg_fast_all == 0;
-#define LH_CS_GO(F, PC, NI, VG)                                                                                                        \
-    do {                                                                                                                               \
-        if (wave && cw == 1) {                                                                                                         \
-            cpb = wave_stepper_columns<column_stepper_wave_kernel<FT, MODEL, F, PC, M, 1, NI, VG>>(P.ncols, dyn_col, nsteps);                  \
-        } else if (wave) {                                                                                                             \
-            cpb = wave_stepper_columns<column_stepper_wave_kernel<FT, MODEL, F, PC, M, 2, NI, VG>>(P.ncols, dyn_col, nsteps);                  \
-        }                                                                                                                              \
-        if (P.cs_cpb > 0 && (unsigned)P.cs_cpb * tpc <= 1024u) cpb = (unsigned)P.cs_cpb;                                               \
-        const dim3 g((unsigned)((P.ncols + cpb - 1) / cpb)), b(tpc * cpb);                                                             \
-        const unsigned dyn = (unsigned)(cpb * dyn_col);                                                                                \
-        if (wave && cw == 1) hipLaunchKernelGGL((column_stepper_wave_kernel<FT, MODEL, F, PC, M, 1, NI, VG>), g, b, dyn, s, P, Y, aux, dt, dt_dev, nsteps, bcv); \
-        else if (wave) hipLaunchKernelGGL((column_stepper_wave_kernel<FT, MODEL, F, PC, M, 2, NI, VG>), g, b, dyn, s, P, Y, aux, dt, dt_dev, nsteps, bcv);      \
-        else hipLaunchKernelGGL((column_stepper_kernel<FT, MODEL, F, PC, M, NI, VG>), g, b, dyn, s, P, Y, aux, dt, dt_dev, nsteps, bcv);                \
-    } while (0)
-#define LH_CS(F, PC, NI)                                    \
-    do {                                                    \
-        if constexpr (has_robust) {                         \
-            if (robust) {                                   \
-                LH_CS_GO(F, PC, NI, false);                 \
-                break;                                      \
-            }                                               \
-        }                                                   \
-        LH_CS_GO(F, PC, NI, true);                          \
-    } while (0)
-    if (factors) {
-        if (percol) LH_CS(true, true, false);
-        else LH_CS(true, false, false);
-    } else if (noice) {
-        if (percol) LH_CS(false, true, true);
-        else LH_CS(false, false, true);
-    } else {
-        if (percol) LH_CS(false, true, false);
-        else LH_CS(false, false, false);
-    }
-#undef LH_CS_GO
-#undef LH_CS
+    const bool ni = noice && noice_exists<M>(factors);
+    const bool robust = robust_vg_exists<M, MODEL>() && P.vg_fast_all == 0; // (as launch_rhs_model)
+    with_bool(factors, [&](auto f) { with_bool(percol, [&](auto pc) { with_bool(ni, [&](auto i) { with_bool(!robust, [&](auto vg) {
+        // cells per lane of the wave kernel; 0: the thread-per-cell kernel
+        with_int(int_list<1, 2, 0>{}, wave ? cw : 0, [&](auto w) {
+            constexpr bool F = decltype(f)::value, PC = decltype(pc)::value, NI = decltype(i)::value, VG = decltype(vg)::value;
+            constexpr int CW = decltype(w)::value;
+            // (ni and robust are normalised with the same rules: the guard only keeps what cannot occur un-instantiated)
+            if constexpr ((!NI || noice_exists<M>(F)) && (VG || robust_vg_exists<M, MODEL>())) {
+                constexpr auto kernel = [] {
+                    if constexpr (CW > 0) return column_stepper_wave_kernel<FT, MODEL, F, PC, M, CW, NI, VG>;
+                    else return column_stepper_kernel<FT, MODEL, F, PC, M, NI, VG>;
+                }();
+                if constexpr (CW > 0) cpb = wave_stepper_columns<kernel>(P.ncols, dyn_col, nsteps);
+                if (P.cs_cpb > 0 && (unsigned)P.cs_cpb * tpc <= 1024u) cpb = (unsigned)P.cs_cpb;
+                const dim3 g((unsigned)((P.ncols + cpb - 1) / cpb)), b(tpc * cpb);
+                const unsigned dyn = (unsigned)(cpb * dyn_col);
+                hipLaunchKernelGGL(kernel, g, b, dyn, s, P, Y, aux, dt, dt_dev, nsteps, bcv);
+            }
+        });
+    }); }); }); });
 }
 
 #define LH_CS_MODEL_ARGS(FT) \
@@ -1825,77 +1817,39 @@ template <typename FT>
 void launch_rhs(const DevParams<FT>& P, const Planes<FT>& in, const Planes<FT>& aux,
                 const Planes<FT>& base, const Planes<FT>& out, FT dt, const FT* dt_dev, int mode,
                 bool factors, bool percol, bool noice, int math, const Tune& tune, hipStream_t s) {
-    switch (P.model) {
-        case MODEL_RICHARDS: launch_rhs_for_model<FT, MODEL_RICHARDS>(P, in, aux, base, out, dt, dt_dev, mode, factors, percol, noice, math, tune, s); break;
-        case MODEL_HEAT: launch_rhs_for_model<FT, MODEL_HEAT>(P, in, aux, base, out, dt, dt_dev, mode, factors, percol, noice, math, tune, s); break;
-        default: launch_rhs_for_model<FT, MODEL_COUPLED>(P, in, aux, base, out, dt, dt_dev, mode, factors, percol, noice, math, tune, s); break;
-    }
+    with_int(model_list{}, P.model, [&](auto m) {
+        launch_rhs_for_model<FT, decltype(m)::value>(P, in, aux, base, out, dt, dt_dev, mode, factors, percol, noice, math, tune, s);
+    });
 }
 
 template <typename FT>
 void launch_column_stepper(const DevParams<FT>& P, const Planes<FT>& Y, const Planes<FT>& aux, FT dt,
                            const FT* dt_dev, int64_t nsteps, const FT* bcv, bool factors, bool percol,
                            bool noice, hipStream_t s) {
-    switch (P.model) {
-        case MODEL_RICHARDS: launch_column_stepper_for_model<FT, MODEL_RICHARDS>(P, Y, aux, dt, dt_dev, nsteps, bcv, factors, percol, noice, s); break;
-        case MODEL_HEAT: launch_column_stepper_for_model<FT, MODEL_HEAT>(P, Y, aux, dt, dt_dev, nsteps, bcv, factors, percol, noice, s); break;
-        default: launch_column_stepper_for_model<FT, MODEL_COUPLED>(P, Y, aux, dt, dt_dev, nsteps, bcv, factors, percol, noice, s); break;
-    }
+    with_int(model_list{}, P.model, [&](auto m) {
+        launch_column_stepper_for_model<FT, decltype(m)::value>(P, Y, aux, dt, dt_dev, nsteps, bcv, factors, percol, noice, s);
+    });
 }
 
 template <typename FT>
 void launch_diag(const DevParams<FT>& P, const Planes<FT>& in, const Planes<FT>& aux,
                  const Planes<FT>& out, bool percol, int math, hipStream_t s) {
     dim3 g = grid_for(P.ncols, 256), b(256);
-#define LH_DIAG(MODEL, MATH)                                                                           \
-    do {                                                                                               \
-        if (percol) hipLaunchKernelGGL((diag_kernel<FT, MODEL, true, true, MATH>), g, b, 0, s, P, in, aux, out);  \
-        else hipLaunchKernelGGL((diag_kernel<FT, MODEL, true, false, MATH>), g, b, 0, s, P, in, aux, out);        \
-    } while (0)
-#define LH_DIAG_M(MATH)                                          \
-    switch (P.model) {                                           \
-        case MODEL_RICHARDS: LH_DIAG(MODEL_RICHARDS, MATH); break; \
-        case MODEL_HEAT: LH_DIAG(MODEL_HEAT, MATH); break;         \
-        default: LH_DIAG(MODEL_COUPLED, MATH); break;              \
-    }
-    if (math == MATH_LIBM) {
-        LH_DIAG_M(MathLibm<FT>)
-    } else {
-        LH_DIAG_M(MathFast<FT>)
-    }
-#undef LH_DIAG_M
-#undef LH_DIAG
+    with_math<FT>(math == MATH_LIBM, [&](auto m) { with_int(model_list{}, P.model, [&](auto md) { with_bool(percol, [&](auto pc) {
+        hipLaunchKernelGGL((diag_kernel<FT, decltype(md)::value, true, decltype(pc)::value, typename decltype(m)::type>), g, b, 0, s, P, in, aux, out);
+    }); }); });
 }
 
 template <typename FT>
 void launch_boundary_fluxes(const DevParams<FT>& P, const Planes<FT>& in, const Planes<FT>& aux, int face, FT* out_e,
                             FT* out_w, bool factors, bool percol, int math, hipStream_t s) {
     dim3 g = grid_for(P.ncols, 256), b(256);
-#define LH_BF(MODEL, F, PC, MATH) hipLaunchKernelGGL((boundary_flux_kernel<FT, MODEL, F, PC, MATH>), g, b, 0, s, P, in, aux, face, out_e, out_w)
-#define LH_BF_M(MODEL, MATH)                                \
-    do {                                                    \
-        if (factors) {                                      \
-            if (percol) LH_BF(MODEL, true, true, MATH);     \
-            else LH_BF(MODEL, true, false, MATH);           \
-        } else {                                            \
-            if (percol) LH_BF(MODEL, false, true, MATH);    \
-            else LH_BF(MODEL, false, false, MATH);          \
-        }                                                   \
-    } while (0)
-#define LH_BF_MODEL(MATH)                                              \
-    switch (P.model) {                                                 \
-        case MODEL_RICHARDS: LH_BF_M(MODEL_RICHARDS, MATH); break;     \
-        case MODEL_HEAT: LH_BF_M(MODEL_HEAT, MATH); break;             \
-        default: LH_BF_M(MODEL_COUPLED, MATH); break;                  \
-    }
-    if (math == MATH_LIBM) {
-        LH_BF_MODEL(MathLibm<FT>)
-    } else {
-        LH_BF_MODEL(MathFast<FT>)
-    }
-#undef LH_BF_MODEL
-#undef LH_BF_M
-#undef LH_BF
+    with_math<FT>(math == MATH_LIBM, [&](auto m) { with_int(model_list{}, P.model, [&](auto md) {
+        with_bool(factors, [&](auto f) { with_bool(percol, [&](auto pc) {
+            hipLaunchKernelGGL((boundary_flux_kernel<FT, decltype(md)::value, decltype(f)::value, decltype(pc)::value, typename decltype(m)::type>),
+                               g, b, 0, s, P, in, aux, face, out_e, out_w);
+        }); });
+    }); });
 }
 
 template <typename FT>
@@ -1905,27 +1859,18 @@ void launch_stable_dt(const DevParams<FT>& P, const Planes<FT>& in, const Planes
     U* out = reinterpret_cast<U*>(out_ft);
     hipLaunchKernelGGL((init_bits_kernel<FT>), dim3(1), dim3(1), 0, s, out);
     dim3 g = grid_for(P.ncols, 256), b(256);
-#define LH_SDT(MODEL)                                                                                       \
-    do {                                                                                                    \
-        if (percol) hipLaunchKernelGGL((stable_dt_kernel<FT, MODEL, true, MathFast<FT>>), g, b, 0, s, P, in, aux, courant, out);  \
-        else hipLaunchKernelGGL((stable_dt_kernel<FT, MODEL, false, MathFast<FT>>), g, b, 0, s, P, in, aux, courant, out);        \
-    } while (0)
-    switch (P.model) {
-        case MODEL_RICHARDS: LH_SDT(MODEL_RICHARDS); break;
-        case MODEL_HEAT: LH_SDT(MODEL_HEAT); break;
-        default: LH_SDT(MODEL_COUPLED); break;
-    }
-#undef LH_SDT
+    with_int(model_list{}, P.model, [&](auto md) { with_bool(percol, [&](auto pc) {
+        hipLaunchKernelGGL((stable_dt_kernel<FT, decltype(md)::value, decltype(pc)::value, MathFast<FT>>), g, b, 0, s, P, in, aux, courant, out);
+    }); });
 }
 
 template <typename FT>
 void launch_strided_copy(FT* plane, int64_t stride, FT* user, int64_t ls, int64_t cs,
                          int64_t ncols, int nlev, bool to_plane, hipStream_t s) {
     dim3 g((unsigned)((ncols + 63) / 64), (unsigned)((nlev + 63) / 64)), b(256);
-    if (to_plane)
-        hipLaunchKernelGGL((strided_copy_kernel<FT, true>), g, b, 0, s, plane, stride, user, ls, cs, ncols, nlev);
-    else
-        hipLaunchKernelGGL((strided_copy_kernel<FT, false>), g, b, 0, s, plane, stride, user, ls, cs, ncols, nlev);
+    with_bool(to_plane, [&](auto tp) {
+        hipLaunchKernelGGL((strided_copy_kernel<FT, decltype(tp)::value>), g, b, 0, s, plane, stride, user, ls, cs, ncols, nlev);
+    });
 }
 
 template <typename FT>
@@ -1935,8 +1880,9 @@ void launch_stream_probe(int64_t ncols, int64_t stride, int nlev, int xcd_remap,
     constexpr int CPL = CFG::CPL, PF = CFG::PF;
     const int64_t lanes = (ncols + CPL - 1) / CPL;
     dim3 g = grid_for(lanes, 256), b(256);
-    if (nt) hipLaunchKernelGGL((stream_probe_kernel<FT, CPL, PF, true>), g, b, 0, s, ncols, stride, nlev, xcd_remap, in, nr, out, nw);
-    else hipLaunchKernelGGL((stream_probe_kernel<FT, CPL, PF, false>), g, b, 0, s, ncols, stride, nlev, xcd_remap, in, nr, out, nw);
+    with_bool(nt, [&](auto n) {
+        hipLaunchKernelGGL((stream_probe_kernel<FT, CPL, PF, decltype(n)::value>), g, b, 0, s, ncols, stride, nlev, xcd_remap, in, nr, out, nw);
+    });
 }
 
 template <typename FT>
