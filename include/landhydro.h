@@ -354,6 +354,45 @@ int lh_step_ssprk33_device_dt(lh_ctx*, lh_state* Y, const lh_state* Ya, double t
 int lh_step_ssprk33_adaptive(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double courant,
                              double dt_max, int64_t nsteps, void* dt_device_ft, void* elapsed_device_ft);
 
+/* lh_step_ssprk33_adaptive with the step size HELD for `hold` steps: nchunks chunks of `hold`
+ * SSPRK33 steps each (1 <= hold <= 2^20, nchunks >= 0), nothing leaving the device.  Per chunk: the
+ * stable-step bound of the current Y (the rule of lh_rhs_stable_dt; the RCCL min over ranks follows
+ * when a communicator is attached -- one collective per chunk, not per step), dt formed from it
+ * exactly as lh_step_ssprk33_adaptive forms it (dt_max, the dt = 0 fallback and status bit 2
+ * included), then `hold` steps at that dt, and *elapsed advanced by `hold` successive += dt.
+ * Every column takes the same dt sequence.  Y and the dt of every chunk are bitwise those of: copy
+ * Y to Z, lh_step_ssprk33_adaptive(Z, nsteps = 1, dtbuf), then `hold` x
+ * lh_step_ssprk33_device_dt(Y, dtbuf); with hold = 1 the call is bitwise
+ * lh_step_ssprk33_adaptive(nsteps = nchunks).
+ * Where the persistent column stepper serves the call (lh_adaptive_hold_engine) a chunk is ONE
+ * launch, which also leaves the bound of the state it ends on: nchunks + 1 heavy launches instead of
+ * 3 nchunks hold.  Elsewhere a chunk is the bound's launch plus `hold` x the three fused stages
+ * (3 hold + 1 launches, f(Y) evaluated twice for the chunk's first step) and the call ends with
+ * one more bound launch: slower than lh_step_ssprk33_adaptive at small `hold` (four launches
+ * against three per step at hold = 1), level with it at large `hold`, never faster.  On
+ * ensembles of more than 2^20 lanes (ncolumns x nlev rounded up to 64) the stepper serves calls of 3
+ * steps and more only, so hold = 1 and hold = 2 take that path there: use hold >= 3, in practice 8
+ * and more (the bound's extra closure pass and the launch are paid once per chunk).
+ * hold <= 1048576 (2^20; LH_EINVAL above): *elapsed is advanced by a one-thread loop of `hold`
+ * additions between two chunks.
+ * Overrun flag: after every chunk (the last included) the rank-reduced bound of the state the chunk
+ * ENDED on is compared with the dt the chunk used; a bound below that dt, or one that is not a
+ * positive finite number, sets bit 5 (value 32) of lh_get_status: the held step exceeded the stable
+ * step of the state it produced -- `hold` or `courant` is too aggressive.  The call goes on.
+ * dt_device_ft holds the last chunk's dt afterwards.  Boundary values are the constants of
+ * lh_set_bc.  Does not synchronise. */
+int lh_step_ssprk33_adaptive_hold(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double courant,
+                                  double dt_max, int64_t nchunks, int32_t hold,
+                                  void* dt_device_ft, void* elapsed_device_ft);
+
+/* Which engine lh_step_ssprk33_adaptive_hold runs the chunks of a call with (as lh_step_engine):
+ * LH_ENGINE_COLUMN_STEPPER = one stepper launch per chunk, LH_ENGINE_FUSED_STAGES = 3 hold + 1
+ * streamed launches per chunk (more than 128 levels, the Float64 coupled model with conductivity
+ * factors on large ensembles, a prescribed atmosphere, LH_TUNE persist=0, and hold < 3 on
+ * ensembles of more than 2^20 lanes).
+ * Returns the engine (>= 0) or a negative LH_E* code. */
+int lh_adaptive_hold_engine(const lh_ctx*, int32_t hold);
+
 /* Backward-Euler steps of a Richards model: per step, Newton on
  * Y - Yn - dt f(Y, t+dt) = 0 with f exactly lh_rhs's tendency, one tridiagonal solve per
  * column and iteration.  bcv: NULL (current boundary values) or nsteps*4 doubles at t_{n+1}.
@@ -456,7 +495,8 @@ int lh_allreduce_min(lh_ctx*, void* value_device_ft);
  * no dt_max, or a NaN) and was taken with dt = 0; bit 3: an implicit step (lh_step_implicit_euler)
  * did not converge in some column (also the fixed-step mode of lh_integrate_trbdf2); bit 4: a column
  * of lh_integrate_trbdf2 failed (its step fell below the floor or it hit the step cap) and did not
- * reach t1; synchronises and clears. */
+ * reach t1; bit 5: a chunk of lh_step_ssprk33_adaptive_hold held a step that exceeded the stable step of
+ * the state it produced; synchronises and clears. */
 int lh_get_status(lh_ctx*, uint32_t* flags);
 int lh_synchronize(lh_ctx*);
 /* Streaming ceiling of the column launch on a given set of planes (measurement aid, no

@@ -733,8 +733,10 @@ bool use_column_stepper(const lh_ctx* c, int64_t nsteps, bool bcv = false) {
     return nsteps >= 3;
 }
 
+// bound_out (the wave stepper, <= 128 levels, with dt_device): one FT word that receives the stable-step
+// bound of the state the call ends on, `dt` then being the Courant factor (lh_step_ssprk33_adaptive_hold)
 int run_column_stepper(lh_ctx* c, lh_state* Y, const lh_state* Ya, double dt, const void* dt_device,
-                       int64_t nsteps, const double* bcv) {
+                       int64_t nsteps, const double* bcv, void* bound_out = nullptr) {
     if (nsteps <= 0) return LH_OK;
     Range r_("lh:column_stepper");
     DeviceBuffer d_bcv; // [nsteps][3][2][2] doubles -> FT on the device
@@ -753,8 +755,9 @@ int run_column_stepper(lh_ctx* c, lh_state* Y, const lh_state* Ya, double dt, co
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
         set_aux_profiles<FT>(c, Ya, P);
+        P.dt_out = bound_out;
         launch_column_stepper<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), FT(dt), static_cast<const FT*>(dt_device),
-                                  nsteps, static_cast<const FT*>(d_bcv.p), factors, any_percol(c), noice, c->stream);
+                                  nsteps, static_cast<const FT*>(d_bcv.p), factors, any_percol(c), noice, bound_out != nullptr, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
     const hipError_t e = launch_error(c, d_bcv);
@@ -1711,6 +1714,80 @@ int lh_step_ssprk33_adaptive(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
             }
         }
     }
+    LH_HIP(c, hipGetLastError());
+    return LH_OK;
+}
+
+// The longest chunk (2^20 steps): the one-thread kernel between two chunks advances `elapsed` by `hold`
+// successive additions, and one stepper launch runs `hold` steps -- both stay well inside a second.
+static constexpr int32_t ADAPTIVE_HOLD_MAX = 1 << 20;
+
+// One stepper launch per chunk: the stepper serves a call of `hold` steps and the column fits its wave form
+static bool adaptive_hold_in_stepper(const lh_ctx* c, int32_t hold) {
+    return use_column_stepper(c, hold, false) && c->cfg.nlev <= 128;
+}
+
+int lh_adaptive_hold_engine(const lh_ctx* c, int32_t hold) {
+    if (!c || hold < 1 || hold > ADAPTIVE_HOLD_MAX) return LH_EINVAL;
+    return adaptive_hold_in_stepper(c, hold) ? LH_ENGINE_COLUMN_STEPPER : LH_ENGINE_FUSED_STAGES;
+}
+
+int lh_step_ssprk33_adaptive_hold(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double courant, double dt_max,
+                                  int64_t nchunks, int32_t hold, void* dt_device_ft, void* elapsed_device_ft) {
+    (void)t;
+    if (!c || !dt_device_ft) return fail(c, LH_EINVAL, "lh_step_ssprk33_adaptive_hold: NULL argument");
+    if (nchunks < 0 || hold < 1 || hold > ADAPTIVE_HOLD_MAX || !(courant > 0))
+        return fail(c, LH_EINVAL, "lh_step_ssprk33_adaptive_hold: need nchunks >= 0, 1 <= hold <= %d and courant > 0", int(ADAPTIVE_HOLD_MAX));
+    Range r_("lh:step_ssprk33_adaptive_hold");
+    int rc = validate_model(c);
+    if (rc) return rc;
+    const uint32_t pm = prognostic_mask(c->cfg.model);
+    if ((rc = check_state(c, Y, pm, "Y"))) return rc;
+    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
+    (void)hipSetDevice(c->device);
+    if (nchunks == 0) return LH_OK;
+    if (!c->scratch_k1 && (rc = state_alloc(c, pm, &c->scratch_k1))) return rc;
+    lh_state* K1 = c->scratch_k1; // the tendency the bound's launch writes with it: not used
+    void* bound = c->d_dt;        // the bound of the current Y; dt_device_ft keeps the step of the chunk
+    // f(Y) and the step bound of Y in one launch (rhs_kernel MODE 4)
+    auto bound_of_Y = [&]() {
+        return with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, Y, Ya, nullptr, K1, courant, 4, nullptr, nullptr, bound); });
+    };
+    // the global minimum with a communicator; then the overrun check of the chunk that ended, the next dt, elapsed
+    auto prepare = [&](int steps, bool check) -> int {
+        if (int r = allreduce_min(c, bound)) return r;
+        with_ft(c, [&](auto ft) {
+            using FT = decltype(ft);
+            launch_dt_hold_prepare<FT>(static_cast<FT*>(dt_device_ft), static_cast<const FT*>(bound), FT(dt_max),
+                                       static_cast<FT*>(elapsed_device_ft), steps, check, c->d_status, c->stream);
+        });
+        return LH_OK;
+    };
+    if (adaptive_hold_in_stepper(c, hold)) {
+        // the first bound from the tendency launch; every chunk's stepper launch leaves the next
+        if ((rc = bound_of_Y())) return rc;
+        for (int64_t k = 0; k < nchunks; ++k) {
+            if ((rc = prepare(hold, k > 0))) return rc;
+            if ((rc = run_column_stepper(c, Y, Ya, courant, dt_device_ft, hold, nullptr, bound))) return rc;
+        }
+    } else {
+        if (!c->scratch_u1 && (rc = state_alloc(c, pm & ~LH_MASK(LH_VAR_THETA_I), &c->scratch_u1))) return rc;
+        lh_state* U1 = c->scratch_u1;
+        lh_state* U2 = U1;
+        if ((rc = second_stage_state(c, &U2))) return rc;
+        for (int64_t k = 0; k < nchunks; ++k) {
+            if ((rc = bound_of_Y()) || (rc = prepare(hold, k > 0))) return rc;
+            for (int32_t s = 0; s < hold; ++s)
+                for (int stage = 0; stage < 3; ++stage) { // (as lh_step_ssprk33_device_dt)
+                    const lh_state* in = stage == 0 ? Y : (stage == 1 ? U1 : U2);
+                    lh_state* out = stage == 2 ? Y : (stage == 1 ? U2 : U1);
+                    rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, in, Ya, Y, out, 0.0, stage + 1, nullptr, dt_device_ft); });
+                    if (rc) return rc;
+                }
+        }
+        if ((rc = bound_of_Y())) return rc; // the bound of the state the last chunk ended on
+    }
+    if ((rc = prepare(0, true))) return rc;
     LH_HIP(c, hipGetLastError());
     return LH_OK;
 }

@@ -1024,7 +1024,12 @@ constexpr int cs_wave_min_waves() {
     if (CW == 1) return 6; // (the ice-free kernel needs 61 of its own accord; held to 64 it runs 4 % slower)
     return (NOICE && !FACTORS) ? 6 : 4;
 }
-template <typename FT, int MODEL, bool FACTORS, bool PERCOL, typename M, int CW, bool NOICE = false, bool VGF = true>
+// BOUND: the call also leaves the stable-step bound of the state it ENDS on in P.dt_out (which the launcher
+// has set to +inf), by rhs_kernel MODE 4's rule and with its expressions: one more closure pass over the
+// final state, the wave's integer maxima of the face terms, one division and one atomicMin per column.
+// dt_device then carries the step and dt_value the Courant factor (as in MODE 4).  The maxima are exact and
+// x -> fl(c / x) is monotone, so the word ends up with the bits a MODE 4 launch on the same state leaves.
+template <typename FT, int MODEL, bool FACTORS, bool PERCOL, typename M, int CW, bool NOICE = false, bool VGF = true, bool BOUND = false>
 __global__ void __launch_bounds__(1024, (cs_wave_min_waves<FT, MODEL, FACTORS, PERCOL, M, CW, NOICE>()))
 column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Planes<FT> AUX, const FT dt_value,
                            const FT* __restrict__ dt_device, const int64_t nsteps, const FT* __restrict__ bcv) {
@@ -1273,6 +1278,95 @@ column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Pla
         for (int q = 0; q < CW; ++q) {
             y_vl[q] = u_vl[q];
             y_re[q] = u_re[q];
+        }
+    }
+    if constexpr (BOUND) {
+        // The step came from *dt_device (a BOUND launch always has one), which leaves the scalar argument
+        // free: it carries the Courant factor, exactly as rhs_kernel MODE 4 takes it.  Named here so that
+        // nothing below reads `dt_value` as a step.
+        const FT courant = dt_value;
+        // (every neighbour has read the last stage's LDS values: the wave_sync that ends a stage)
+        FT K[CW], kap[CW], T[CW];
+        float dpsi[CW], ircs[CW];
+#pragma unroll
+        for (int q = 0; q < CW; ++q) {
+            FT rcs = FT(1), psi = FT(0);
+            T[q] = Ta[q];
+            kap[q] = K[q] = FT(0);
+            dpsi[q] = ircs[q] = 0.0f;
+            if (HEAT) {
+                T[q] = temperature_closure<FT, M, NOICE>(mm, P, c, y_vl[q], ti[q], y_re[q], rcs);
+                kap[q] = kappa_closure<FT, M, NOICE>(mm, P, c, y_vl[q], ti[q]);
+                ircs[q] = float(mm.rcp(rcs));
+            }
+            if (WATER) water_closures<FT, M, FACTORS, true, true, NOICE, RELK, HEAT, true>(mm, P, c, y_vl[q], ti[q], T[q], K[q], psi, &dpsi[q], vgf);
+        }
+        // the lane's top cell, for the lane above (a float passes through an FT word unchanged)
+        if (WATER) { sK[l] = K[CW - 1]; sh[l] = FT(dpsi[CW - 1]); }
+        if (HEAT) { sKap[l] = kap[CW - 1]; sT[l] = FT(ircs[CW - 1]); }
+        wave_sync();
+        float DmaxW = 0.0f, DmaxWb = 0.0f, DmaxT = 0.0f; // as rhs_kernel MODE 4 names them
+#pragma unroll
+        for (int q = 0; q < CW; ++q) { // the interior face below cell q
+            const int i = CW * l + q;
+            if (i > 0 && i < n) {
+                FT K_p = FT(0), kap_p = FT(0);
+                float dpsi_p = 0.0f, ircs_p = 0.0f;
+                if (q > 0) { // the cell below is the lane's own (q is a constant of the unrolled loop)
+                    K_p = K[q - 1]; kap_p = kap[q - 1]; dpsi_p = dpsi[q - 1]; ircs_p = ircs[q - 1];
+                } else {
+                    if (WATER) { K_p = sK[l - 1]; dpsi_p = float(sh[l - 1]); }
+                    if (HEAT) { kap_p = sKap[l - 1]; ircs_p = float(sT[l - 1]); }
+                }
+                if (WATER) DmaxW = max_nonneg(DmaxW, float(K_p + K[q]) * max_nonneg(dpsi_p, dpsi[q]));
+                if (HEAT) DmaxT = max_nonneg(DmaxT, float(kap_p + kap[q]) * max_nonneg(ircs_p, ircs[q]));
+            }
+        }
+        // the boundary cells' own coefficients; Dirichlet faces: half a cell away, face-state coefficients
+        auto boundary_terms = [&](int face, bool hoisted, int q_cell) {
+            FT bv = y_vl[0], bti = ti[0], bT = T[0], bK = K[0], bkap = kap[0];
+            float bdpsi = dpsi[0], bircs = ircs[0];
+#pragma unroll
+            for (int q = 1; q < CW; ++q)
+                if (q == q_cell) { bv = y_vl[q]; bti = ti[q]; bT = T[q]; bK = K[q]; bkap = kap[q]; bdpsi = dpsi[q]; bircs = ircs[q]; }
+            FT K_f, kap_f;
+            if (hoisted) {
+                const FT* src = sFace + (face == FACE_BOTTOM ? 0 : 3);
+                K_f = src[0];
+                kap_f = src[2];
+            } else {
+                const FaceState<FT> fs = face_state<FT, M, MODEL, FACTORS, NOICE>(mm, P, c, face, col, bv, bti, bT, vgf);
+                K_f = fs.K;
+                kap_f = fs.kap;
+            }
+            const FT K_c = bK * Ksc; // the true conductivity of the boundary cell
+            DmaxW = max_nonneg(DmaxW, 2.0f * float(bK) * bdpsi);
+            DmaxWb = max_nonneg(DmaxWb, 4.0f * float(fmax_ft(K_f, K_f > FT(0) ? K_c : FT(0))) * bdpsi);
+            if (HEAT) {
+                DmaxT = max_nonneg(DmaxT, 2.0f * float(bkap) * bircs);
+                DmaxT = max_nonneg(DmaxT, 4.0f * float(fmax_ft(kap_f, kap_f > FT(0) ? bkap : FT(0))) * bircs);
+            }
+        };
+        if (at_bottom || at_top) boundary_terms(at_bottom ? FACE_BOTTOM : FACE_TOP, at_bottom ? hoist_b : hoist_t, at_bottom ? 0 : qt);
+        if (at_bottom && at_top) boundary_terms(FACE_TOP, hoist_t, qt); // a column of <= CW cells
+        // wave maxima (every lane of the wave is here: the kernel has no early exit)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            DmaxW = max_nonneg(DmaxW, __shfl_xor(DmaxW, off, 64));
+            DmaxWb = max_nonneg(DmaxWb, __shfl_xor(DmaxWb, off, 64));
+            if (HEAT) DmaxT = max_nonneg(DmaxT, __shfl_xor(DmaxT, off, 64));
+        }
+        if (l == 0 && col_raw < P.ncols) { // (a column whose maximum is NaN is dropped, as in MODE 4)
+            const float Dj = max_nonneg(max_nonneg(DmaxW * float(Ksc), DmaxWb) * float(FT(1) / (c.n * c.m)), DmaxT);
+            const float dmax = Dj == Dj ? max_nonneg(0.0f, Dj) : 0.0f;
+            if (dmax > 0.0f) {
+                using U = typename Bits<FT>::type;
+                const FT best = (FT(2) * courant * P.dz * P.dz) / FT(dmax); // dmax = twice the diffusivity
+                U b;
+                __builtin_memcpy(&b, &best, sizeof(FT));
+                U* word = reinterpret_cast<U*>(P.dt_out);
+                if (b < __atomic_load_n(word, __ATOMIC_RELAXED)) atomicMin(word, b);
+            }
         }
     }
     __syncthreads(); // the tiles overlay other columns' exchange arrays
@@ -1594,15 +1688,37 @@ __global__ void __launch_bounds__(256) convert_kernel(FT* dst, const double* src
 // positive finite number (no positive diffusivity anywhere and no cap: +inf; a NaN) would turn the
 // state into NaNs: the step is then taken with dt = 0 (the state stays) and bit 2 of the status is set.
 template <typename FT>
-__global__ void dt_prepare_kernel(FT* dt, FT dt_max, FT* elapsed, uint32_t* status) {
-    FT d = *dt;
+__device__ __forceinline__ FT dt_from_bound(FT d, FT dt_max, uint32_t* status) {
     if (dt_max > FT(0) && !(d <= dt_max)) d = dt_max;
     if (!(d > FT(0)) || d - d != FT(0)) {
         d = FT(0);
         atomicOr(status, 4u);
     }
+    return d;
+}
+template <typename FT>
+__global__ void dt_prepare_kernel(FT* dt, FT dt_max, FT* elapsed, uint32_t* status) {
+    const FT d = dt_from_bound(*dt, dt_max, status);
     *dt = d;
     if (elapsed) *elapsed += d;
+}
+// lh_step_ssprk33_adaptive_hold, one thread between two chunks of `hold` steps.  *bound: the
+// (rank-reduced) stable-step bound of the current state.  check: a chunk has just ended on that state
+// with the step still in *dt -- a bound below that step, or one that is not a positive finite number,
+// sets bit 5 of the status (the held step exceeded the stable step of the state it produced).
+// hold > 0: *dt = the next chunk's step (dt_prepare_kernel's rule), elapsed += dt, `hold` times.
+template <typename FT>
+__global__ void dt_hold_prepare_kernel(FT* dt, const FT* bound, FT dt_max, FT* elapsed, int hold, int check, uint32_t* status) {
+    const FT b = *bound;
+    if (check && (!(b > FT(0)) || b - b != FT(0) || b < *dt)) atomicOr(status, 32u);
+    if (hold <= 0) return;
+    const FT d = dt_from_bound(b, dt_max, status);
+    *dt = d;
+    if (elapsed) {
+        FT e = *elapsed;
+        for (int k = 0; k < hold; ++k) e += d;
+        *elapsed = e;
+    }
 }
 
 template <typename FT>
@@ -1748,7 +1864,7 @@ unsigned wave_stepper_columns(int64_t ncols, size_t dyn_col, int64_t nsteps) {
 template <typename FT, int MODEL>
 void launch_column_stepper_for_model(const DevParams<FT>& P, const Planes<FT>& Y, const Planes<FT>& aux,
                                      FT dt, const FT* dt_dev, int64_t nsteps, const FT* bcv, bool factors,
-                                     bool percol, bool noice, hipStream_t s) {
+                                     bool percol, bool noice, bool bound, hipStream_t s) {
     // One wave per column with 1 or 2 adjacent cells per lane (column_stepper_wave_kernel) for columns
     // of up to 128 levels; one thread per cell with workgroup barriers beyond that.
     const int cw = (P.nlev + 63) / 64;
@@ -1771,27 +1887,32 @@ void launch_column_stepper_for_model(const DevParams<FT>& P, const Planes<FT>& Y
     const bool robust = robust_vg_exists<M, MODEL>() && P.vg_fast_all == 0; // (as launch_rhs_model)
     with_bool(factors, [&](auto f) { with_bool(percol, [&](auto pc) { with_bool(ni, [&](auto i) { with_bool(!robust, [&](auto vg) {
         // cells per lane of the wave kernel; 0: the thread-per-cell kernel
-        with_int(int_list<1, 2, 0>{}, wave ? cw : 0, [&](auto w) {
+        // (bound: the wave kernel only -- the caller asks for it for columns of up to 128 levels, with the
+        // step in device memory, the Courant factor in `dt` and P.dt_out addressing the word for the bound)
+        with_int(int_list<1, 2, 0>{}, wave ? cw : 0, [&](auto w) { with_bool(bound && wave, [&](auto bd) {
             constexpr bool F = decltype(f)::value, PC = decltype(pc)::value, NI = decltype(i)::value, VG = decltype(vg)::value;
             constexpr int CW = decltype(w)::value;
+            constexpr bool B = decltype(bd)::value;
             // (ni and robust are normalised with the same rules: the guard only keeps what cannot occur un-instantiated)
-            if constexpr ((!NI || noice_exists<M>(F)) && (VG || robust_vg_exists<M, MODEL>())) {
+            if constexpr ((!NI || noice_exists<M>(F)) && (VG || robust_vg_exists<M, MODEL>()) && (!B || CW > 0)) {
                 constexpr auto kernel = [] {
-                    if constexpr (CW > 0) return column_stepper_wave_kernel<FT, MODEL, F, PC, M, CW, NI, VG>;
+                    if constexpr (CW > 0) return column_stepper_wave_kernel<FT, MODEL, F, PC, M, CW, NI, VG, B>;
                     else return column_stepper_kernel<FT, MODEL, F, PC, M, NI, VG>;
                 }();
                 if constexpr (CW > 0) cpb = wave_stepper_columns<kernel>(P.ncols, dyn_col, nsteps);
                 if (P.cs_cpb > 0 && (unsigned)P.cs_cpb * tpc <= 1024u) cpb = (unsigned)P.cs_cpb;
                 const dim3 g((unsigned)((P.ncols + cpb - 1) / cpb)), b(tpc * cpb);
                 const unsigned dyn = (unsigned)(cpb * dyn_col);
+                if (B) // the minimum starts at +inf (as launch_rhs_mode does for MODE 4)
+                    hipLaunchKernelGGL((init_bits_kernel<FT>), dim3(1), dim3(1), 0, s, reinterpret_cast<typename Bits<FT>::type*>(P.dt_out));
                 hipLaunchKernelGGL(kernel, g, b, dyn, s, P, Y, aux, dt, dt_dev, nsteps, bcv);
             }
-        });
+        }); });
     }); }); }); });
 }
 
 #define LH_CS_MODEL_ARGS(FT) \
-    const DevParams<FT>&, const Planes<FT>&, const Planes<FT>&, FT, const FT*, int64_t, const FT*, bool, bool, bool, hipStream_t
+    const DevParams<FT>&, const Planes<FT>&, const Planes<FT>&, FT, const FT*, int64_t, const FT*, bool, bool, bool, bool, hipStream_t
 #define LH_RHS_MODEL_ARGS(FT)                                                                        \
     const DevParams<FT>&, const Planes<FT>&, const Planes<FT>&, const Planes<FT>&, const Planes<FT>&, \
         FT, const FT*, int, bool, bool, bool, int, const Tune&, hipStream_t
@@ -1825,9 +1946,9 @@ void launch_rhs(const DevParams<FT>& P, const Planes<FT>& in, const Planes<FT>& 
 template <typename FT>
 void launch_column_stepper(const DevParams<FT>& P, const Planes<FT>& Y, const Planes<FT>& aux, FT dt,
                            const FT* dt_dev, int64_t nsteps, const FT* bcv, bool factors, bool percol,
-                           bool noice, hipStream_t s) {
+                           bool noice, bool bound, hipStream_t s) {
     with_int(model_list{}, P.model, [&](auto m) {
-        launch_column_stepper_for_model<FT, decltype(m)::value>(P, Y, aux, dt, dt_dev, nsteps, bcv, factors, percol, noice, s);
+        launch_column_stepper_for_model<FT, decltype(m)::value>(P, Y, aux, dt, dt_dev, nsteps, bcv, factors, percol, noice, bound, s);
     });
 }
 
@@ -1891,6 +2012,11 @@ void launch_dt_prepare(FT* dt, FT dt_max, FT* elapsed, uint32_t* status, hipStre
 }
 
 template <typename FT>
+void launch_dt_hold_prepare(FT* dt, const FT* bound, FT dt_max, FT* elapsed, int hold, bool check, uint32_t* status, hipStream_t s) {
+    hipLaunchKernelGGL((dt_hold_prepare_kernel<FT>), dim3(1), dim3(1), 0, s, dt, bound, dt_max, elapsed, hold, check ? 1 : 0, status);
+}
+
+template <typename FT>
 void launch_fill(FT* p, int64_t n, FT v, hipStream_t s) {
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
@@ -1915,7 +2041,7 @@ void launch_convert(FT* dst, const double* src, int64_t n, hipStream_t s) {
                                  const Planes<FT>&, const Planes<FT>&, FT, const FT*, int, bool, bool, \
                                  bool, int, const Tune&, hipStream_t);                                                      \
     template void launch_column_stepper<FT>(const DevParams<FT>&, const Planes<FT>&, const Planes<FT>&, \
-                                            FT, const FT*, int64_t, const FT*, bool, bool, bool, hipStream_t); \
+                                            FT, const FT*, int64_t, const FT*, bool, bool, bool, bool, hipStream_t); \
     template void launch_diag<FT>(const DevParams<FT>&, const Planes<FT>&, const Planes<FT>&,         \
                                   const Planes<FT>&, bool, int, hipStream_t);                         \
     template void launch_stable_dt<FT>(const DevParams<FT>&, const Planes<FT>&, const Planes<FT>&,    \
@@ -1931,6 +2057,7 @@ void launch_convert(FT* dst, const double* src, int64_t n, hipStream_t s) {
     template void launch_fill<FT>(FT*, int64_t, FT, hipStream_t);                                     \
     template void launch_broadcast_profile<FT>(FT*, const FT*, int64_t, int64_t, int, hipStream_t);   \
     template void launch_dt_prepare<FT>(FT*, FT, FT*, uint32_t*, hipStream_t);                                   \
+    template void launch_dt_hold_prepare<FT>(FT*, const FT*, FT, FT*, int, bool, uint32_t*, hipStream_t);        \
     template void launch_convert<FT>(FT*, const double*, int64_t, hipStream_t);
 
 } // namespace lh

@@ -44,7 +44,7 @@ void launch_rhs(const DevParams<FT>& P, const Planes<FT>& in, const Planes<FT>& 
 template <typename FT>
 void launch_column_stepper(const DevParams<FT>& P, const Planes<FT>& Y, const Planes<FT>& aux, FT dt,
                            const FT* dt_dev, int64_t nsteps, const FT* bcv, bool factors, bool percol,
-                           bool noice, hipStream_t s);
+                           bool noice, bool bound, hipStream_t s);
 template <typename FT>
 void launch_diag(const DevParams<FT>& P, const Planes<FT>& in, const Planes<FT>& aux,
                  const Planes<FT>& out, bool percol, int math, hipStream_t s);
@@ -74,6 +74,10 @@ void launch_broadcast_profile(FT* plane, const FT* prof, int64_t ncols, int64_t 
 // one thread: dt = min(dt, dt_max), elapsed += dt (lh_step_ssprk33_adaptive)
 template <typename FT>
 void launch_dt_prepare(FT* dt, FT dt_max, FT* elapsed, uint32_t* status, hipStream_t s);
+// one thread between two chunks of lh_step_ssprk33_adaptive_hold: the overrun check of the chunk that
+// ended (check), the next chunk's dt from *bound and elapsed += dt, hold times (hold > 0)
+template <typename FT>
+void launch_dt_hold_prepare(FT* dt, const FT* bound, FT dt_max, FT* elapsed, int hold, bool check, uint32_t* status, hipStream_t s);
 // nsteps backward-Euler steps of a Richards model in one launch (lh_implicit.hpp)
 template <typename FT>
 void launch_implicit_euler(const DevParams<FT>& P, const ImplicitArgs<FT>& A, bool percol, bool noice, int math,

@@ -429,6 +429,32 @@ function step_ssprk33_adaptive!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, cour
 end
 
 """
+    step_ssprk33_adaptive_hold!(ens, Y, Ya, t, courant, nchunks, hold, dt_dev; dt_max = 0.0, elapsed_dev = C_NULL)
+
+`nchunks` chunks of `hold` SSPRK33 steps, the step size formed once per chunk from the stable-step
+bound of `Y` and held over it (lh_step_ssprk33_adaptive_hold): one launch of the persistent column
+stepper and one collective per chunk where the stepper serves the call (`adaptive_hold_engine`).
+Bitwise `step_ssprk33_adaptive!` on a copy for the chunk's dt and `hold` x `step_ssprk33_device_dt!`.
+Status bit 5: a held step exceeded the stable step of the state it produced.
+"""
+function step_ssprk33_adaptive_hold!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, courant, nchunks, hold,
+                                     dt_dev::Ptr{Cvoid}; dt_max = 0.0, elapsed_dev::Ptr{Cvoid} = C_NULL)
+    set_bcs!(ens, t)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    check(ens.ctx, ccall((:lh_step_ssprk33_adaptive_hold, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                         ens.ctx, Y.handle, ya, t, courant, dt_max, Int64(nchunks), Int32(hold), dt_dev, elapsed_dev))
+    return Y
+end
+
+"`:column_stepper` or `:fused_stages`: the engine the chunks of `step_ssprk33_adaptive_hold!` run with"
+function adaptive_hold_engine(ens::ColumnEnsemble, hold::Integer)
+    e = ccall((:lh_adaptive_hold_engine, lib), Cint, (Ptr{Cvoid}, Int32), ens.ctx, Int32(hold))
+    e < 0 && check(ens.ctx, e)
+    return e == 1 ? :column_stepper : :fused_stages
+end
+
+"""
     step_implicit_euler!(ens, Y, Ya, t, dt, nsteps; bcv = nothing, tol = 0.0, max_iter = 0) -> (max_iters, unconverged, iterations)
 
 `nsteps` backward-Euler steps of a Richards ensemble (lh_step_implicit_euler): per step Newton on

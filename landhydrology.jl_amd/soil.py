@@ -874,7 +874,7 @@ def stable_dt(model: SoilModel, Y: "FieldVector", Ya=None, courant: float = 0.5)
 
 
 def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, courant: float = 0.5,
-                  nsteps: int = 1, dt_max: float = 0.0, profiles_constant: bool = False):
+                  nsteps: int = 1, dt_max: float = 0.0, profiles_constant: bool = False, hold: int = 1):
     """Build extension: `nsteps` adaptive SSPRK33 steps of `Y` with nothing leaving the device
     (lh_step_ssprk33_adaptive: per step the tendency and the stable-step bound in one launch, the
     min over ranks when a communicator is attached, stages 2 and 3 -- three evaluations of the
@@ -883,7 +883,13 @@ def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, c
     The stage times of an adaptive step are not known in advance, so prescribed profiles the device
     reads (T with a viscosity factor, the water fields of a heat-only model) cannot be probed for
     time dependence: the caller states `profiles_constant=True` (they are then taken at time `t`).
+    `hold` > 1 (lh_step_ssprk33_adaptive_hold): the step size is formed once per CHUNK of `hold` steps
+    and held over it -- `nsteps` then counts chunks, the call takes `nsteps * hold` steps, with one
+    stepper launch (and one collective) per chunk where the persistent column stepper serves it.  Bit
+    5 of the status reports a held step that exceeded the stable step of the state it produced.
     Returns (simulated time advanced, last dt)."""
+    if int(hold) < 1:
+        raise ValueError("step_adaptive: hold must be >= 1")
     if _time_dependent(model):
         raise ValueError("step_adaptive needs boundary values that do not depend on time")
     if _device_reads_aux(model, Ya):
@@ -903,9 +909,13 @@ def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, c
     dev = torch.device("cuda", be.device_index())
     buf = torch.zeros(2, device=dev, dtype=dtype)
     torch.cuda.synchronize(dev)
-    F.check(L.lh_step_ssprk33_adaptive(be.ctx, Y.handle, ya, float(t), float(courant), float(dt_max), int(nsteps),
-                                       C.c_void_p(buf.data_ptr()),
-                                       C.c_void_p(buf.data_ptr() + buf.element_size())), be.ctx)
+    dt_ptr, elapsed_ptr = C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + buf.element_size())
+    if int(hold) == 1:
+        F.check(L.lh_step_ssprk33_adaptive(be.ctx, Y.handle, ya, float(t), float(courant), float(dt_max), int(nsteps),
+                                           dt_ptr, elapsed_ptr), be.ctx)
+    else:
+        F.check(L.lh_step_ssprk33_adaptive_hold(be.ctx, Y.handle, ya, float(t), float(courant), float(dt_max),
+                                                int(nsteps), int(hold), dt_ptr, elapsed_ptr), be.ctx)
     F.check(L.lh_synchronize(be.ctx), be.ctx)
     dt, elapsed = (float(x) for x in buf.cpu())
     return elapsed, dt
