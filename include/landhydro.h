@@ -445,6 +445,28 @@ int lh_integrate_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, dou
 #define LH_TRBDF2_NSTATS 7
 int lh_trbdf2_stats(lh_ctx*, int64_t* stats);
 
+/* Implicit steps of the heat-only model, SoilEnergyModel + PrescribedHydrologyModel
+ * (right_hand_side.jl:192-263).  With vartheta_l and theta_i prescribed the
+ * tendency is affine in rhoe_int, so a stage Y - w - c f(Y) = 0 is one tridiagonal solve, exact up to
+ * round-off: no Newton iteration, no tolerance, no convergence flag.  The matrix is factored once
+ * per call; a step is one forward and one back substitution (flags 0: backward Euler,
+ * Y - Yn - dt f(Y, t+dt) = 0) or two of each (LH_HEAT_TRBDF2: fixed-step TR-BDF2, second order and
+ * L-stable, gamma = 2 - sqrt 2, the stages at t + gamma dt and t + dt).  Fixed step: no error control.
+ * (Build-defined: the reference hands any OrdinaryDiffEq method to DiffEqBase.init,
+ * src/Simulations/simulation.jl:34-73.)
+ * bcv: NULL (lh_set_bc's values, per-column arrays included) or (nsteps + 1) * 4 doubles
+ * [nsteps + 1][2 faces][2 components] at t + k dt, k = 0 .. nsteps; the hydrology entries are
+ * ignored.  Backward Euler takes sample k + 1 for step k; TR-BDF2 takes (1 - gamma) v_k + gamma v_k+1
+ * for its first stage, v_k+1 for its second and v_k for the tendency at the start of the step.
+ * The prescribed vartheta_l and theta_i of Ya are read once per call and held through it.
+ * A non-finite result sets status bit 0.  LH_EMODEL for any model but LH_MODEL_HEAT; LH_EINVAL for
+ * dt <= 0 or not finite, nsteps < 0 or unknown flag bits; nsteps == 0 does nothing.  Asynchronous.
+ * (With a non-NULL bcv the call waits for its launch before it releases the device copy of the
+ * values, as lh_step_implicit_euler does.) */
+#define LH_HEAT_TRBDF2 1u
+int lh_step_heat_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
+                          int64_t nsteps, uint32_t flags, const double* bcv);
+
 /* Build-defined stable step (the reference uses a fixed user dt):
  * courant*dz^2 / max over owned faces of the face diffusivities
  * ((K_lo+K_hi)/2 * max dpsi/dvl, (kappa_lo+kappa_hi)/2 / min rho_c_s; boundary

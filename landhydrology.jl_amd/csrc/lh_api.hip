@@ -104,6 +104,7 @@ struct lh_ctx {
     void* d_imp_stats = nullptr;       // ... and its statistics: int32 max iterations, uint64 unconverged, uint64 iterations
     void* d_tr = nullptr;              // lh_integrate_trbdf2: six FT planes [nlev][stride] (Y_n, f_n, Y_gamma, w, c', d')
     void* d_tr_stats = nullptr;        // ... and its LH_TRBDF2_NSTATS uint64 counters
+    void* d_heat = nullptr;            // lh_step_heat_implicit: eight FT planes [nlev][stride] (three of the factorisation, kc, z; kappa sums, alpha, beta)
     void* d_tr_f = nullptr;            // ... two more planes when the error solve reuses stage 2's factorisation
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
@@ -1119,6 +1120,7 @@ int lh_destroy(lh_ctx* c) {
     if (c->d_tr) (void)hipFree(c->d_tr);
     if (c->d_tr_stats) (void)hipFree(c->d_tr_stats);
     if (c->d_tr_f) (void)hipFree(c->d_tr_f);
+    if (c->d_heat) (void)hipFree(c->d_heat);
     for (int k = 0; k < 3; ++k)
         if (c->d_atm_pc[k]) (void)hipFree(c->d_atm_pc[k]);
     for (int k = 0; k < 2; ++k)
@@ -1989,6 +1991,55 @@ int lh_trbdf2_stats(lh_ctx* c, int64_t* stats) {
     const int rc = read_stats(c, c->d_tr_stats, u, sizeof u, "c->d_tr_stats");
     for (int k = 0; k < LH_TRBDF2_NSTATS; ++k) stats[k] = int64_t(u[k]);
     return rc;
+}
+
+int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                          uint32_t flags, const double* bcv) {
+    (void)t; // boundary values come through bcv or lh_set_bc, as for lh_step_implicit_euler
+    if (!c) return LH_EINVAL;
+    if (nsteps < 0 || !std::isfinite(dt) || !(dt > 0))
+        return fail(c, LH_EINVAL, "lh_step_heat_implicit: need nsteps >= 0 and a finite dt > 0");
+    if (flags & ~LH_HEAT_TRBDF2) return fail(c, LH_EINVAL, "lh_step_heat_implicit: unknown flags 0x%x", flags);
+    Range r_("lh:step_heat_implicit");
+    if (c->cfg.model != LH_MODEL_HEAT)
+        return fail(c, LH_EMODEL, "lh_step_heat_implicit: heat-only models (SoilEnergyModel + PrescribedHydrologyModel)");
+    int rc = validate_model(c);
+    if (rc) return rc;
+    if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
+    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
+    if (nsteps == 0) return LH_OK;
+    (void)hipSetDevice(c->device);
+    const bool trbdf2 = (flags & LH_HEAT_TRBDF2) != 0;
+    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+    if ((rc = ensure_scratch(c, &c->d_heat, 8 * pl * c->esize, "c->d_heat", "8 * plane"))) return rc;
+    // (level-uniform variables of Ya become planes: the prologue reads each cell once)
+    if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u))) return rc;
+    DeviceBuffer d_bcv; // [nsteps + 1][2][2] doubles -> FT on the device
+    if (bcv && (rc = upload_boundary_values(c, bcv, size_t(nsteps + 1) * 4, d_bcv))) return rc;
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        HeatImplicitArgs<FT> A;
+        A.y = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
+        A.vl = static_cast<const FT*>(Ya->plane[LH_VAR_VARTHETA_L]);
+        A.ti = static_cast<const FT*>(Ya->plane[LH_VAR_THETA_I]);
+        A.a = static_cast<FT*>(c->d_heat);
+        A.iden = A.a + pl;
+        A.cp = A.iden + pl;
+        A.kc = A.cp + pl;
+        A.z = A.kc + pl;
+        A.ks = A.z + pl;
+        A.al = A.ks + pl;
+        A.be = A.al + pl;
+        A.bcv = static_cast<const FT*>(d_bcv.p);
+        A.coef = FT(trbdf2 ? 0.5 * (2.0 - 1.4142135623730951) * dt : dt);
+        A.nsteps = nsteps;
+        launch_heat_implicit<FT>(P, A, any_percol(c), trbdf2, c->math, c->stream);
+    });
+    mark_written(Y, LH_MASK(LH_VAR_RHOE_INT));
+    const hipError_t e = launch_error(c, d_bcv);
+    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "heat implicit launch failed: %s", hipGetErrorString(e));
+    return LH_OK;
 }
 
 int lh_stable_dt_device(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double courant, void* d_out) {

@@ -139,6 +139,25 @@ struct ImplicitStats {
 };
 static_assert(sizeof(ImplicitStats) == 24, "one int32 (padded) and two 64-bit counters");
 
+// lh_step_heat_implicit's launch (lh_heat_implicit.hpp)
+template <typename FT>
+struct HeatImplicitArgs {
+    FT* y;               // rhoe_int plane of Y
+    const FT* vl;        // the prescribed vartheta_l and theta_i planes of Ya, read once per call
+    const FT* ti;
+    FT* a;               // scratch planes [nlev][stride]: the factorisation (G_i-1 / den_i-1, rho_c_s,i / den_i, G_i alpha_i+1 rho_c_s,i / den_i),
+    FT* iden;
+    FT* cp;
+    FT* kc;              // ... coef x the constant of the affine tendency (without the boundary faces' share),
+    FT* z;               // ... r' of a forward sweep, TR-BDF2's w2
+    FT* ks;              // (TR-BDF2) kappa_i + kappa_i+1, alpha_i = 1 / rho_c_s, beta_i = T(rhoe_int = 0): the tendency
+    FT* al;
+    FT* be;
+    const FT* bcv;       // [nsteps + 1][2 faces][2 components] boundary values at t + k dt, or nullptr
+    FT coef;             // dt (backward Euler) or (2 - sqrt 2)/2 dt (both TR-BDF2 stages)
+    int64_t nsteps;
+};
+
 // lh_integrate_trbdf2's launch (lh_implicit.hpp)
 template <typename FT>
 struct Trbdf2Args {

@@ -85,6 +85,10 @@ void launch_implicit_euler(const DevParams<FT>& P, const ImplicitArgs<FT>& A, bo
 // TR-BDF2 of a Richards model over [t0, t1], per-column step control, in one launch (lh_implicit.hpp)
 template <typename FT>
 void launch_trbdf2(const DevParams<FT>& P, const Trbdf2Args<FT>& A, bool percol, bool noice, int math, hipStream_t s);
+// nsteps backward-Euler or fixed-step TR-BDF2 steps of a heat-only model in one launch (lh_heat_implicit.hpp)
+template <typename FT>
+void launch_heat_implicit(const DevParams<FT>& P, const HeatImplicitArgs<FT>& A, bool percol, bool trbdf2, int math,
+                          hipStream_t s);
 template <typename FT>
 void launch_convert(FT* dst, const double* src, int64_t n, hipStream_t s);
 

@@ -509,6 +509,28 @@ function integrate_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, t1, dt; 
 end
 
 """
+    step_heat_implicit!(ens, Y, Ya, t, dt, nsteps; method = :euler, bcv = nothing)
+
+`nsteps` implicit steps of a heat-only ensemble, SoilEnergyModel + PrescribedHydrologyModel
+(lh_step_heat_implicit): the tendency is affine in `ρe_int`, so every stage is one exact tridiagonal
+solve with a matrix factored once per call.  `method`: `:euler` (backward Euler) or `:trbdf2`
+(fixed-step TR-BDF2).  `bcv`: `nothing` or `(nsteps + 1) * 4` boundary values at `t + k dt`
+([sample][face][component], the hydrology entries are ignored).  The prescribed `ϑ_l` and `θ_i` of `Ya`
+are held at their values through the call.
+"""
+function step_heat_implicit!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt, nsteps; method = :euler, bcv = nothing)
+    method in (:euler, :trbdf2) || throw(ArgumentError("method must be :euler or :trbdf2"))
+    set_bcs!(ens, t)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    flags = method === :trbdf2 ? UInt32(1) : UInt32(0)
+    check(ens.ctx, ccall((:lh_step_heat_implicit, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Int64, UInt32, Ptr{Float64}),
+                         ens.ctx, Y.handle, ya, t, dt, Int64(nsteps), flags, vals))
+    return Y
+end
+
+"""
     tune_placement!(ens, Y, Ya, dY = nothing; max_candidates = 0, move_input = true)
 
 Let the library place the state written by `rhs!` (`dY` given) or the SSPRK33 stage state

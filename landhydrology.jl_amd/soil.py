@@ -931,7 +931,8 @@ class SSPRK33:
 class ImplicitEuler:
     """OrdinaryDiffEq.ImplicitEuler marker: backward Euler with Newton and one tridiagonal solve per
     column and iteration (lh_step_implicit_euler).  Richards models without conductivity factors
-    and without a prescribed atmosphere.  tol / max_iter: None = the library's defaults."""
+    and without a prescribed atmosphere; a heat-only model steps implicitly under HeatImplicitEuler /
+    HeatTRBDF2 (lh_step_heat_implicit).  tol / max_iter: None = the library's defaults."""
 
     def __init__(self, tol=None, max_iter=None):
         self.tol = tol
@@ -950,6 +951,22 @@ class TRBDF2:
         self.abstol = abstol
         self.reltol = reltol
         self.adaptive = adaptive
+
+
+class HeatImplicitEuler:
+    """Backward Euler of a heat-only model, SoilEnergyModel + PrescribedHydrologyModel
+    (lh_step_heat_implicit): the tendency is affine in ρe_int, so a step is one exact tridiagonal solve
+    with a matrix factored once per library call -- no Newton, no tolerance.  Simulation runs one call
+    per saveat chunk (per run without saveat); the prescribed ϑ_l and θ_i are refreshed between calls and
+    held within one."""
+    method = "euler"
+
+
+class HeatTRBDF2:
+    """Fixed-step TR-BDF2 of a heat-only model (lh_step_heat_implicit with LH_HEAT_TRBDF2): second order,
+    L-stable, two exact tridiagonal solves per step of the Simulation's dt, no error control.  Calls and
+    prescribed profiles as HeatImplicitEuler."""
+    method = "trbdf2"
 
 
 def _check_implicit_scope(model, name="ImplicitEuler"):
@@ -980,6 +997,50 @@ def _implicit_bcv(model, be, t, dt, nsteps):
             if kind == F.LH_BC_DIRICHLET and np.ndim(v) == 0:
                 vals[k, f, c] = float(v)
     return np.ascontiguousarray(vals)
+
+
+def _check_heat_implicit_scope(model, name="HeatImplicitEuler"):
+    """NotImplementedError for what lh_step_heat_implicit refuses with LH_EMODEL."""
+    if not (isinstance(model.energy_model, SoilEnergyModel) and
+            isinstance(model.hydrology_model, PrescribedHydrologyModel)):
+        raise NotImplementedError(f"{name} is provided for heat-only models only "
+                                  "(SoilEnergyModel + PrescribedHydrologyModel)")
+
+
+def _heat_implicit_bcv(model, be, t, dt, nsteps):
+    """[nsteps + 1][2][2] boundary values at t + k dt, k = 0 .. nsteps, of every scalar Dirichlet closure
+    (None when nothing depends on time)."""
+    if not _time_dependent(model):
+        return None
+    vals = np.zeros((nsteps + 1, 2, 2))
+    for (f, c), (kind, v) in be.bc_values(model, t).items():
+        if np.ndim(v) == 0:
+            vals[:, f, c] = float(v)
+    for k in range(1, nsteps + 1):
+        for (f, c), (kind, v) in be.bc_values(model, t + k * dt).items():
+            if kind == F.LH_BC_DIRICHLET and np.ndim(v) == 0:
+                vals[k, f, c] = float(v)
+    return np.ascontiguousarray(vals)
+
+
+def step_implicit_heat(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
+                       nsteps: int = 1, method: str = "euler"):
+    """Build extension: `nsteps` implicit steps of the heat-only model in one library call
+    (lh_step_heat_implicit), method "euler" (backward Euler) or "trbdf2" (fixed-step TR-BDF2).  Every
+    stage is one exact tridiagonal solve; the matrix is factored once per call.  Time-dependent Dirichlet
+    energy closures are sampled at the nsteps + 1 step times t + k dt (per-column values at `t`).  The
+    prescribed ϑ_l and θ_i are those `Ya` holds: they are held at these values through the call."""
+    if method not in ("euler", "trbdf2"):
+        raise ValueError('step_implicit_heat: method must be "euler" or "trbdf2"')
+    _check_heat_implicit_scope(model, "step_implicit_heat")
+    be = model._backend()
+    ya = Ya.handle if isinstance(Ya, FieldVector) else None
+    bcv = _heat_implicit_bcv(model, be, t, dt, int(nsteps))
+    be.set_bcs(model, t)
+    F.check(F.lib().lh_step_heat_implicit(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
+                                          F.LH_HEAT_TRBDF2 if method == "trbdf2" else 0,
+                                          bcv.ctypes.data_as(C.POINTER(C.c_double)) if bcv is not None else None),
+            be.ctx)
 
 
 def step_implicit(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0, nsteps: int = 1,
@@ -1117,8 +1178,11 @@ class Simulation:
             _check_implicit_scope(model)
         elif isinstance(method, TRBDF2):
             _check_implicit_scope(model, "TRBDF2")
+        elif isinstance(method, (HeatImplicitEuler, HeatTRBDF2)):
+            _check_heat_implicit_scope(model, type(method).__name__)
         elif not isinstance(method, SSPRK33):
-            raise NotImplementedError("only SSPRK33, ImplicitEuler and TRBDF2 are provided on the device")
+            raise NotImplementedError("only SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler and HeatTRBDF2 are "
+                                      "provided on the device")
         self.method = method
         if Y_init is None:
             # simulation.jl:50 references an undefined variable here:
@@ -1214,6 +1278,15 @@ def _advance(sim: Simulation, nsteps: int):
             _advance_trbdf2(sim, it.tf if it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
                             else it.t0 + (it._nsteps_done + nsteps) * it.dt)
             it._nsteps_done += nsteps
+        return
+    if isinstance(getattr(sim, "method", None), (HeatImplicitEuler, HeatTRBDF2)):
+        if nsteps > 0:
+            if isinstance(it.p, FieldVector):   # the prescribed profiles of THIS time, held through the call
+                make_update_aux(model.energy_model)(it.p, it.t)
+                make_update_aux(model.hydrology_model)(it.p, it.t)
+            step_implicit_heat(model, it.u, it.p, it.t, it.dt, nsteps, sim.method.method)
+            it._nsteps_done += nsteps
+            it.t = it.t + nsteps * it.dt
         return
     be = model._backend()
     L = F.lib()
