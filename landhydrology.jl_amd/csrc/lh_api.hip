@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -777,6 +778,95 @@ int second_stage_state(lh_ctx* c, lh_state** U2) {
     }
     *U2 = c->scratch_u2;
     return LH_OK;
+}
+
+// ---- what the stepping entry points share on the host
+
+// The opening of every stepping call, after its own argument checks: the model, the two states, the device
+int stepping_preamble(lh_ctx* c, const lh_state* Y, const lh_state* Ya) {
+    int rc = validate_model(c);
+    if (rc) return rc;
+    if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
+    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
+    (void)hipSetDevice(c->device);
+    return LH_OK;
+}
+
+// The stage states of the fused SSPRK33 launches, allocated on first use.  The stage state carries no
+// theta_i plane: the fused stages read theta_i from Y.  U2 (may be NULL: not wanted, not allocated) is U1
+// itself unless the launch is level-segmented.
+int stage_states(lh_ctx* c, lh_state** U1, lh_state** U2) {
+    int rc;
+    if (!c->scratch_u1 && (rc = state_alloc(c, prognostic_mask(c->cfg.model) & ~LH_MASK(LH_VAR_THETA_I), &c->scratch_u1)))
+        return rc;
+    *U1 = c->scratch_u1;
+    if (!U2) return LH_OK;
+    *U2 = *U1;
+    return second_stage_state(c, U2);
+}
+
+// One SSPRK33 step as three fused-stage launches.  The step is `dt`, or the device word `dt_device` when
+// there is one; bc3: [3 stages][2][2] boundary values, or NULL.
+int fused_ssprk33_step(lh_ctx* c, lh_state* Y, const lh_state* Ya, lh_state* U1, lh_state* U2, double dt,
+                       const void* dt_device, const double* bc3) {
+    for (int stage = 0; stage < 3; ++stage) {
+        const double* ov = bc3 ? bc3 + stage * 4 : nullptr;
+        // stage 1: U1 = Y + dt f(Y); 2: U2 = (3Y + U1 + dt f(U1))/4; 3: Y = (Y + 2U2 + 2dt f(U2))/3
+        const lh_state* in = stage == 0 ? Y : (stage == 1 ? U1 : U2);
+        lh_state* out = stage == 2 ? Y : (stage == 1 ? U2 : U1);
+        int rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, in, Ya, Y, out, dt, stage + 1, ov, dt_device); });
+        if (rc) return rc;
+    }
+    return LH_OK;
+}
+
+// Small ensembles with constant boundary values: the launches themselves are the cost of a step (a few
+// microseconds of device work each), so a block of steps is captured once into a hipGraph and replayed.
+// Returns the steps replayed; anything that goes wrong with the capture leaves the rest to plain launches
+// (*rc: a launch refused while capturing, or a replay that failed part of the way).
+template <typename STEP>
+int64_t replay_step_graph(lh_ctx* c, int64_t nsteps, STEP one_step, int* rc) {
+    constexpr int GRAPH_STEPS = 16;
+    int64_t done = 0;
+    *rc = LH_OK;
+    if (c->tune.graph == 0 || segment_length(c) <= 0 || nsteps < 4 * GRAPH_STEPS) return 0;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    bool ok = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    if (ok) {
+        for (int k = 0; k < GRAPH_STEPS && !*rc; ++k) *rc = one_step(nullptr);
+        ok = hipStreamEndCapture(c->stream, &graph) == hipSuccess && graph && !*rc;
+        if (*rc) { // a launch was refused while capturing: nothing has run yet
+            if (graph) (void)hipGraphDestroy(graph);
+            (void)hipGetLastError();
+            return 0;
+        }
+    }
+    if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+    if (ok)
+        for (; done + GRAPH_STEPS <= nsteps; done += GRAPH_STEPS)
+            if (hipGraphLaunch(exec, c->stream) != hipSuccess) {
+                ok = false;
+                break;
+            }
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (!ok) {
+        const hipError_t e = hipGetLastError();
+        if (done > 0 && done < nsteps && e != hipSuccess)
+            *rc = fail(c, LH_ENODEVICE, "hipGraphLaunch failed after %lld steps: %s", (long long)done, hipGetErrorString(e));
+    }
+    return done;
+}
+
+// Names the successive `pl`-element planes of a scratch block, in the block's order
+template <typename FT>
+void carve_planes(void* block, size_t pl, std::initializer_list<FT**> names) {
+    FT* p = static_cast<FT*>(block);
+    for (FT** name : names) {
+        *name = p;
+        p += pl;
+    }
 }
 
 int upload_percol(lh_ctx* c, void** slot, const double* host) {
@@ -1562,66 +1652,16 @@ int lh_step_ssprk33(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double
     if (!c) return LH_EINVAL;
     if (nsteps < 0 || !(dt > 0)) return fail(c, LH_EINVAL, "lh_step_ssprk33: need nsteps >= 0 and dt > 0");
     Range r_("lh:step_ssprk33");
-    int rc = validate_model(c);
+    int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
-    const uint32_t pm = prognostic_mask(c->cfg.model);
-    if ((rc = check_state(c, Y, pm, "Y"))) return rc;
-    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
-    (void)hipSetDevice(c->device);
     // Default: all nsteps in ONE launch of the persistent column stepper (state in registers,
     // no plane traffic between stages or steps; column_stepper_kernel)
     if (use_column_stepper(c, nsteps, bcv != nullptr)) return run_column_stepper(c, Y, Ya, dt, nullptr, nsteps, bcv);
-    // the stage state carries no theta_i plane: the fused stages read theta_i from Y
-    if (!c->scratch_u1 && (rc = state_alloc(c, pm & ~LH_MASK(LH_VAR_THETA_I), &c->scratch_u1))) return rc;
-    lh_state* U1 = c->scratch_u1;
-    lh_state* U2 = U1;
-    if ((rc = second_stage_state(c, &U2))) return rc;
-    auto one_step = [&](const double* bc3) -> int {
-        for (int stage = 0; stage < 3; ++stage) {
-            const double* ov = bc3 ? bc3 + stage * 4 : nullptr;
-            // stage 1: U1 = Y + dt f(Y); 2: U2 = (3Y + U1 + dt f(U1))/4; 3: Y = (Y + 2U2 + 2dt f(U2))/3
-            // (U2 is U1 itself unless the launch is level-segmented)
-            const lh_state* in = stage == 0 ? Y : (stage == 1 ? U1 : U2);
-            lh_state* out = stage == 2 ? Y : (stage == 1 ? U2 : U1);
-            int r = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, in, Ya, Y, out, dt, stage + 1, ov); });
-            if (r) return r;
-        }
-        return LH_OK;
-    };
-    int64_t done = 0;
-    // Small ensembles with constant boundary values: the launches themselves are the cost of a
-    // step (a few microseconds of device work each), so a block of steps is captured once into
-    // a hipGraph and replayed.  Anything that goes wrong with the capture falls back to plain
-    // launches of whatever is left.
-    constexpr int GRAPH_STEPS = 16;
-    if (!bcv && c->tune.graph != 0 && segment_length(c) > 0 && nsteps >= 4 * GRAPH_STEPS) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        bool ok = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        if (ok) {
-            for (int k = 0; k < GRAPH_STEPS && !rc; ++k) rc = one_step(nullptr);
-            ok = hipStreamEndCapture(c->stream, &graph) == hipSuccess && graph && !rc;
-            if (rc) { // a launch was refused while capturing: nothing has run yet
-                if (graph) (void)hipGraphDestroy(graph);
-                (void)hipGetLastError();
-                return rc;
-            }
-        }
-        if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-        if (ok)
-            for (; done + GRAPH_STEPS <= nsteps; done += GRAPH_STEPS)
-                if (hipGraphLaunch(exec, c->stream) != hipSuccess) {
-                    ok = false;
-                    break;
-                }
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (!ok) {
-            const hipError_t e = hipGetLastError();
-            if (done > 0 && done < nsteps && e != hipSuccess)
-                return fail(c, LH_ENODEVICE, "hipGraphLaunch failed after %lld steps: %s", (long long)done, hipGetErrorString(e));
-        }
-    }
+    lh_state *U1, *U2;
+    if ((rc = stage_states(c, &U1, &U2))) return rc;
+    auto one_step = [&](const double* bc3) { return fused_ssprk33_step(c, Y, Ya, U1, U2, dt, nullptr, bc3); };
+    const int64_t done = bcv ? 0 : replay_step_graph(c, nsteps, one_step, &rc);
+    if (rc) return rc;
     for (int64_t s = done; s < nsteps; ++s)
         if ((rc = one_step(bcv ? bcv + s * 12 : nullptr))) return rc;
     return LH_OK;
@@ -1650,25 +1690,12 @@ int lh_step_ssprk33_device_dt(lh_ctx* c, lh_state* Y, const lh_state* Ya, double
                               const void* dt_device_ft, const double* bcv) {
     (void)t;
     if (!c || !dt_device_ft) return fail(c, LH_EINVAL, "lh_step_ssprk33_device_dt: NULL argument");
-    int rc = validate_model(c);
+    int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
-    const uint32_t pm = prognostic_mask(c->cfg.model);
-    if ((rc = check_state(c, Y, pm, "Y"))) return rc;
-    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
-    (void)hipSetDevice(c->device);
     if (use_column_stepper(c, 1, bcv != nullptr)) return run_column_stepper(c, Y, Ya, 0.0, dt_device_ft, 1, bcv);
-    if (!c->scratch_u1 && (rc = state_alloc(c, pm & ~LH_MASK(LH_VAR_THETA_I), &c->scratch_u1))) return rc;
-    lh_state* U1 = c->scratch_u1;
-    lh_state* U2 = U1;
-    if ((rc = second_stage_state(c, &U2))) return rc;
-    for (int stage = 0; stage < 3; ++stage) {
-        const double* ov = bcv ? bcv + stage * 4 : nullptr;
-        const lh_state* in = stage == 0 ? Y : (stage == 1 ? U1 : U2);
-        lh_state* out = stage == 2 ? Y : (stage == 1 ? U2 : U1);
-        rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, in, Ya, Y, out, 0.0, stage + 1, ov, dt_device_ft); });
-        if (rc) return rc;
-    }
-    return LH_OK;
+    lh_state *U1, *U2;
+    if ((rc = stage_states(c, &U1, &U2))) return rc;
+    return fused_ssprk33_step(c, Y, Ya, U1, U2, 0.0, dt_device_ft, bcv);
 }
 
 int lh_step_ssprk33_adaptive(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double courant, double dt_max,
@@ -1677,21 +1704,15 @@ int lh_step_ssprk33_adaptive(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
     if (!c || !dt_device_ft) return fail(c, LH_EINVAL, "lh_step_ssprk33_adaptive: NULL argument");
     if (nsteps < 0 || !(courant > 0)) return fail(c, LH_EINVAL, "lh_step_ssprk33_adaptive: need nsteps >= 0 and courant > 0");
     Range r_("lh:step_ssprk33_adaptive");
-    int rc = validate_model(c);
+    int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
-    const uint32_t pm = prognostic_mask(c->cfg.model);
-    if ((rc = check_state(c, Y, pm, "Y"))) return rc;
-    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
-    (void)hipSetDevice(c->device);
-    if (!c->scratch_k1 && (rc = state_alloc(c, pm, &c->scratch_k1))) return rc;
-    if (!c->scratch_u1 && (rc = state_alloc(c, pm & ~LH_MASK(LH_VAR_THETA_I), &c->scratch_u1))) return rc;
+    if (!c->scratch_k1 && (rc = state_alloc(c, prognostic_mask(c->cfg.model), &c->scratch_k1))) return rc;
     lh_state* K1 = c->scratch_k1;
-    lh_state* U1 = c->scratch_u1;
     // With a prescribed atmosphere the surface fluxes of a stage come from the stage state's top
     // cells, which MODE 5 never stores: that model takes the four-launch sequence.
     const bool three = !c->hp.atmos_on;
-    lh_state* U2 = U1;
-    if (!three && (rc = second_stage_state(c, &U2))) return rc;
+    lh_state *U1, *U2 = nullptr; // (the three-launch sequence has no second stage state)
+    if ((rc = stage_states(c, &U1, three ? nullptr : &U2))) return rc;
     for (int64_t s = 0; s < nsteps; ++s) {
         // f(Y) and the step bound of Y in one launch; the global minimum with a communicator
         rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, Y, Ya, nullptr, K1, courant, 4, nullptr, nullptr, dt_device_ft); });
@@ -1707,13 +1728,8 @@ int lh_step_ssprk33_adaptive(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
             if (rc) return rc;
             rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, U1, Ya, Y, Y, 0.0, 3, nullptr, dt_device_ft); });
             if (rc) return rc;
-        } else {
-            for (int stage = 0; stage < 3; ++stage) {
-                const lh_state* in = stage == 0 ? Y : (stage == 1 ? U1 : U2);
-                lh_state* out = stage == 2 ? Y : (stage == 1 ? U2 : U1);
-                rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, in, Ya, Y, out, 0.0, stage + 1, nullptr, dt_device_ft); });
-                if (rc) return rc;
-            }
+        } else if ((rc = fused_ssprk33_step(c, Y, Ya, U1, U2, 0.0, dt_device_ft, nullptr))) {
+            return rc;
         }
     }
     LH_HIP(c, hipGetLastError());
@@ -1741,14 +1757,10 @@ int lh_step_ssprk33_adaptive_hold(lh_ctx* c, lh_state* Y, const lh_state* Ya, do
     if (nchunks < 0 || hold < 1 || hold > ADAPTIVE_HOLD_MAX || !(courant > 0))
         return fail(c, LH_EINVAL, "lh_step_ssprk33_adaptive_hold: need nchunks >= 0, 1 <= hold <= %d and courant > 0", int(ADAPTIVE_HOLD_MAX));
     Range r_("lh:step_ssprk33_adaptive_hold");
-    int rc = validate_model(c);
+    int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
-    const uint32_t pm = prognostic_mask(c->cfg.model);
-    if ((rc = check_state(c, Y, pm, "Y"))) return rc;
-    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
-    (void)hipSetDevice(c->device);
     if (nchunks == 0) return LH_OK;
-    if (!c->scratch_k1 && (rc = state_alloc(c, pm, &c->scratch_k1))) return rc;
+    if (!c->scratch_k1 && (rc = state_alloc(c, prognostic_mask(c->cfg.model), &c->scratch_k1))) return rc;
     lh_state* K1 = c->scratch_k1; // the tendency the bound's launch writes with it: not used
     void* bound = c->d_dt;        // the bound of the current Y; dt_device_ft keeps the step of the chunk
     // f(Y) and the step bound of Y in one launch (rhs_kernel MODE 4)
@@ -1773,19 +1785,12 @@ int lh_step_ssprk33_adaptive_hold(lh_ctx* c, lh_state* Y, const lh_state* Ya, do
             if ((rc = run_column_stepper(c, Y, Ya, courant, dt_device_ft, hold, nullptr, bound))) return rc;
         }
     } else {
-        if (!c->scratch_u1 && (rc = state_alloc(c, pm & ~LH_MASK(LH_VAR_THETA_I), &c->scratch_u1))) return rc;
-        lh_state* U1 = c->scratch_u1;
-        lh_state* U2 = U1;
-        if ((rc = second_stage_state(c, &U2))) return rc;
+        lh_state *U1, *U2;
+        if ((rc = stage_states(c, &U1, &U2))) return rc;
         for (int64_t k = 0; k < nchunks; ++k) {
             if ((rc = bound_of_Y()) || (rc = prepare(hold, k > 0))) return rc;
             for (int32_t s = 0; s < hold; ++s)
-                for (int stage = 0; stage < 3; ++stage) { // (as lh_step_ssprk33_device_dt)
-                    const lh_state* in = stage == 0 ? Y : (stage == 1 ? U1 : U2);
-                    lh_state* out = stage == 2 ? Y : (stage == 1 ? U2 : U1);
-                    rc = with_ft(c, [&](auto ft) { return do_rhs<decltype(ft)>(c, in, Ya, Y, out, 0.0, stage + 1, nullptr, dt_device_ft); });
-                    if (rc) return rc;
-                }
+                if ((rc = fused_ssprk33_step(c, Y, Ya, U1, U2, 0.0, dt_device_ft, nullptr))) return rc;
         }
         if ((rc = bound_of_Y())) return rc; // the bound of the state the last chunk ended on
     }
@@ -1805,10 +1810,7 @@ static int implicit_refusals(lh_ctx* c, const char* who, const lh_state* Y, cons
     // (validate_model refuses a prescribed atmosphere on any model but the coupled one already; kept so
     // that this path stays closed to it should that change)
     if (c->hp.atmos_on) return fail(c, LH_EMODEL, "%s: a prescribed-atmosphere top is not supported", who);
-    int rc = validate_model(c);
-    if (rc) return rc;
-    if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
-    return check_state(c, Ya, aux_mask(c), "Ya");
+    return stepping_preamble(c, Y, Ya);
 }
 
 // The helpers below take the buffer's name and size as the entry points write them (`name`, `size`), so that a
@@ -1855,7 +1857,6 @@ int lh_step_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t,
     if (nsteps < 0 || !(dt > 0)) return fail(c, LH_EINVAL, "lh_step_implicit_euler: need nsteps >= 0 and dt > 0");
     Range r_("lh:step_implicit_euler");
     if ((rc = implicit_refusals(c, "lh_step_implicit_euler", Y, Ya))) return rc;
-    (void)hipSetDevice(c->device);
     if (!(tol > 0)) tol = c->cfg.dtype == LH_F64 ? 1e-10 : 1e-5;
     if (max_iter <= 0) max_iter = 50;
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
@@ -1872,9 +1873,7 @@ int lh_step_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t,
         ImplicitArgs<FT> A;
         A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
         A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
-        A.yn = static_cast<FT*>(c->d_imp);
-        A.cp = A.yn + pl;
-        A.dp = A.cp + pl;
+        carve_planes<FT>(c->d_imp, pl, {&A.yn, &A.cp, &A.dp});
         A.bcv = static_cast<const FT*>(d_bcv.p);
         A.dt = FT(dt);
         A.tol = FT(tol);
@@ -1932,7 +1931,6 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
             if (!std::isfinite(bcv[k])) return fail(c, LH_EINVAL, "lh_integrate_trbdf2: non-finite boundary value");
     Range r_("lh:integrate_trbdf2");
     if ((rc = implicit_refusals(c, "lh_integrate_trbdf2", Y, Ya))) return rc;
-    (void)hipSetDevice(c->device);
     const bool fixed = (flags & LH_TRBDF2_FIXED) != 0;
     // each tolerance that is 0 takes its own default (OrdinaryDiffEq's)
     if (!(abstol > 0)) abstol = LH_TRBDF2_ABSTOL_DEFAULT;
@@ -1954,12 +1952,7 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
         Trbdf2Args<FT> A;
         A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
         A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
-        A.yn = static_cast<FT*>(c->d_tr);
-        A.fn = A.yn + pl;
-        A.yg = A.fn + pl;
-        A.w = A.yg + pl;
-        A.cp = A.w + pl;
-        A.dp = A.cp + pl;
+        carve_planes<FT>(c->d_tr, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp});
         A.dt_cols = static_cast<FT*>(dt_cols_device_ft);
         A.t0 = t0;
         A.t1 = t1;
@@ -1974,8 +1967,8 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
         A.kappa = FT(c->tune.trk > 0 ? 1e-4 * c->tune.trk : LH_TRBDF2_NEWTON_KAPPA);
         A.newton_max = c->tune.trn > 0 ? c->tune.trn : LH_TRBDF2_NEWTON_MAX;
         A.reuse = reuse;
-        A.fa = reuse ? static_cast<FT*>(c->d_tr_f) : nullptr;
-        A.fden = reuse ? A.fa + pl : nullptr;
+        A.fa = A.fden = nullptr;
+        if (reuse) carve_planes<FT>(c->d_tr_f, pl, {&A.fa, &A.fden});
         A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
         launch_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
     });
@@ -2003,12 +1996,9 @@ int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, 
     Range r_("lh:step_heat_implicit");
     if (c->cfg.model != LH_MODEL_HEAT)
         return fail(c, LH_EMODEL, "lh_step_heat_implicit: heat-only models (SoilEnergyModel + PrescribedHydrologyModel)");
-    int rc = validate_model(c);
+    int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
-    if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
-    if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
     if (nsteps == 0) return LH_OK;
-    (void)hipSetDevice(c->device);
     const bool trbdf2 = (flags & LH_HEAT_TRBDF2) != 0;
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
     if ((rc = ensure_scratch(c, &c->d_heat, 8 * pl * c->esize, "c->d_heat", "8 * plane"))) return rc;
@@ -2023,14 +2013,7 @@ int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, 
         A.y = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
         A.vl = static_cast<const FT*>(Ya->plane[LH_VAR_VARTHETA_L]);
         A.ti = static_cast<const FT*>(Ya->plane[LH_VAR_THETA_I]);
-        A.a = static_cast<FT*>(c->d_heat);
-        A.iden = A.a + pl;
-        A.cp = A.iden + pl;
-        A.kc = A.cp + pl;
-        A.z = A.kc + pl;
-        A.ks = A.z + pl;
-        A.al = A.ks + pl;
-        A.be = A.al + pl;
+        carve_planes<FT>(c->d_heat, pl, {&A.a, &A.iden, &A.cp, &A.kc, &A.z, &A.ks, &A.al, &A.be});
         A.bcv = static_cast<const FT*>(d_bcv.p);
         A.coef = FT(trbdf2 ? 0.5 * (2.0 - 1.4142135623730951) * dt : dt);
         A.nsteps = nsteps;

@@ -427,6 +427,44 @@ class FieldVector:
 # -------------------------------------------------------------------- model
 
 
+def _bc_values(model, t):
+    """Evaluate the BC closures at time t -> {(face, comp): (kind, value)}."""
+    out = {}
+    for face, tag in ((F.LH_FACE_BOTTOM, "bottom"), (F.LH_FACE_TOP, "top")):
+        fbc = getattr(model.boundary_conditions, tag)
+        if isinstance(fbc, PrescribedAtmosForcing):      # set through lh_set_atmos_forcing
+            continue
+        for comp, cname in ((F.LH_COMP_ENERGY, "energy"), (F.LH_COMP_HYDROLOGY, "hydrology")):
+            bc = getattr(fbc, cname)
+            kind = _BC_KIND.get(type(bc))
+            if kind is None:
+                raise TypeError(f"unsupported boundary condition {type(bc).__name__}")
+            val = 0.0
+            if kind == F.LH_BC_FLUX:
+                val = bc.flux
+            elif kind == F.LH_BC_DIRICHLET:
+                val = bc.state_value(t)
+            out[(face, comp)] = (kind, val)
+    return out
+
+
+def _handle(Ya):
+    """The library's state of Ya, or None for a Ya that stays on the host."""
+    return Ya.handle if isinstance(Ya, FieldVector) else None
+
+
+def _dptr(a):
+    """double* of a contiguous float64 array, NULL for None."""
+    return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
+
+
+def _torch_ft_device(model):
+    """(torch dtype of the model's FT, torch device of the model's context)."""
+    import torch
+    ft = torch.float64 if np.dtype(model.domain.FT) == np.float64 else torch.float32
+    return ft, torch.device("cuda", model._backend().device_index())
+
+
 class _Backend:
     """One lh_ctx: the device-side image of a SoilModel."""
 
@@ -501,26 +539,6 @@ class _Backend:
                                             a.ctypes.data_as(C.POINTER(C.c_double))), self.ctx)
         return float(a[0])
 
-    def bc_values(self, model, t):
-        """Evaluate the BC closures at time t -> {(face, comp): (kind, value)}."""
-        out = {}
-        for face, tag in ((F.LH_FACE_BOTTOM, "bottom"), (F.LH_FACE_TOP, "top")):
-            fbc = getattr(model.boundary_conditions, tag)
-            if isinstance(fbc, PrescribedAtmosForcing):      # set through lh_set_atmos_forcing
-                continue
-            for comp, cname in ((F.LH_COMP_ENERGY, "energy"), (F.LH_COMP_HYDROLOGY, "hydrology")):
-                bc = getattr(fbc, cname)
-                kind = _BC_KIND.get(type(bc))
-                if kind is None:
-                    raise TypeError(f"unsupported boundary condition {type(bc).__name__}")
-                val = 0.0
-                if kind == F.LH_BC_FLUX:
-                    val = bc.flux
-                elif kind == F.LH_BC_DIRICHLET:
-                    val = bc.state_value(t)
-                out[(face, comp)] = (kind, val)
-        return out
-
     def set_atmos(self, model):
         """lh_set_atmos_forcing from SoilColumnBC.top (or its removal)."""
         L = F.lib()
@@ -561,7 +579,7 @@ class _Backend:
         L = F.lib()
         d = model.domain
         self.set_atmos(model)
-        for (face, comp), (kind, val) in self.bc_values(model, t).items():
+        for (face, comp), (kind, val) in _bc_values(model, t).items():
             a = np.asarray(val, dtype=np.float64)
             if a.ndim == 0:
                 F.check(L.lh_set_bc(self.ctx, face, comp, kind, float(a), None), self.ctx)
@@ -758,7 +776,7 @@ def tune_placement(model: SoilModel, Y: "FieldVector", Ya=None, dY: Optional["Fi
     SSPRK33 stage state (dY=None) lives -- lh_tune_placement.  Returns the launch
     time in ms before and after.  Results of later calls do not depend on it."""
     be = model._backend()
-    ya = Ya.handle if isinstance(Ya, FieldVector) else None
+    ya = _handle(Ya)
     be.set_bcs(model, 0.0)
     b, a = C.c_float(), C.c_float()
     F.check(F.lib().lh_tune_placement(be.ctx, Y.handle, ya, dY.handle if dY is not None else None,
@@ -788,7 +806,7 @@ def make_rhs(model: SoilModel):
             update_en(Ya, t)
             update_hy(Ya, t)
         be.set_bcs(model, t)
-        ya = Ya.handle if isinstance(Ya, FieldVector) else None
+        ya = _handle(Ya)
         if placed is not None and (id(Y), id(dY)) not in placed:
             placed.add((id(Y), id(dY)))
             F.check(L.lh_tune_placement(be.ctx, Y.handle, ya, dY.handle, 0, 0, None, None), be.ctx)
@@ -854,7 +872,7 @@ def boundary_fluxes(X, bc, face, model: SoilModel, cs=None, t=0.0):
     be.set_bcs(model, t)
     d = model.domain
     fe, fw = np.empty(d.ncolumns), np.empty(d.ncolumns)
-    ya = Ya.handle if isinstance(Ya, FieldVector) else None
+    ya = _handle(Ya)
     F.check(F.lib().lh_boundary_fluxes(be.ctx, Y.handle, ya, float(t), F.LH_FACE_TOP if tag == "top" else F.LH_FACE_BOTTOM,
                                        fe.ctypes.data_as(C.POINTER(C.c_double)), fw.ctypes.data_as(C.POINTER(C.c_double))),
             be.ctx)
@@ -868,7 +886,7 @@ def stable_dt(model: SoilModel, Y: "FieldVector", Ya=None, courant: float = 0.5)
     minimum with `partition.global_min_dt`."""
     be = model._backend()
     out = C.c_double()
-    ya = Ya.handle if isinstance(Ya, FieldVector) else None
+    ya = _handle(Ya)
     F.check(F.lib().lh_stable_dt(be.ctx, Y.handle, ya, float(courant), C.byref(out)), be.ctx)
     return out.value
 
@@ -900,13 +918,12 @@ def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, c
         make_update_aux(model.hydrology_model)(Ya, t)
     be = model._backend()
     L = F.lib()
-    ya = Ya.handle if isinstance(Ya, FieldVector) else None
+    ya = _handle(Ya)
     be.set_bcs(model, t)
     import torch
-    dtype = torch.float64 if np.dtype(model.domain.FT) == np.float64 else torch.float32
     # [dt, elapsed] on the CONTEXT's device; the zero fill runs on torch's stream, the library on its
     # own (non-blocking) one: the fill must have completed before the first `*elapsed += dt`
-    dev = torch.device("cuda", be.device_index())
+    dtype, dev = _torch_ft_device(model)
     buf = torch.zeros(2, device=dev, dtype=dtype)
     torch.cuda.synchronize(dev)
     dt_ptr, elapsed_ptr = C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + buf.element_size())
@@ -924,8 +941,19 @@ def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, c
 # --------------------------------------------------------------- Simulations
 
 
+# Each method marker states what it refuses (check_scope: NotImplementedError, as the library's LH_EMODEL)
+# and how a Simulation advances `nsteps` intervals of dt with it (advance: returns the time reached, None
+# for it.t + nsteps dt; _advance keeps the step count and the time).
+
+
 class SSPRK33:
     """OrdinaryDiffEq.SSPRK33 marker (the only stepper the reference's tests use)."""
+
+    def check_scope(self, model):
+        pass
+
+    def advance(self, sim, nsteps):
+        return _advance_ssprk33(sim, nsteps)
 
 
 class ImplicitEuler:
@@ -937,6 +965,13 @@ class ImplicitEuler:
     def __init__(self, tol=None, max_iter=None):
         self.tol = tol
         self.max_iter = max_iter
+
+    def check_scope(self, model):
+        _check_implicit_scope(model)
+
+    def advance(self, sim, nsteps):
+        it = sim.integrator
+        step_implicit(sim.model, it.u, it.p, it.t, it.dt, nsteps, self.tol, self.max_iter)
 
 
 class TRBDF2:
@@ -952,6 +987,15 @@ class TRBDF2:
         self.reltol = reltol
         self.adaptive = adaptive
 
+    def check_scope(self, model):
+        _check_implicit_scope(model, "TRBDF2")
+
+    def advance(self, sim, nsteps):
+        it = sim.integrator
+        # the end of a chunk of nsteps intervals of dt, as the fixed-step methods reach it; tf itself at the last
+        last = it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
+        return _advance_trbdf2(sim, it.tf if last else it.t0 + (it._nsteps_done + nsteps) * it.dt)
+
 
 class HeatImplicitEuler:
     """Backward Euler of a heat-only model, SoilEnergyModel + PrescribedHydrologyModel
@@ -961,8 +1005,18 @@ class HeatImplicitEuler:
     held within one."""
     method = "euler"
 
+    def check_scope(self, model):
+        _check_heat_implicit_scope(model, type(self).__name__)
 
-class HeatTRBDF2:
+    def advance(self, sim, nsteps):
+        it, model = sim.integrator, sim.model
+        if isinstance(it.p, FieldVector):   # the prescribed profiles of THIS time, held through the call
+            make_update_aux(model.energy_model)(it.p, it.t)
+            make_update_aux(model.hydrology_model)(it.p, it.t)
+        step_implicit_heat(model, it.u, it.p, it.t, it.dt, nsteps, self.method)
+
+
+class HeatTRBDF2(HeatImplicitEuler):
     """Fixed-step TR-BDF2 of a heat-only model (lh_step_heat_implicit with LH_HEAT_TRBDF2): second order,
     L-stable, two exact tridiagonal solves per step of the Simulation's dt, no error control.  Calls and
     prescribed profiles as HeatImplicitEuler."""
@@ -983,20 +1037,24 @@ def _check_implicit_scope(model, name="ImplicitEuler"):
         raise NotImplementedError(f"{name} does not support a prescribed-atmosphere top")
 
 
-def _implicit_bcv(model, be, t, dt, nsteps):
-    """[nsteps][2][2] boundary values at t_{n+1} = t + (k+1) dt of every scalar Dirichlet closure
-    (None when nothing depends on time)."""
+def _sampled_bcv(model, times, base_t):
+    """Boundary values of the scalar closures at `times` (any shape; the caller writes the times with its
+    own expression, so that the bits the library receives are the caller's): an array of shape
+    np.shape(times) + (2, 2), [..., face, component], or None when no boundary condition is a Dirichlet
+    closure (nothing depends on time).  Every entry first takes its scalar value at `base_t`; a scalar
+    Dirichlet value is then that of its own time.  A flux value is a constant of the model (`bc.flux`), so
+    sampling every kind at every time gives the same numbers.  Per-column values stay 0 here: they reach
+    the library through set_bcs."""
     if not _time_dependent(model):
         return None
-    vals = np.zeros((nsteps, 2, 2))
-    for (f, c), (kind, v) in be.bc_values(model, t).items():
-        if np.ndim(v) == 0:
-            vals[:, f, c] = float(v)
-    for k in range(nsteps):
-        for (f, c), (kind, v) in be.bc_values(model, t + (k + 1) * dt).items():
-            if kind == F.LH_BC_DIRICHLET and np.ndim(v) == 0:
-                vals[k, f, c] = float(v)
-    return np.ascontiguousarray(vals)
+    times = np.asarray(times)
+    vals = np.zeros(times.shape + (2, 2))
+    base = (Ellipsis,)   # the pass that fills every time with the values at base_t
+    for k, t in [(base, base_t)] + [(k, times[k]) for k in np.ndindex(times.shape)]:
+        for (f, c), (kind, v) in _bc_values(model, t).items():
+            if np.ndim(v) == 0 and (k is base or kind == F.LH_BC_DIRICHLET):
+                vals[k + (f, c)] = float(v)
+    return vals
 
 
 def _check_heat_implicit_scope(model, name="HeatImplicitEuler"):
@@ -1005,22 +1063,6 @@ def _check_heat_implicit_scope(model, name="HeatImplicitEuler"):
             isinstance(model.hydrology_model, PrescribedHydrologyModel)):
         raise NotImplementedError(f"{name} is provided for heat-only models only "
                                   "(SoilEnergyModel + PrescribedHydrologyModel)")
-
-
-def _heat_implicit_bcv(model, be, t, dt, nsteps):
-    """[nsteps + 1][2][2] boundary values at t + k dt, k = 0 .. nsteps, of every scalar Dirichlet closure
-    (None when nothing depends on time)."""
-    if not _time_dependent(model):
-        return None
-    vals = np.zeros((nsteps + 1, 2, 2))
-    for (f, c), (kind, v) in be.bc_values(model, t).items():
-        if np.ndim(v) == 0:
-            vals[:, f, c] = float(v)
-    for k in range(1, nsteps + 1):
-        for (f, c), (kind, v) in be.bc_values(model, t + k * dt).items():
-            if kind == F.LH_BC_DIRICHLET and np.ndim(v) == 0:
-                vals[k, f, c] = float(v)
-    return np.ascontiguousarray(vals)
 
 
 def step_implicit_heat(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
@@ -1034,13 +1076,12 @@ def step_implicit_heat(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0
         raise ValueError('step_implicit_heat: method must be "euler" or "trbdf2"')
     _check_heat_implicit_scope(model, "step_implicit_heat")
     be = model._backend()
-    ya = Ya.handle if isinstance(Ya, FieldVector) else None
-    bcv = _heat_implicit_bcv(model, be, t, dt, int(nsteps))
+    ya = _handle(Ya)
+    bcv = _sampled_bcv(model, [t + k * dt for k in range(int(nsteps) + 1)], t)
     be.set_bcs(model, t)
     F.check(F.lib().lh_step_heat_implicit(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
                                           F.LH_HEAT_TRBDF2 if method == "trbdf2" else 0,
-                                          bcv.ctypes.data_as(C.POINTER(C.c_double)) if bcv is not None else None),
-            be.ctx)
+                                          _dptr(bcv)), be.ctx)
 
 
 def step_implicit(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0, nsteps: int = 1,
@@ -1052,28 +1093,14 @@ def step_implicit(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, d
     _check_implicit_scope(model)
     be = model._backend()
     L = F.lib()
-    ya = Ya.handle if isinstance(Ya, FieldVector) else None
-    bcv = _implicit_bcv(model, be, t, dt, int(nsteps))
+    ya = _handle(Ya)
+    bcv = _sampled_bcv(model, [t + (k + 1) * dt for k in range(int(nsteps))], t)   # t_{n+1} of every step
     be.set_bcs(model, t)
     F.check(L.lh_step_implicit_euler(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
-                                     bcv.ctypes.data_as(C.POINTER(C.c_double)) if bcv is not None else None,
-                                     float(tol or 0.0), int(max_iter or 0)), be.ctx)
+                                     _dptr(bcv), float(tol or 0.0), int(max_iter or 0)), be.ctx)
     mi, un = C.c_int32(), C.c_int64()
     F.check(L.lh_implicit_stats(be.ctx, C.byref(mi), C.byref(un)), be.ctx)
     return int(mi.value), int(un.value)
-
-
-def _trbdf2_bcv(model, be, t0, t1):
-    """[t0 | t1][2][2] boundary values of every scalar Dirichlet closure at the two ends of a call (None
-    when nothing depends on time)."""
-    if not _time_dependent(model):
-        return None
-    vals = np.zeros((2, 2, 2))
-    for k, t in enumerate((t0, t1)):
-        for (f, c), (kind, v) in be.bc_values(model, t).items():
-            if np.ndim(v) == 0:
-                vals[k, f, c] = float(v)
-    return np.ascontiguousarray(vals)
 
 
 TRBDF2_ABSTOL, TRBDF2_RELTOL = 1e-6, 1e-3   # OrdinaryDiffEq's defaults (the library's for a 0)
@@ -1098,14 +1125,13 @@ def integrate_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.
     _check_implicit_scope(model, "TRBDF2")
     be = model._backend()
     L = F.lib()
-    ya = Ya.handle if isinstance(Ya, FieldVector) else None
-    bcv = _trbdf2_bcv(model, be, t0, t1)
+    ya = _handle(Ya)
+    bcv = _sampled_bcv(model, (t0, t1), t0)
     be.set_bcs(model, t0)
     ptr = None
     if dt_cols is not None:
         import torch
-        ft = torch.float64 if np.dtype(model.domain.FT) == np.float64 else torch.float32
-        if dt_cols.dtype != ft or not dt_cols.is_cuda or dt_cols.numel() != model.domain.ncolumns \
+        if dt_cols.dtype != _torch_ft_device(model)[0] or not dt_cols.is_cuda or dt_cols.numel() != model.domain.ncolumns \
                 or not dt_cols.is_contiguous():
             raise ValueError("dt_cols must be a contiguous device tensor of ncolumns values in the model's FT")
         torch.cuda.synchronize(dt_cols.device)   # (written on torch's stream, read on the library's)
@@ -1113,7 +1139,7 @@ def integrate_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.
     flags = 0 if adaptive else F.LH_TRBDF2_FIXED
     abstol, reltol = _trbdf2_tolerances(abstol, reltol)
     F.check(L.lh_integrate_trbdf2(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol, reltol, flags, ptr,
-                                  bcv.ctypes.data_as(C.POINTER(C.c_double)) if bcv is not None else None), be.ctx)
+                                  _dptr(bcv)), be.ctx)
     st = (C.c_int64 * F.LH_TRBDF2_NSTATS)()
     F.check(L.lh_trbdf2_stats(be.ctx, st), be.ctx)
     keys = ("accepted", "rejected", "newton_iterations", "max_steps", "failed", "wave_steps", "unconverged")
@@ -1122,15 +1148,15 @@ def integrate_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.
 
 def _advance_trbdf2(sim, t1):
     """The Simulation's TR-BDF2 from it.t to t1: one library call per dt interval when Dirichlet closures
-    depend on time, one for the whole interval otherwise; the per-column step proposals carry over."""
+    depend on time, one for the whole interval otherwise; the per-column step proposals carry over.
+    Returns the time reached (t1 itself, not a sum of steps)."""
     it, m, model = sim.integrator, sim.method, sim.model
     if t1 <= it.t:
-        return
+        return it.t
     if getattr(it, "_dt_cols", None) is None:
         import torch
-        be = model._backend()
-        ft = torch.float64 if np.dtype(model.domain.FT) == np.float64 else torch.float32
-        it._dt_cols = torch.zeros(model.domain.ncolumns, dtype=ft, device=torch.device("cuda", be.device_index()))
+        ft, dev = _torch_ft_device(model)
+        it._dt_cols = torch.zeros(model.domain.ncolumns, dtype=ft, device=dev)
         it.trbdf2_stats = dict(accepted=0, rejected=0, newton_iterations=0, max_steps=0, failed=0, wave_steps=0,
                                unconverged=0)
     if _time_dependent(model):
@@ -1143,6 +1169,7 @@ def _advance_trbdf2(sim, t1):
         for k, v in st.items():
             it.trbdf2_stats[k] += v   # (max_steps: the sum over calls of each call's largest count)
         it.t = te
+    return it.t
 
 
 class _Solution:
@@ -1174,15 +1201,10 @@ class Simulation:
 
     def __init__(self, model, method, *, Y_init, dt, tspan, Ya_init, callbacks=None, saveat=None,
                  **kwargs):
-        if isinstance(method, ImplicitEuler):
-            _check_implicit_scope(model)
-        elif isinstance(method, TRBDF2):
-            _check_implicit_scope(model, "TRBDF2")
-        elif isinstance(method, (HeatImplicitEuler, HeatTRBDF2)):
-            _check_heat_implicit_scope(model, type(method).__name__)
-        elif not isinstance(method, SSPRK33):
+        if not isinstance(method, (SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler)):
             raise NotImplementedError("only SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler and HeatTRBDF2 are "
                                       "provided on the device")
+        method.check_scope(model)
         self.method = method
         if Y_init is None:
             # simulation.jl:50 references an undefined variable here:
@@ -1238,7 +1260,8 @@ def _aux_constant_over(model, Ya, t, dt, nsteps) -> bool:
 def _advance_refreshing_aux(sim: Simulation, nsteps: int):
     """SSPRK33 steps for prescribed profiles that depend on time: the reference's rhs! re-evaluates
     them at EVERY stage time (update_aux_en!/update_aux_hydr!, right_hand_side.jl:37-42), so each
-    stage is its own launch (lh_ssprk33_stage) with Ya refreshed in between."""
+    stage is its own launch (lh_ssprk33_stage) with Ya refreshed in between.  Returns the time reached:
+    the sum of the steps, one dt at a time."""
     it, model = sim.integrator, sim.model
     be = model._backend()
     L = F.lib()
@@ -1247,92 +1270,65 @@ def _advance_refreshing_aux(sim: Simulation, nsteps: int):
     if getattr(it, "_stage_state", None) is None:
         it._stage_state = it.u.similar()
     U = it._stage_state
+    t = it.t
     for _ in range(nsteps):
-        for stage, ts in ((1, it.t), (2, it.t + it.dt), (3, it.t + it.dt / 2)):
+        stage_times = (t, t + it.dt, t + it.dt / 2)
+        # (without a Dirichlet closure: NULL, the values set_bcs has just set -- the same numbers)
+        vals = _sampled_bcv(model, stage_times, t)
+        for stage, ts in enumerate(stage_times, 1):
             update_en(it.p, ts)
             update_hy(it.p, ts)
-            vals = np.zeros((2, 2))
-            for (f, c), (kind, v) in be.bc_values(model, ts).items():
-                if np.ndim(v) == 0:
-                    vals[f, c] = float(v)
             be.set_bcs(model, ts)       # kinds and per-column values
             F.check(L.lh_ssprk33_stage(be.ctx, stage, it.u.handle, U.handle, it.p.handle, it.dt,
-                                       vals.ctypes.data_as(C.POINTER(C.c_double))), be.ctx)
-        it._nsteps_done += 1
-        it.t = it.t + it.dt
+                                       _dptr(None if vals is None else vals[stage - 1])), be.ctx)
+        t = t + it.dt
+    return t
 
 
-def _advance(sim: Simulation, nsteps: int):
+def _stage_times(t, dt, nsteps):
+    """[nsteps][3]: the stage times t_k, t_k + dt, t_k + dt/2 of SSPRK33 steps from t_k = (t + dt arange)[k]."""
+    return (t + dt * np.arange(nsteps))[:, None] + np.array((0.0, dt, dt / 2))
+
+
+def _advance_ssprk33(sim: Simulation, nsteps: int):
+    """lh_step_ssprk33 over `nsteps` steps, Dirichlet closures sampled at the three stage times of each.
+    Returns the time reached."""
     it = sim.integrator
     model = sim.model
-    if isinstance(getattr(sim, "method", None), ImplicitEuler):
-        if nsteps > 0:
-            m = sim.method
-            step_implicit(model, it.u, it.p, it.t, it.dt, nsteps, m.tol, m.max_iter)
-            it._nsteps_done += nsteps
-            it.t = it.t + nsteps * it.dt
-        return
-    if isinstance(getattr(sim, "method", None), TRBDF2):
-        if nsteps > 0:
-            # (the end of a chunk of nsteps intervals of dt, as the fixed-step methods reach it)
-            _advance_trbdf2(sim, it.tf if it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
-                            else it.t0 + (it._nsteps_done + nsteps) * it.dt)
-            it._nsteps_done += nsteps
-        return
-    if isinstance(getattr(sim, "method", None), (HeatImplicitEuler, HeatTRBDF2)):
-        if nsteps > 0:
-            if isinstance(it.p, FieldVector):   # the prescribed profiles of THIS time, held through the call
-                make_update_aux(model.energy_model)(it.p, it.t)
-                make_update_aux(model.hydrology_model)(it.p, it.t)
-            step_implicit_heat(model, it.u, it.p, it.t, it.dt, nsteps, sim.method.method)
-            it._nsteps_done += nsteps
-            it.t = it.t + nsteps * it.dt
-        return
     be = model._backend()
     L = F.lib()
-    ya = it.p.handle if isinstance(it.p, FieldVector) else None
-    if nsteps <= 0:
-        return
+    ya = _handle(it.p)
     if _device_reads_aux(model, it.p):
         # prescribed profiles on the device: every stage time of the chunk is probed; only a chunk
         # over which they do not change runs with Ya frozen (the persistent stepper), any other
         # refreshes Ya at every stage like the reference's rhs! does
         if nsteps > _PROBE_STEPS:
-            done = 0
-            while done < nsteps:
-                k = min(_PROBE_STEPS, nsteps - done)
-                _advance(sim, k)
-                done += k
-            return
+            for done in range(0, nsteps, _PROBE_STEPS):
+                it.t = _advance_ssprk33(sim, min(_PROBE_STEPS, nsteps - done))
+            return it.t
         if not _aux_constant_over(model, it.p, it.t, it.dt, nsteps):
             return _advance_refreshing_aux(sim, nsteps)
     if _aux_mask(be.kind, model) and isinstance(it.p, FieldVector):
         # constant-in-time profiles: still the values of THIS time (a user may have edited Ya)
         make_update_aux(model.energy_model)(it.p, it.t)
         make_update_aux(model.hydrology_model)(it.p, it.t)
-    bcv = None
-    if _time_dependent(model):
-        t = it.t + it.dt * np.arange(nsteps)
-        vals = np.zeros((nsteps, 3, 2, 2))
-        base = be.bc_values(model, it.t)
-        for (f, c), (kind, v) in base.items():
-            if np.ndim(v) == 0:
-                vals[:, :, f, c] = float(v)
-        for si, off in enumerate((0.0, it.dt, it.dt / 2)):
-            for k in range(nsteps):
-                for (f, c), (kind, v) in be.bc_values(model, t[k] + off).items():
-                    if kind == F.LH_BC_DIRICHLET and np.ndim(v) == 0:
-                        vals[k, si, f, c] = float(v)
-        bcv = np.ascontiguousarray(vals)
+    bcv = _sampled_bcv(model, _stage_times(it.t, it.dt, nsteps), it.t)
     be.set_bcs(model, it.t)
     if not getattr(it, "_placed", False) and _placement_tuning_wanted(model):
         it._placed = True
         F.check(L.lh_tune_placement(be.ctx, it.u.handle, ya, None, 0, 0, None, None), be.ctx)
-    F.check(L.lh_step_ssprk33(be.ctx, it.u.handle, ya, it.t, it.dt, nsteps,
-                              bcv.ctypes.data_as(C.POINTER(C.c_double)) if bcv is not None
-                              else None), be.ctx)
+    F.check(L.lh_step_ssprk33(be.ctx, it.u.handle, ya, it.t, it.dt, nsteps, _dptr(bcv)), be.ctx)
+    return it.t + nsteps * it.dt
+
+
+def _advance(sim: Simulation, nsteps: int):
+    """`nsteps` intervals of dt with the Simulation's method; the step count and the time are kept here."""
+    if nsteps <= 0:
+        return
+    it = sim.integrator
+    t = sim.method.advance(sim, nsteps)
     it._nsteps_done += nsteps
-    it.t = it.t + nsteps * it.dt
+    it.t = it.t + nsteps * it.dt if t is None else t
 
 
 def step(sim: Simulation):
