@@ -25,15 +25,11 @@
 // the step (the matrix is an M-matrix: its inverse is non-negative).  Stored per cell, folded back to
 // Y = rho_c_s u: the multiplier G_i-1 / den_i-1, rho_c_s,i / den_i and G_i alpha_i+1 rho_c_s,i / den_i.
 #pragma once
-#include "lh_kernels_impl.hpp" // grid_for, stage_math_tables; with it lh_closures.hpp, lh_launch.hpp, lh_dispatch.hpp
-                               // (with_bool), lh_fastmath.hpp (with_math) and lh_device.hpp (HeatImplicitArgs)
+#include "lh_kernels_impl.hpp" // grid_for; with it lh_column_ops.hpp (implicit_threads, implicit_math, implicit_lane_column),
+                               // lh_closures.hpp, lh_launch.hpp, lh_dispatch.hpp (with_bool), lh_fastmath.hpp (with_math)
+                               // and lh_device.hpp (HeatImplicitArgs)
 
 namespace lh {
-
-template <typename M>
-constexpr int heat_implicit_threads() {
-    return M::uses_tables ? 512 : 256; // (the Float64 tables take 48 KiB of LDS per workgroup)
-}
 
 // the energy flux of one boundary face in tendency units, as rhs_kernel forms it: boundary_fluxes_from / dz
 template <typename FT>
@@ -224,11 +220,10 @@ __device__ __forceinline__ void heat_implicit_column(const M& mm, DevParams<FT> 
 }
 
 template <typename FT, typename M, bool PERCOL, bool TRBDF2>
-__global__ void __launch_bounds__(heat_implicit_threads<M>())
+__global__ void __launch_bounds__(implicit_threads<M>())
 heat_implicit_kernel(const DevParams<FT> P, const HeatImplicitArgs<FT> A) {
-    __shared__ double s_tab[M::uses_tables ? MATH_TAB_DOUBLES : 2];
-    const M mm(stage_math_tables<M>(P.math_tab, s_tab)); // (every thread of the workgroup)
-    const int64_t col = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const M mm = implicit_math<M>(P.math_tab); // (every thread of the workgroup)
+    const int64_t col = implicit_lane_column();
     if (col >= P.ncols) return;
     FT nf_acc = FT(0);
     heat_implicit_column<FT, M, PERCOL, TRBDF2>(mm, P, A, col, nf_acc);
@@ -241,7 +236,7 @@ void launch_heat_implicit(const DevParams<FT>& P, const HeatImplicitArgs<FT>& A,
     with_math<FT>(math == MATH_LIBM, [&](auto m) { with_bool(percol, [&](auto pc) { with_bool(trbdf2, [&](auto tr) {
         using M = typename decltype(m)::type;
         hipLaunchKernelGGL((heat_implicit_kernel<FT, M, decltype(pc)::value, decltype(tr)::value>),
-                           grid_for(P.ncols, heat_implicit_threads<M>()), dim3(heat_implicit_threads<M>()), 0, s, P, A);
+                           grid_for(P.ncols, implicit_threads<M>()), dim3(implicit_threads<M>()), 0, s, P, A);
     }); }); });
 }
 

@@ -14,7 +14,7 @@
 // v_n lives in a third scratch plane, written by the first upward sweep of the step.
 // The Jacobian is approximate (slopes in Float32, water_slopes); R always uses the exact f.
 #pragma once
-#include "lh_kernels_impl.hpp" // grid_for, stage_math_tables, fmin_ft / fmax_ft; with it lh_closures.hpp, lh_launch.hpp,
+#include "lh_kernels_impl.hpp" // grid_for; with it lh_column_ops.hpp (implicit_math, fmin_ft / fmax_ft), lh_closures.hpp, lh_launch.hpp,
                                // lh_dispatch.hpp (with_bool), lh_fastmath.hpp (with_math) and lh_device.hpp (ImplicitArgs, Trbdf2Args)
 
 namespace lh {
@@ -86,11 +86,6 @@ __device__ __forceinline__ FT boundary_flux_slope(const DevParams<FT>& P, const 
     return FT(0);
 }
 
-template <typename M>
-constexpr int implicit_threads() {
-    return M::uses_tables ? 512 : 256; // (the Float64 tables take 48 KiB of LDS per workgroup)
-}
-
 // Which <M, PERCOL, NOICE, VGF> of implicit_euler_kernel / trbdf2_kernel exist: every one of the production
 // math (noice_exists, no conductivity factors here), and one per PERCOL of MathLibm, which reads theta_i
 // and has no tables for VGF to mean anything -- it is spelled NOICE = false, VGF = false.
@@ -110,15 +105,6 @@ inline void with_implicit_variant(const DevParams<FT>& P, bool percol, bool noic
     }); }); }); });
 }
 
-// The opening both kernels share: the math tables staged in LDS (every thread of the workgroup) ...
-template <typename M>
-__device__ __forceinline__ M implicit_math(const double* math_tab) {
-    __shared__ double s_tab[M::uses_tables ? MATH_TAB_DOUBLES : 2];
-    return M(stage_math_tables<M>(math_tab, s_tab));
-}
-// ... and the column this lane owns
-__device__ __forceinline__ int64_t implicit_lane_column() { return int64_t(blockIdx.x) * blockDim.x + threadIdx.x; }
-
 // The column's constants of one solve: ColC, the K and conductance scales of rhs_kernel's
 // instantiation, the safeguard's bound
 template <typename FT, typename M, bool PERCOL, bool NOICE>
@@ -129,8 +115,7 @@ struct ColumnSolve {
     __device__ __forceinline__ ColumnSolve(const M& mm, const DevParams<FT>& P, int64_t col) {
         c = make_colc<FT, M>(P, col, PERCOL);
         if (!NOICE) finish_colc<FT, M>(mm, c);
-        Ksc = RELK ? c.Ksat : FT(1);
-        cgw = RELK ? c.cgw : P.cg2;
+        flux_scales<FT, M>(P, c, Ksc, cgw);
         dmax = FT(LH_IMPLICIT_DMAX_FRAC) * (c.nu - c.theta_r);
         floor_r = c.theta_r;
     }
@@ -184,7 +169,8 @@ __device__ __forceinline__ void column_sweep_up(const M& mm, const DevParams<FT>
             vu = y[idu];
             tiu = NOICE ? FT(0) : ti[idu];
             closures(vu, tiu, Ku, npu, dKu, dnu);
-            // rhs_kernel's interior face: -(K_lo + K_hi) ((npsi_lo - npsi_hi) + dz) cgw
+            // interior_face's water flux (lh_column_ops.hpp), h and K_lo + K_hi kept for the Jacobian rows:
+            // -(K_lo + K_hi) ((npsi_lo - npsi_hi) + dz) cgw
             const FT h = head_difference(npu, np, P.dz);
             const FT Ks = K + Ku;
             Fhi = -Ks * (h * cgw);
@@ -299,13 +285,7 @@ __device__ __forceinline__ void implicit_column(const M& mm, DevParams<FT> P, co
     const int64_t stride = P.stride;
     const FT T = FT(288); // (read by nothing: no conductivity factors on this path)
     for (int64_t s = 0; s < A.nsteps; ++s) {
-        if (A.bcv) {
-            const FT* b = A.bcv + s * 4;
-            P.bc_value[FACE_BOTTOM][COMP_ENERGY] = b[0];
-            P.bc_value[FACE_BOTTOM][COMP_HYDROLOGY] = b[1];
-            P.bc_value[FACE_TOP][COMP_ENERGY] = b[2];
-            P.bc_value[FACE_TOP][COMP_HYDROLOGY] = b[3];
-        }
+        if (A.bcv) set_stage_boundary_values(P, A.bcv + s * 4);
         // The Dirichlet face states read the boundary value and the boundary cell's theta_i only
         // (no conductivity factors): constants of the step -- boundary_fluxes is face_state +
         // boundary_fluxes_from, so the fluxes are bitwise its own

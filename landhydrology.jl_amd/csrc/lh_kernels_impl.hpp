@@ -11,6 +11,7 @@
 // reference's equilibrium tests rely on (coupled.jl:117, richards_equation.jl:94).
 #pragma once
 #include "lh_closures.hpp"
+#include "lh_column_ops.hpp"
 #include "lh_launch.hpp"
 #include "lh_dispatch.hpp"
 #include "lh_atmos.hpp"
@@ -189,37 +190,6 @@ struct KCfg {
     static constexpr bool NT = NT_, SEG = SEG_;
 };
 
-// Stage the log2/exp2 tables of MathFast<double> in LDS (48 KiB per workgroup);
-// every thread of the block must call this before any thread leaves.
-template <typename M>
-__device__ __forceinline__ MathTables stage_math_tables(const double* gtab, double* lds) {
-    MathTables t;
-    t.log_tab = lds;
-    t.exp_tab = lds + 2 * LOG_TAB_N;
-    if (M::uses_tables) {
-        for (int i = threadIdx.x; i < MATH_TAB_DOUBLES; i += blockDim.x) lds[i] = gtab[i];
-        __syncthreads();
-    }
-    return t;
-}
-
-// positive IEEE values order like their bit patterns: global minima are integer atomicMin
-template <typename FT> struct Bits;
-template <> struct Bits<double> { using type = unsigned long long; };
-template <> struct Bits<float> { using type = unsigned int; };
-
-__device__ __forceinline__ double fmax_ft(double a, double b) { return __builtin_fmax(a, b); }
-__device__ __forceinline__ float fmax_ft(float a, float b) { return __builtin_fmaxf(a, b); }
-__device__ __forceinline__ double fmin_ft(double a, double b) { return __builtin_fmin(a, b); }
-__device__ __forceinline__ float fmin_ft(float a, float b) { return __builtin_fminf(a, b); }
-
-// max of two NON-NEGATIVE floats as a signed-integer max of their bit patterns (they order alike;
-// -0.0 and negative values lose, a NaN wins and is dropped with its lane at the end): one
-// v_max_i32 / v_max3_i32, where fmaxf costs a canonicalising v_max_f32 per operand on top
-__device__ __forceinline__ float max_nonneg(float a, float b) {
-    return __builtin_bit_cast(float, __builtin_elementwise_max(__builtin_bit_cast(int, a), __builtin_bit_cast(int, b)));
-}
-
 // Orders one wave's LDS traffic around a hand-off between its lanes: the LDS operations of a wave
 // execute in order, so no instruction is needed -- the wave barrier pins the compiler's schedule and
 // the two wavefront-scope fences (no code on gfx950) keep it from moving a load of another lane's
@@ -383,9 +353,7 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
     const M mm(stage_math_tables<M>(P.math_tab, s_tab));
     if (!M::uses_tables) __syncthreads();
 
-    // Workgroups are dealt round-robin to the 8 XCDs.  With xcd_remap, workgroup b handles
-    // column block (b % 8) * (nblocks / 8) + b / 8: each XCD streams one contiguous eighth of
-    // every plane row instead of every eighth 2-KiB piece.
+    // xcd_block's lines (through the call its blocks land in front of the staging loop and one scalar branch flips)
     unsigned blk = blockIdx.x;
     if (P.xcd_remap) {
         const unsigned per = gridDim.x >> 3;
@@ -454,20 +422,11 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
     }
 
     constexpr bool vgf = VGF && M::uses_tables; // integer-exponent 2^(.) (a host decision)
-    // Fluxes are carried in units of the TENDENCY: the arithmetic-mean factor 1/2 of InterpolateC2F,
-    // the 1/dz of GradientC2F and the 1/dz of DivergenceF2C are one constant cg = (1/2)/dz^2 applied to
-    // the centre difference, and (production math) the closures return K WITHOUT Ksat, which joins cg in
-    // the per-column constant of the water flux: two multiplications per cell less than
-    // F = -(K_lo + K_hi) (dh (1/2)/dz), -(F_hi - F_lo)/dz, a rounding-level regrouping.  Boundary
-    // fluxes (physical units, boundary_fluxes) are scaled by 1/dz once per column.
-    constexpr bool RELK = M::is_production;
+    // fluxes in tendency units, K without Ksat (flux_scales)
     const FT cgT = P.cg2;
-    FT cgw[CPL], Ksc[CPL]; // water flux constant; the factor that makes a closure K a true conductivity
+    FT cgw[CPL], Ksc[CPL];
 #pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-        Ksc[j] = RELK ? c[j].Ksat : FT(1);
-        cgw[j] = RELK ? c[j].cgw : cgT;
-    }
+    for (int j = 0; j < CPL; ++j) flux_scales<FT, M>(P, c[j], Ksc[j], cgw[j]);
 
     FT vl[CPL], ti[CPL], re[CPL], Ta[CPL];         // current cell inputs
     FT vl_n[PF][CPL], ti_n[PF][CPL], re_n[PF][CPL], Ta_n[PF][CPL]; // PF levels in flight
@@ -550,23 +509,13 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
             if (HEAT) rstore(o_re, dre);
         } else {
             auto stage = [&](const FT* brow, FT* orow, const FT (&u)[CPL], const FT (&k)[CPL], const FT (&yb)[CPL]) {
-                FT b[CPL], r[CPL];
+                constexpr int STAGE = MODE == 1 ? 0 : (MODE == 3 ? 2 : 1); // (MODE 2 and 5 are stage 1)
+                FT b[CPL] = {}, r[CPL]; // (b = 0: MODE 1 passes it on, stage 0 ignores it)
                 if (MODE == 2 || MODE == 3) rload(brow, b);
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
                     if (FROM_K1) b[j] = yb[j]; // (the base was read with the state: no second load)
-                    if (MODE == 1)
-                        r[j] = u[j] + dt * k[j];
-                    else if (MODE == 2 || MODE == 5)
-                        r[j] = (FT(3) * b[j] + u[j] + dt * k[j]) * FT(0.25);
-                    else {
-                        // s / 3 as s*(1/3) plus one residual correction: a bare multiply by
-                        // the rounded 1/3 biases every step by 5.5e-17 and the total mass
-                        // drifts (1.6e-11 after 138 240 steps); this form is unbiased
-                        const FT sum = b[j] + FT(2) * u[j] + FT(2) * dt * k[j];
-                        const FT q = sum * FT(1.0 / 3.0);
-                        r[j] = fma_ft(fma_ft(FT(-3), q, sum), FT(1.0 / 3.0), q);
-                    }
+                    r[j] = ssprk33_stage_value<FT>(STAGE, b[j], u[j], k[j], dt);
                 }
                 rstore(orow, r);
             };
@@ -609,24 +558,25 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
         // was measured: -1 instruction per cell but the prefetch distance shrinks by a cell -- C2 +2 %,
         // the HBM-bound Float32 C3 +5 % slower; with 4 levels in flight -1 % at twice the code.)
         if (i + PF < i_end) fetch(k);
-        FT K[CPL], psi[CPL], T[CPL], kap[CPL], E[CPL], rcs[CPL];
+        FT K[CPL], psi[CPL], T[CPL], kap[CPL], E[CPL]; // (psi[], psi_p[] hold -psi: see head_difference)
         float dpsi[CPL], ircs[CPL];
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
+            // cell_closures' lines, kept in this kernel's own text: through the call the step-bound terms of the MODE 4
+            // instantiations come out in other registers, and rhs_kernel's device code is held fixed
+            FT rcs = FT(1);
             T[j] = Ta[j];
             kap[j] = FT(0);
             K[j] = psi[j] = E[j] = FT(0);
             dpsi[j] = ircs[j] = 0.0f;
-            rcs[j] = FT(1);
             if (HEAT) {
-                T[j] = temperature_closure<FT, M, NOICE>(mm, P, c[j], vl[j], ti[j], re[j], rcs[j]);
+                T[j] = temperature_closure<FT, M, NOICE>(mm, P, c[j], vl[j], ti[j], re[j], rcs);
                 kap[j] = kappa_closure<FT, M, NOICE>(mm, P, c[j], vl[j], ti[j]);
-                if (WANT_DT) ircs[j] = float(mm.rcp(rcs[j])); // (the reciprocal temperature_closure formed)
+                if (WANT_DT) ircs[j] = float(mm.rcp(rcs)); // (the reciprocal temperature_closure formed)
             }
             if (WATER) {
-                // (psi[], psi_p[] hold -psi: see head_difference)
-                water_closures<FT, M, FACTORS, true, WANT_DT, NOICE, RELK, HEAT, true>(mm, P, c[j], vl[j], ti[j], T[j], K[j],
-                                                                                       psi[j], &dpsi[j], vgf);
+                water_closures<FT, M, FACTORS, true, WANT_DT, NOICE, M::is_production, HEAT, true>(mm, P, c[j], vl[j], ti[j], T[j], K[j],
+                                                                                                   psi[j], &dpsi[j], vgf);
                 if (HEAT) E[j] = (P.rhocp_l * (T[j] - P.T_ref)) * K[j]; // rho_e_int_l * K (:364)
             }
             if (WANT_DT && i > i_first) { // the rule of stable_dt_kernel per interior face (x 2)
@@ -655,21 +605,9 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
         } else if (!SEG || i > i_first) { // (the cell below a segment only primes the *_p values)
             FT Fw[CPL], Fe[CPL];
 #pragma unroll
-            for (int j = 0; j < CPL; ++j) {
-                Fw[j] = Fe[j] = FT(0);
-                FT gh = FT(0);
-                // -1/2 (a_lo + a_hi) (x_hi - x_lo)/dz /dz with the three constants (and Ksat) folded
-                // into the gradient's factor (see cgw above)
-                if (WATER) {
-                    gh = head_difference(psi[j], psi_p[j], P.dz) * cgw[j];
-                    Fw[j] = -(K_p[j] + K[j]) * gh;
-                }
-                if (HEAT) {
-                    FT gT = (T[j] - T_p[j]) * cgT;
-                    Fe[j] = -(kap_p[j] + kap[j]) * gT;
-                    if (WATER) Fe[j] = Fe[j] - (E_p[j] + E[j]) * gh;
-                }
-            }
+            for (int j = 0; j < CPL; ++j)
+                interior_face<FT, WATER, HEAT>(K_p[j], psi_p[j], T_p[j], kap_p[j], E_p[j], K[j], psi[j], T[j], kap[j], E[j],
+                                               P.dz, cgw[j], cgT, Fw[j], Fe[j]);
             if (!SEG || i > i_lo) emit(Fw, Fe, vl_p, re_p, yv_p, ye_p); // cell i-1 belongs to this segment
 #pragma unroll
             for (int j = 0; j < CPL; ++j) {
@@ -720,16 +658,13 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
     }
     if (nf_acc != nf_acc) atomicOr(P.status, 1u);
     if (WANT_DT) { // dt = courant dz^2 / (max D over the wave's columns), one atomicMin per wave
-        using U = typename Bits<FT>::type;
         float dmax = 0.0f;
 #pragma unroll
         for (int j = 0; j < CPL; ++j) { // (a column whose maximum is NaN is dropped: it is flagged through P.status)
             const float Dj = max_nonneg(max_nonneg(DmaxW[j] * float(Ksc[j]), DmaxWb[j]) * float(FT(1) / (c[j].n * c[j].m)), DmaxT[j]);
             if ((CPL == 1 || col0 + j < P.ncols) && Dj == Dj) dmax = max_nonneg(dmax, Dj);
         }
-        // Wave maximum by a binary tree through LDS (x -> fl(c/x) is monotone, so the minimum of
-        // the lanes' quotients IS the quotient of the maximum: one division per wave; a maximum
-        // is exact, so the result does not depend on how columns are dealt to waves or ranks).
+        // Wave maximum by a binary tree through LDS (one division per workgroup: bound_publish).
         // Lanes past the last column returned early -- a cross-lane shuffle could read their dead
         // registers; their LDS words hold the neutral 0 from the prologue.  The lanes still here
         // are a prefix of the wave (col0 grows with the lane), so lane l < off always has its
@@ -755,15 +690,7 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
             const unsigned nw = lanes_left >= int64_t(blockDim.x) ? nwaves : unsigned((lanes_left + 63) >> 6); // waves not gone at the top
             if (atomicAdd(&s_waves_done, 1u) == nw - 1u) {
                 for (unsigned w = 0; w < nwaves; ++w) dmax = max_nonneg(dmax, s_red[w << 6]);
-                if (dmax > 0.0f) {
-                    const FT best = (FT(2) * dt * P.dz * P.dz) / FT(dmax); // dmax = twice the diffusivity
-                    U b;
-                    __builtin_memcpy(&b, &best, sizeof(FT));
-                    // (most bounds are above the minimum already there: a plain read first -- the atomic only
-                    // when it would change the word; a stale read can only cause a redundant atomic)
-                    U* word = reinterpret_cast<U*>(P.dt_out);
-                    if (b < __atomic_load_n(word, __ATOMIC_RELAXED)) atomicMin(word, b);
-                }
+                if (dmax > 0.0f) bound_publish<FT>(P, dt, dmax); // (MODE 4: dt carries the Courant factor)
             }
         }
     }
@@ -784,11 +711,8 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
 // This thread-per-cell form serves columns of MORE than 128 levels; up to 128 levels a column is one
 // wavefront with one or two adjacent cells per lane and no workgroup barrier at all
 // (column_stepper_wave_kernel below).
-// exchange arrays per column / plane tiles of the initial fetch (the two share the dynamic LDS)
+// exchange arrays per column (StepperLds) / plane tiles of the initial fetch: the two share the dynamic LDS
 constexpr int CS_FACE_WORDS = 8; // column_stepper_wave_kernel: 2 faces x (K, psi, kappa) of a Dirichlet face state, padded
-template <int MODEL> constexpr int cs_exchange_arrays() {
-    return MODEL == MODEL_COUPLED ? 5 : 2;
-}
 // one-wave columns also publish the flux of the face BELOW each cell (water and/or heat), so that the
 // face above is read, not evaluated a second time
 template <int MODEL> constexpr int cs_flux_arrays() {
@@ -814,25 +738,13 @@ column_stepper_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Planes<F
     const int slot = int(threadIdx.x) / tpc;
     const int cpb = int(blockDim.x) / tpc;
     const FT dt = dt_device ? *dt_device : dt_value;
-    // exchange arrays of this column: (K, -psi) for the water, (T, kappa) for the heat, rho_e_l K for
-    // both -- only what the model needs (LDS per workgroup sets how many workgroups a CU holds)
     constexpr int NARR = cs_exchange_arrays<MODEL>();
-    FT* sK = reinterpret_cast<FT*>(s_dyn) + size_t(slot) * NARR * n;
-    FT* sh = sK + n;
-    FT* sT = WATER ? sh + n : sK;
-    FT* sKap = sT + n;
-    FT* sE = sKap + n;
+    const StepperLds<FT, MODEL> ex(reinterpret_cast<FT*>(s_dyn) + size_t(slot) * NARR * n, n); // this column's
     const M mm(stage_math_tables<M>(P0.math_tab, s_tab));
     if (!M::uses_tables) __syncthreads();
     DevParams<FT> P = P0; // boundary values change per stage
     const int i = int(threadIdx.x) - slot * tpc;
-    // XCD-contiguous workgroup map (as rhs_kernel): neighbouring workgroups share the 128-byte
-    // lines their 16..64-byte pieces of a plane row lie in, so they must share an L2
-    unsigned blk = blockIdx.x;
-    if (P.xcd_remap) {
-        const unsigned per = gridDim.x >> 3;
-        if (blk < (per << 3)) blk = (blk & 7u) * per + (blk >> 3);
-    }
+    const unsigned blk = xcd_block(P.xcd_remap);
     const int64_t col_raw = int64_t(blk) * cpb + slot;
     const bool cell = i < n && col_raw < P.ncols;
     const int ic = i < n ? i : n - 1;
@@ -840,11 +752,9 @@ column_stepper_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Planes<F
     ColC<FT> c = make_colc<FT, M>(P, col, PERCOL);
     if (WATER && !NOICE) finish_colc<FT, M>(mm, c);
     constexpr bool vgf = VGF && M::uses_tables; // (as rhs_kernel)
-    // fluxes in tendency units, K without Ksat: rhs_kernel's constants and expressions, to the letter
-    constexpr bool RELK = M::is_production;
     const FT cgT = P.cg2;
-    const FT Ksc = RELK ? c.Ksat : FT(1);
-    const FT cgw = RELK ? c.cgw : cgT;
+    FT Ksc, cgw;
+    flux_scales<FT, M>(P, c, Ksc, cgw);
     const bool need_Taux = (MODEL == MODEL_RICHARDS) && FACTORS && P.viscosity_kind;
     // Planes are column-fastest, threads here are level-fastest: go through LDS tiles so that
     // global memory sees the cpb adjacent columns of a level as one contiguous piece.  All
@@ -880,26 +790,14 @@ column_stepper_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Planes<F
         FT u_vl = y_vl, u_re = y_re; // the stage state
 #pragma unroll 1
         for (int stage = 0; stage < 3; ++stage) {
-            if (bcv) {
-                const FT* b = bcv + (s * 3 + stage) * 4;
-                P.bc_value[0][0] = b[0];
-                P.bc_value[0][1] = b[1];
-                P.bc_value[1][0] = b[2];
-                P.bc_value[1][1] = b[3];
-            }
-            FT T = Ta, kap = FT(0), K = FT(0), psi = FT(0), E = FT(0), rcs = FT(1);
-            if (HEAT) {
-                T = temperature_closure<FT, M, NOICE>(mm, P, c, u_vl, ti, u_re, rcs);
-                kap = kappa_closure<FT, M, NOICE>(mm, P, c, u_vl, ti);
-            }
-            if (WATER) {
-                water_closures<FT, M, FACTORS, true, false, NOICE, RELK, HEAT, true>(mm, P, c, u_vl, ti, T, K, psi, nullptr, vgf); // psi: -psi
-                if (HEAT) E = (P.rhocp_l * (T - P.T_ref)) * K; // rho_e_int_l * K (:364)
-            }
+            if (bcv) set_stage_boundary_values(P, bcv + (s * 3 + stage) * 4);
+            FT T, kap, K, psi, E; // psi: -psi
+            float dpsi, ircs;     // (the step bound's: not formed here)
+            cell_closures<FT, M, MODEL, FACTORS, NOICE, false>(mm, P, c, u_vl, ti, u_re, Ta, vgf, T, kap, K, psi, E, dpsi, ircs);
             if (i < n) {
-                if (WATER) { sK[i] = K; sh[i] = psi; }
-                if (HEAT) { sT[i] = T; sKap[i] = kap; }
-                if (HEAT && WATER) sE[i] = E;
+                if (WATER) { ex.K[i] = K; ex.h[i] = psi; }
+                if (HEAT) { ex.T[i] = T; ex.kap[i] = kap; }
+                if (HEAT && WATER) ex.E[i] = E;
             }
             __syncthreads();
             FT Fw_lo = FT(0), Fe_lo = FT(0), Fw_hi = FT(0), Fe_hi = FT(0);
@@ -918,16 +816,8 @@ column_stepper_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Planes<F
                     Fw_lo = Fw_b;
                     Fe_lo = Fe_b;
                 } else {
-                    FT gh = FT(0);
-                    if (WATER) { // (as rhs_kernel)
-                        gh = head_difference(psi, sh[i - 1], P.dz) * cgw;
-                        Fw_lo = -(sK[i - 1] + K) * gh;
-                    }
-                    if (HEAT) {
-                        const FT gT = (T - sT[i - 1]) * cgT;
-                        Fe_lo = -(sKap[i - 1] + kap) * gT;
-                        if (WATER) Fe_lo = Fe_lo - (sE[i - 1] + E) * gh;
-                    }
+                    interior_face<FT, WATER, HEAT>(ex.K[i - 1], ex.h[i - 1], ex.T[i - 1], ex.kap[i - 1], ex.E[i - 1], K, psi, T, kap, E,
+                                                   P.dz, cgw, cgT, Fw_lo, Fe_lo);
                 }
                 if (at_top) {
                     if (at_bottom) { // a one-cell column: the same thread owns both faces
@@ -939,16 +829,8 @@ column_stepper_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Planes<F
                         Fe_hi = Fe_b;
                     }
                 } else {
-                    FT gh = FT(0);
-                    if (WATER) {
-                        gh = head_difference(sh[i + 1], psi, P.dz) * cgw;
-                        Fw_hi = -(K + sK[i + 1]) * gh;
-                    }
-                    if (HEAT) {
-                        const FT gT = (sT[i + 1] - T) * cgT;
-                        Fe_hi = -(kap + sKap[i + 1]) * gT;
-                        if (WATER) Fe_hi = Fe_hi - (E + sE[i + 1]) * gh;
-                    }
+                    interior_face<FT, WATER, HEAT>(K, psi, T, kap, E, ex.K[i + 1], ex.h[i + 1], ex.T[i + 1], ex.kap[i + 1], ex.E[i + 1],
+                                                   P.dz, cgw, cgT, Fw_hi, Fe_hi);
                 }
             }
             const FT dvl = WATER ? Fw_lo - Fw_hi : FT(0);
@@ -957,16 +839,8 @@ column_stepper_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Planes<F
                 if (WATER) nf_acc = fma_ft(dvl, FT(0), nf_acc);
                 if (HEAT) nf_acc = fma_ft(dre, FT(0), nf_acc);
             }
-            // the stage updates of rhs_kernel MODE 1..3 (b = Y, u = stage state)
-            auto upd = [&](FT b, FT u, FT k) -> FT {
-                if (stage == 0) return u + dt * k;
-                if (stage == 1) return (FT(3) * b + u + dt * k) * FT(0.25);
-                const FT sum = b + FT(2) * u + FT(2) * dt * k;
-                const FT q = sum * FT(1.0 / 3.0);
-                return fma_ft(fma_ft(FT(-3), q, sum), FT(1.0 / 3.0), q);
-            };
-            if (WATER) u_vl = upd(y_vl, u_vl, dvl);
-            if (HEAT) u_re = upd(y_re, u_re, dre);
+            if (WATER) u_vl = ssprk33_stage_value<FT>(stage, y_vl, u_vl, dvl, dt);
+            if (HEAT) u_re = ssprk33_stage_value<FT>(stage, y_re, u_re, dre, dt);
             __syncthreads(); // neighbours have read this stage's LDS values
         }
         y_vl = u_vl;
@@ -1048,22 +922,14 @@ column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Pla
     constexpr int NEX = cs_exchange_arrays<MODEL>();
     constexpr int NARR = NEX + cs_flux_arrays<MODEL>();
     constexpr size_t COLW = size_t(NARR) * 64 + CS_FACE_WORDS;
-    FT* sK = reinterpret_cast<FT*>(s_dyn) + size_t(slot) * COLW;
-    FT* sh = sK + 64;
-    FT* sT = WATER ? sh + 64 : sK;
-    FT* sKap = sT + 64;
-    FT* sE = sKap + 64;
-    FT* sFw = sK + size_t(NEX) * 64;
+    const StepperLds<FT, MODEL> ex(reinterpret_cast<FT*>(s_dyn) + size_t(slot) * COLW, 64);
+    FT* sFw = ex.K + size_t(NEX) * 64;
     FT* sFe = WATER ? sFw + 64 : sFw;
-    FT* sFace = sK + size_t(NARR) * 64;
+    FT* sFace = ex.K + size_t(NARR) * 64;
     const M mm(stage_math_tables<M>(P0.math_tab, s_tab));
     if (!M::uses_tables) __syncthreads();
     DevParams<FT> P = P0; // boundary values change per stage
-    unsigned blk = blockIdx.x; // XCD-contiguous workgroup map (as rhs_kernel)
-    if (P.xcd_remap) {
-        const unsigned per = gridDim.x >> 3;
-        if (blk < (per << 3)) blk = (blk & 7u) * per + (blk >> 3);
-    }
+    const unsigned blk = xcd_block(P.xcd_remap);
     const int64_t col_raw = int64_t(blk) * cpb + slot;
     const int64_t col = col_raw < P.ncols ? col_raw : P.ncols - 1; // spare slots shadow the last column
     ColC<FT> c = make_colc<FT, M>(P, col, PERCOL);
@@ -1072,10 +938,9 @@ column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Pla
     // has to keep them in vector registers)
     if constexpr (PERCOL) c = wave_uniform(c);
     constexpr bool vgf = VGF && M::uses_tables;
-    constexpr bool RELK = M::is_production; // fluxes in tendency units, K without Ksat: as rhs_kernel, to the letter
     const FT cgT = P.cg2;
-    const FT Ksc = RELK ? c.Ksat : FT(1);
-    const FT cgw = RELK ? c.cgw : cgT;
+    FT Ksc, cgw;
+    flux_scales<FT, M>(P, c, Ksc, cgw);
     const bool need_Taux = (MODEL == MODEL_RICHARDS) && FACTORS && P.viscosity_kind;
     // planes are column-fastest, lanes here level-fastest: through LDS tiles [cpb][n] (column_stepper_kernel)
     FT* tiles = reinterpret_cast<FT*>(s_dyn);
@@ -1144,32 +1009,18 @@ column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Pla
         }
 #pragma unroll 1
         for (int stage = 0; stage < 3; ++stage) {
-            if (bcv) {
-                const FT* b = bcv + (s * 3 + stage) * 4;
-                P.bc_value[0][0] = b[0];
-                P.bc_value[0][1] = b[1];
-                P.bc_value[1][0] = b[2];
-                P.bc_value[1][1] = b[3];
-            }
-            FT T[CW], kap[CW], K[CW], psi[CW], E[CW];
+            if (bcv) set_stage_boundary_values(P, bcv + (s * 3 + stage) * 4);
+            FT T[CW], kap[CW], K[CW], psi[CW], E[CW]; // psi: -psi
 #pragma unroll
             for (int q = 0; q < CW; ++q) {
-                FT rcs = FT(1);
-                T[q] = Ta[q];
-                kap[q] = K[q] = psi[q] = E[q] = FT(0);
-                if (HEAT) {
-                    T[q] = temperature_closure<FT, M, NOICE>(mm, P, c, u_vl[q], ti[q], u_re[q], rcs);
-                    kap[q] = kappa_closure<FT, M, NOICE>(mm, P, c, u_vl[q], ti[q]);
-                }
-                if (WATER) {
-                    water_closures<FT, M, FACTORS, true, false, NOICE, RELK, HEAT, true>(mm, P, c, u_vl[q], ti[q], T[q], K[q], psi[q], nullptr, vgf); // psi: -psi
-                    if (HEAT) E[q] = (P.rhocp_l * (T[q] - P.T_ref)) * K[q]; // rho_e_int_l * K (:364)
-                }
+                float dpsi, ircs; // (the step bound's: not formed here)
+                cell_closures<FT, M, MODEL, FACTORS, NOICE, false>(mm, P, c, u_vl[q], ti[q], u_re[q], Ta[q], vgf, T[q], kap[q], K[q],
+                                                                   psi[q], E[q], dpsi, ircs);
             }
             // the lane's top cell, for the lane above
-            if (WATER) { sK[l] = K[CW - 1]; sh[l] = psi[CW - 1]; }
-            if (HEAT) { sT[l] = T[CW - 1]; sKap[l] = kap[CW - 1]; }
-            if (HEAT && WATER) sE[l] = E[CW - 1];
+            if (WATER) { ex.K[l] = K[CW - 1]; ex.h[l] = psi[CW - 1]; }
+            if (HEAT) { ex.T[l] = T[CW - 1]; ex.kap[l] = kap[CW - 1]; }
+            if (HEAT && WATER) ex.E[l] = E[CW - 1];
             wave_sync();
             // boundary faces: the lane with the bottom cell and the lane with the top cell go through
             // boundary_fluxes TOGETHER (one divergent pass, not two, when both faces need closures)
@@ -1215,16 +1066,16 @@ column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Pla
             if (at_bottom) {
                 Fw[0] = Fw_b;
                 Fe[0] = Fe_b;
-            } else { // (as rhs_kernel: lower cell first)
+            } else { // interior_face's lines, here and below (through the call one instantiation takes other SGPRs)
                 FT gh = FT(0);
                 if (WATER) {
-                    gh = head_difference(psi[0], sh[l - 1], P.dz) * cgw;
-                    Fw[0] = -(sK[l - 1] + K[0]) * gh;
+                    gh = head_difference(psi[0], ex.h[l - 1], P.dz) * cgw;
+                    Fw[0] = -(ex.K[l - 1] + K[0]) * gh;
                 }
                 if (HEAT) {
-                    const FT gT = (T[0] - sT[l - 1]) * cgT;
-                    Fe[0] = -(sKap[l - 1] + kap[0]) * gT;
-                    if (WATER) Fe[0] = Fe[0] - (sE[l - 1] + E[0]) * gh;
+                    const FT gT = (T[0] - ex.T[l - 1]) * cgT;
+                    Fe[0] = -(ex.kap[l - 1] + kap[0]) * gT;
+                    if (WATER) Fe[0] = Fe[0] - (ex.E[l - 1] + E[0]) * gh;
                 }
             }
 #pragma unroll
@@ -1253,14 +1104,6 @@ column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Pla
                 for (int q = 0; q < CW; ++q)
                     if (q == qt) { Fw[q + 1] = Fw_t; Fe[q + 1] = Fe_t; }
             }
-            // the stage updates of rhs_kernel MODE 1..3 (b = Y, u = stage state)
-            auto upd = [&](FT b, FT u, FT k) -> FT {
-                if (stage == 0) return u + dt * k;
-                if (stage == 1) return (FT(3) * b + u + dt * k) * FT(0.25);
-                const FT sum = b + FT(2) * u + FT(2) * dt * k;
-                const FT qq = sum * FT(1.0 / 3.0);
-                return fma_ft(fma_ft(FT(-3), qq, sum), FT(1.0 / 3.0), qq);
-            };
 #pragma unroll
             for (int q = 0; q < CW; ++q) {
                 const FT dvl = WATER ? Fw[q] - Fw[q + 1] : FT(0);
@@ -1269,8 +1112,8 @@ column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Pla
                     if (WATER) nf_acc = fma_ft(dvl, FT(0), nf_acc);
                     if (HEAT) nf_acc = fma_ft(dre, FT(0), nf_acc);
                 }
-                if (WATER) u_vl[q] = upd(y_vl[q], u_vl[q], dvl);
-                if (HEAT) u_re[q] = upd(y_re[q], u_re[q], dre);
+                if (WATER) u_vl[q] = ssprk33_stage_value<FT>(stage, y_vl[q], u_vl[q], dvl, dt);
+                if (HEAT) u_re[q] = ssprk33_stage_value<FT>(stage, y_re[q], u_re[q], dre, dt);
             }
             wave_sync(); // the neighbours have read this stage's LDS values
         }
@@ -1290,20 +1133,13 @@ column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Pla
         float dpsi[CW], ircs[CW];
 #pragma unroll
         for (int q = 0; q < CW; ++q) {
-            FT rcs = FT(1), psi = FT(0);
-            T[q] = Ta[q];
-            kap[q] = K[q] = FT(0);
-            dpsi[q] = ircs[q] = 0.0f;
-            if (HEAT) {
-                T[q] = temperature_closure<FT, M, NOICE>(mm, P, c, y_vl[q], ti[q], y_re[q], rcs);
-                kap[q] = kappa_closure<FT, M, NOICE>(mm, P, c, y_vl[q], ti[q]);
-                ircs[q] = float(mm.rcp(rcs));
-            }
-            if (WATER) water_closures<FT, M, FACTORS, true, true, NOICE, RELK, HEAT, true>(mm, P, c, y_vl[q], ti[q], T[q], K[q], psi, &dpsi[q], vgf);
+            FT psi, E; // (not needed by the bound)
+            cell_closures<FT, M, MODEL, FACTORS, NOICE, true>(mm, P, c, y_vl[q], ti[q], y_re[q], Ta[q], vgf, T[q], kap[q], K[q], psi, E,
+                                                              dpsi[q], ircs[q]);
         }
         // the lane's top cell, for the lane above (a float passes through an FT word unchanged)
-        if (WATER) { sK[l] = K[CW - 1]; sh[l] = FT(dpsi[CW - 1]); }
-        if (HEAT) { sKap[l] = kap[CW - 1]; sT[l] = FT(ircs[CW - 1]); }
+        if (WATER) { ex.K[l] = K[CW - 1]; ex.h[l] = FT(dpsi[CW - 1]); }
+        if (HEAT) { ex.kap[l] = kap[CW - 1]; ex.T[l] = FT(ircs[CW - 1]); }
         wave_sync();
         float DmaxW = 0.0f, DmaxWb = 0.0f, DmaxT = 0.0f; // as rhs_kernel MODE 4 names them
 #pragma unroll
@@ -1315,8 +1151,8 @@ column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Pla
                 if (q > 0) { // the cell below is the lane's own (q is a constant of the unrolled loop)
                     K_p = K[q - 1]; kap_p = kap[q - 1]; dpsi_p = dpsi[q - 1]; ircs_p = ircs[q - 1];
                 } else {
-                    if (WATER) { K_p = sK[l - 1]; dpsi_p = float(sh[l - 1]); }
-                    if (HEAT) { kap_p = sKap[l - 1]; ircs_p = float(sT[l - 1]); }
+                    if (WATER) { K_p = ex.K[l - 1]; dpsi_p = float(ex.h[l - 1]); }
+                    if (HEAT) { kap_p = ex.kap[l - 1]; ircs_p = float(ex.T[l - 1]); }
                 }
                 if (WATER) DmaxW = max_nonneg(DmaxW, float(K_p + K[q]) * max_nonneg(dpsi_p, dpsi[q]));
                 if (HEAT) DmaxT = max_nonneg(DmaxT, float(kap_p + kap[q]) * max_nonneg(ircs_p, ircs[q]));
@@ -1359,14 +1195,7 @@ column_stepper_wave_kernel(const DevParams<FT> P0, const Planes<FT> Y, const Pla
         if (l == 0 && col_raw < P.ncols) { // (a column whose maximum is NaN is dropped, as in MODE 4)
             const float Dj = max_nonneg(max_nonneg(DmaxW * float(Ksc), DmaxWb) * float(FT(1) / (c.n * c.m)), DmaxT);
             const float dmax = Dj == Dj ? max_nonneg(0.0f, Dj) : 0.0f;
-            if (dmax > 0.0f) {
-                using U = typename Bits<FT>::type;
-                const FT best = (FT(2) * courant * P.dz * P.dz) / FT(dmax); // dmax = twice the diffusivity
-                U b;
-                __builtin_memcpy(&b, &best, sizeof(FT));
-                U* word = reinterpret_cast<U*>(P.dt_out);
-                if (b < __atomic_load_n(word, __ATOMIC_RELAXED)) atomicMin(word, b);
-            }
+            if (dmax > 0.0f) bound_publish<FT>(P, courant, dmax);
         }
     }
     __syncthreads(); // the tiles overlay other columns' exchange arrays
@@ -1612,11 +1441,7 @@ __global__ void __launch_bounds__(256, 8)
 stream_probe_kernel(const int64_t ncols, const int64_t stride, const int nlev, const int xcd_remap,
                     const Planes<FT> IN, const int nr, const Planes<FT> OUT, const int nw) {
     static_assert(sizeof(FT) * CPL == 8, "one 8-byte access per lane");
-    unsigned blk = blockIdx.x;
-    if (xcd_remap) {
-        const unsigned per = gridDim.x >> 3;
-        if (blk < (per << 3)) blk = (blk & 7u) * per + (blk >> 3);
-    }
+    const unsigned blk = xcd_block(xcd_remap);
     const int64_t col0 = (int64_t(blk) * blockDim.x + threadIdx.x) * CPL;
     if (col0 >= ncols) return;
     const unsigned lane_byte = (unsigned)col0 * (unsigned)sizeof(FT);
