@@ -22,9 +22,6 @@
 using namespace lh;
 
 // default address stagger between consecutively allocated planes (bytes)
-#ifndef LH_PLANE_STAGGER
-#define LH_PLANE_STAGGER 0 /* no consistent gain measured (profiles/round1_tune_plane_stagger.txt): placement noise is +-5 % */
-#endif
 
 namespace {
 
@@ -106,7 +103,6 @@ struct lh_ctx {
     void* d_tr = nullptr;              // lh_integrate_trbdf2: six FT planes [nlev][stride] (Y_n, f_n, Y_gamma, w, c', d')
     void* d_tr_stats = nullptr;        // ... and its LH_TRBDF2_NSTATS uint64 counters
     void* d_heat = nullptr;            // lh_step_heat_implicit: eight FT planes [nlev][stride] (three of the factorisation, kc, z; kappa sums, alpha, beta)
-    void* d_tr_f = nullptr;            // ... two more planes when the error solve reuses stage 2's factorisation
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
     Tune tune;
@@ -382,7 +378,7 @@ AtmosParams<FT> make_atmos_params(const lh_ctx* c) {
     return A;
 }
 
-// "block=128,pf=2,nt=1,cpl=2": launch-shape overrides (lh_launch.hpp, Tune)
+// "block=128,nt=1,seg=16": launch overrides (lh_launch.hpp, Tune); a key it does not scan for is ignored
 void parse_tune(Tune& tu, const char* t) {
     tu = Tune();
     int v;
@@ -397,10 +393,7 @@ void parse_tune(Tune& tu, const char* t) {
     if ((q = strstr(t, "vgfast=")) && sscanf(q + 7, "%d", &v) == 1 && (v == 0 || v == 1)) tu.vgfast = v;
     if ((q = strstr(t, "trk=")) && sscanf(q + 4, "%d", &v) == 1 && v >= 1 && v <= 10000) tu.trk = v;
     if ((q = strstr(t, "trn=")) && sscanf(q + 4, "%d", &v) == 1 && v >= 1 && v <= 100) tu.trn = v;
-    if ((q = strstr(t, "trf=")) && sscanf(q + 4, "%d", &v) == 1 && (v == 0 || v == 1)) tu.trf = v;
     if ((q = strstr(t, "block=")) && sscanf(q + 6, "%d", &v) == 1 && v >= 64 && v <= 1024 && v % 64 == 0) tu.block = v;
-    if ((q = strstr(t, "cpl=")) && sscanf(q + 4, "%d", &v) == 1) tu.cpl = v;
-    if ((q = strstr(t, "pf=")) && sscanf(q + 3, "%d", &v) == 1) tu.pf = v;
     if ((q = strstr(t, "nt=")) && sscanf(q + 3, "%d", &v) == 1) tu.nt = v;
     if ((q = strstr(t, "arena=")) && sscanf(q + 6, "%d", &v) == 1 && v >= 1 && v <= 64) tu.arena = v;
     if ((q = strstr(t, "rowpad=")) && sscanf(q + 7, "%d", &v) == 1 && v >= 0 && v % 2 == 0) tu.rowpad = v;
@@ -603,7 +596,8 @@ int do_rhs(lh_ctx* c, const lh_state* in, const lh_state* aux, const lh_state* b
 constexpr int ARENA_SLOTS = 8;
 
 void* plane_alloc(lh_ctx* c, size_t bytes) {
-    const size_t pad = c->tune.pad >= 0 ? size_t(c->tune.pad) : LH_PLANE_STAGGER;
+    // (no stagger by default: no consistent gain measured, profiles/round1_tune_plane_stagger.txt -- placement noise is +-5 %)
+    const size_t pad = c->tune.pad >= 0 ? size_t(c->tune.pad) : 0;
     // slot pitch: plane size rounded to 2 MiB, plus the stagger (LH_TUNE pad=, a multiple of 256 B)
     const size_t slot = (((bytes + (size_t(2) << 20) - 1) >> 21) << 21) + pad;
     for (auto& a : c->arenas)
@@ -1209,7 +1203,6 @@ int lh_destroy(lh_ctx* c) {
     if (c->d_imp_stats) (void)hipFree(c->d_imp_stats);
     if (c->d_tr) (void)hipFree(c->d_tr);
     if (c->d_tr_stats) (void)hipFree(c->d_tr_stats);
-    if (c->d_tr_f) (void)hipFree(c->d_tr_f);
     if (c->d_heat) (void)hipFree(c->d_heat);
     for (int k = 0; k < 3; ++k)
         if (c->d_atm_pc[k]) (void)hipFree(c->d_atm_pc[k]);
@@ -1907,8 +1900,7 @@ int lh_implicit_stats(lh_ctx* c, int32_t* max_iters, int64_t* unconverged) {
     return rc;
 }
 
-// lh_integrate_trbdf2's defaults (LH_TUNE trk= / trn= override the Newton pair, and
-// trf=1 selects the error solve with stage 2's factorisation in tuning builds)
+// lh_integrate_trbdf2's defaults (LH_TUNE trk= / trn= override the Newton pair)
 #define LH_TRBDF2_ABSTOL_DEFAULT 1e-6
 #define LH_TRBDF2_RELTOL_DEFAULT 1e-3
 #define LH_TRBDF2_NEWTON_KAPPA 0.01 // stage Newton test: max |delta| / (atol + rtol |Y|) <= this ...
@@ -1935,14 +1927,8 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
     // each tolerance that is 0 takes its own default (OrdinaryDiffEq's)
     if (!(abstol > 0)) abstol = LH_TRBDF2_ABSTOL_DEFAULT;
     if (!(reltol > 0)) reltol = LH_TRBDF2_RELTOL_DEFAULT;
-#ifdef LH_TUNING_VARIANTS
-    const bool reuse = c->tune.trf > 0; // (measured slower than re-forming J at Y_1: tuning builds only)
-#else
-    const bool reuse = false;
-#endif
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
     if ((rc = ensure_scratch(c, &c->d_tr, 6 * pl * c->esize, "c->d_tr", "6 * plane"))) return rc;
-    if (reuse && (rc = ensure_scratch(c, &c->d_tr_f, 2 * pl * c->esize, "c->d_tr_f", "2 * plane"))) return rc;
     if ((rc = ensure_scratch(c, &c->d_tr_stats, nstat, "c->d_tr_stats", "nstat", true))) return rc;
     if (t1 == t0) return LH_OK;
     if ((rc = materialize(c, Y, ~0u))) return rc;
@@ -1966,9 +1952,6 @@ int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, d
         A.max_iter = 50;
         A.kappa = FT(c->tune.trk > 0 ? 1e-4 * c->tune.trk : LH_TRBDF2_NEWTON_KAPPA);
         A.newton_max = c->tune.trn > 0 ? c->tune.trn : LH_TRBDF2_NEWTON_MAX;
-        A.reuse = reuse;
-        A.fa = A.fden = nullptr;
-        if (reuse) carve_planes<FT>(c->d_tr_f, pl, {&A.fa, &A.fden});
         A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
         launch_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
     });

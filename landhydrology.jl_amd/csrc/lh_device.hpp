@@ -179,9 +179,6 @@ struct Trbdf2Args {
     int32_t max_iter;
     FT kappa;            // (adaptive) stage Newton test max |delta| / (atol + rtol |Y|) <= kappa ...
     int32_t newton_max;  // ... within newton_max iterations, else the step is rejected
-    int32_t reuse;       // error solve with stage 2's last factorisation (fa, fden, cp) instead of J re-formed at Y_1
-    FT* fa;              // (reuse) two more scratch planes: a_i and the pivots of that factorisation
-    FT* fden;
     unsigned long long* stats; // accepted, rejected, Newton iterations, max steps, failed, wave_steps, unconverged
 };
 // one column's counters of a call (reduced over the wave)

@@ -125,14 +125,11 @@ struct ColumnSolve {
 // cells, the face fluxes exactly as rhs_kernel forms them, and f_i = F_lo - F_hi.  row(idx, v_i, f_i)
 // returns R_i; with JAC the sweep also forms row i of J = I - coef df/dv and eliminates forward
 // (c'_i, d'_i of J x = -R to cp, dp); without it, row only sees f (the tendency).
-// With STORE the sweep also keeps a_i and the pivot den_i (planes sa, sden): with cp they are the whole
-// factorisation, for TR-BDF2's error solve at the end of stage 2 (Trbdf2Args::reuse).
-template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool JAC, typename Row, bool STORE = false>
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool JAC, typename Row>
 __device__ __forceinline__ void column_sweep_up(const M& mm, const DevParams<FT>& P,
                                                 const ColumnSolve<FT, M, PERCOL, NOICE>& S, const FaceState<FT>& fsb,
                                                 const FaceState<FT>& fst, int64_t col, const FT* y, const FT* ti,
-                                                FT ti_b, FT coef, FT* cp, FT* dp, Row&& row, FT* sa = nullptr,
-                                                FT* sden = nullptr) {
+                                                FT ti_b, FT coef, FT* cp, FT* dp, Row&& row) {
     constexpr bool RELK = ColumnSolve<FT, M, PERCOL, NOICE>::RELK;
     constexpr bool vgf = VGF && M::uses_tables;
     const ColC<FT>& c = S.c;
@@ -194,10 +191,6 @@ __device__ __forceinline__ void column_sweep_up(const M& mm, const DevParams<FT>
             const FT dpi = (-R - a * dp_prev) / den;
             cp[idx] = cpi;
             dp[idx] = dpi;
-            if constexpr (STORE) {
-                sa[idx] = a;
-                sden[idx] = den;
-            }
             cp_prev = cpi;
             dp_prev = dpi;
         }
@@ -215,12 +208,12 @@ __device__ __forceinline__ void column_sweep_up(const M& mm, const DevParams<FT>
 // with WFIRST the first upward sweep copies y into w (backward Euler's v_n).  Convergence, per column:
 // backward Euler's max_i |delta_i| <= tol max(|v_i|, nu), or with ADAPT
 // max_i |delta_i| / (atol + rtol |v_i|) <= kappa.  Returns the iteration count.
-template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool WFIRST, bool ADAPT, bool STORE = false>
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool WFIRST, bool ADAPT>
 __device__ __forceinline__ int newton_stage(const M& mm, const DevParams<FT>& P,
                                             const ColumnSolve<FT, M, PERCOL, NOICE>& S, const FaceState<FT>& fsb,
                                             const FaceState<FT>& fst, int64_t col, FT* y, const FT* ti, FT ti_b,
                                             FT* w, FT* cp, FT* dp, FT coef, FT tol, FT atol, FT rtol, int max_iter,
-                                            bool& conv, FT kappa = FT(0), FT* sa = nullptr, FT* sden = nullptr) {
+                                            bool& conv, FT kappa = FT(0)) {
     const ColC<FT>& c = S.c;
     const int n = P.nlev;
     const FT dmax = S.dmax, floor_r = S.floor_r;
@@ -235,8 +228,7 @@ __device__ __forceinline__ int newton_stage(const M& mm, const DevParams<FT>& P,
             if (WFIRST && it == 0) { vn = v; w[idx] = v; } else vn = w[idx];
             return (v - vn) - coef * f;
         };
-        column_sweep_up<FT, M, PERCOL, NOICE, VGF, true, decltype(row)&, STORE>(mm, P, S, fsb, fst, col, y, ti, ti_b,
-                                                                               coef, cp, dp, row, sa, sden);
+        column_sweep_up<FT, M, PERCOL, NOICE, VGF, true>(mm, P, S, fsb, fst, col, y, ti, ti_b, coef, cp, dp, row);
         // ---------------- downward sweep
         FT dnext = FT(0);
         bool ok = true;
@@ -438,16 +430,8 @@ __device__ __forceinline__ void trbdf2_column(const M& mm, DevParams<FT> P, cons
                 w[id] = (v - c_yn * yn[id]) * c_w2;
             }
             faces_at(t + hh);
-#ifdef LH_TUNING_VARIANTS
-            if (A.reuse) // (keeps the factorisation of the last iteration for the error solve)
-                it = newton_stage<FT, M, PERCOL, NOICE, VGF, false, true, true>(
-                    mm, P, S, fsb, fst, col, y, A.ti, ti_b, w, A.cp, A.dp, dh, tol, atol, rtol, max_iter, conv, kappa,
-                    A.fa, A.fden);
-            else
-#endif
-                it = newton_stage<FT, M, PERCOL, NOICE, VGF, false, true>(mm, P, S, fsb, fst, col, y, A.ti, ti_b, w,
-                                                                           A.cp, A.dp, dh, tol, atol, rtol, max_iter,
-                                                                           conv, kappa);
+            it = newton_stage<FT, M, PERCOL, NOICE, VGF, false, true>(mm, P, S, fsb, fst, col, y, A.ti, ti_b, w, A.cp,
+                                                                       A.dp, dh, tol, atol, rtol, max_iter, conv, kappa);
             st.iters += unsigned(it);
             newton_ok = conv;
             if (!conv && A.fixed) ++st.unconv;
@@ -456,9 +440,8 @@ __device__ __forceinline__ void trbdf2_column(const M& mm, DevParams<FT> P, cons
         bool accept = A.fixed != 0;
         if (!A.fixed && newton_ok) {
             // the error estimate: rhs b1 h f_n + b2 z_g + b3 z_1 and J re-formed at Y_1 (the stage-2 face
-            // states).  Tuning builds can instead reuse the factorisation of stage 2's last Newton iteration
-            // (A.reuse, LH_TUNE trf=1): two more planes and no closures in the sweep, measured 4-8 % slower
-            // 
+            // states).  (Tried: the factorisation of stage 2's last Newton iteration kept for this solve -- two
+            // more planes, no closures in the sweep -- measured 4-8 % slower and removed)
             const FT hf = FT(hh);
             auto rhs = [&](int64_t idx, FT v) {
                 const FT f0 = fn[idx], v0 = yn[idx];
@@ -466,22 +449,9 @@ __device__ __forceinline__ void trbdf2_column(const M& mm, DevParams<FT> P, cons
                 const FT z1 = (v - w[idx]) * inv_d;
                 return b1 * (hf * f0) + b2 * zg + b3 * z1;
             };
-#ifdef LH_TUNING_VARIANTS
-            if (A.reuse) {
-                FT dprev = FT(0);
-                for (int i = 0; i < n; ++i) {
-                    const int64_t id = int64_t(i) * stride + col;
-                    const FT dpi = (rhs(id, y[id]) - A.fa[id] * dprev) / A.fden[id];
-                    A.dp[id] = dpi;
-                    dprev = dpi;
-                }
-            } else
-#endif
-            {
-                column_sweep_up<FT, M, PERCOL, NOICE, VGF, true>(
-                    mm, P, S, fsb, fst, col, y, A.ti, ti_b, dh, A.cp, A.dp,
-                    [&](int64_t idx, FT v, FT) { return -rhs(idx, v); }); // (R = -rhs: the sweep solves J e = -R)
-            }
+            column_sweep_up<FT, M, PERCOL, NOICE, VGF, true>(
+                mm, P, S, fsb, fst, col, y, A.ti, ti_b, dh, A.cp, A.dp,
+                [&](int64_t idx, FT v, FT) { return -rhs(idx, v); }); // (R = -rhs: the sweep solves J e = -R)
             FT enext = FT(0);
             double sum = 0.0;
             for (int i = n - 1; i >= 0; --i) {

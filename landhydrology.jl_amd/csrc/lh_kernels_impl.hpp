@@ -19,45 +19,14 @@
 
 namespace lh {
 
-// minimum waves per SIMD the register allocator must leave room for in the
-// column kernel (64 VGPRs): the kernel hides HBM latency by occupancy
-#ifndef LH_RHS_WAVES_PER_SIMD
-#define LH_RHS_WAVES_PER_SIMD 8
-#endif
-#ifndef LH_RHS_F64_WAVES
-#define LH_RHS_F64_WAVES 6
-#endif
-
-// waves/SIMD the Float32 coupled tendency + step-bound launch is compiled for (86 VGPRs unconstrained)
-#ifndef LH_F32C_DT_WAVES
-#define LH_F32C_DT_WAVES 5
-#endif
-// ... and whether that launch keeps its column constants in VGPRs (as the plain tendency launch
-// does) or in SGPRs at LH_F32C_DT_WAVES_SGPR waves/SIMD
-// (measured on C3, fused-dt launch: VGPR constants at 5 waves 0.215 ms; SGPR constants at 8 waves
-// with 12 B of scratch 0.224, at 7 waves 0.222)
-#ifndef LH_F32C_DT_VGPRCONST
-#define LH_F32C_DT_VGPRCONST 1
-#endif
-#ifndef LH_F32C_DT_WAVES_SGPR
-#define LH_F32C_DT_WAVES_SGPR 8
-#endif
-
-// waves/SIMD of the per-column Richards tendency + step-bound launch (C5); measured: 6 waves (72 VGPRs)
-// 0.511 ms, 8 waves (64 VGPRs + 20 B of scratch) 0.537 ms
-#ifndef LH_PERCOL_DT_WAVES
-#define LH_PERCOL_DT_WAVES 6
-#endif
-
-// The plain production kernels are held to 64 VGPRs (8 waves/SIMD); the
-// per-column / conductivity-factor variants and the libm debug policy keep what
-// they need (a bound there only produces scratch spills).
-// the coupled tendency launches (MODE 0 and 4; Float32 without factors, Float64 always) keep
-// their column constants in VGPRs
+// the coupled tendency launches (MODE 0 and 4) without conductivity factors keep their column constants in
+// VGPRs, and the Float32 step-bound launch with them too
 template <typename FT, int MODEL, bool FACTORS, bool PERCOL, typename M, int MODE>
 constexpr bool f32_coupled_vgpr_constants() {
     if (MODEL != MODEL_COUPLED || PERCOL || !M::is_production || !(MODE == 0 || MODE == 4)) return false;
-    if (sizeof(FT) == 4 && MODE == 4) return LH_F32C_DT_VGPRCONST != 0;
+    // (Float32 with the step bound, measured on C3, fused-dt launch: VGPR constants at 5 waves 0.215 ms; SGPR
+    // constants at 8 waves with 12 B of scratch 0.224, at 7 waves 0.222)
+    if (sizeof(FT) == 4 && MODE == 4) return true;
     // Float64: without conductivity factors only.  (Round 2 pinned the factors kernels too, +2.5 % at 127
     // VGPRs + 12 B of scratch; with the round-3 closures the pinned tendency kernel needs 154 VGPRs --
     // 3 waves, 0.61 ms on f3c64 -- or spills 76 B at 4 waves, 0.67 ms; unpinned it fits 119 VGPRs at 4
@@ -70,39 +39,49 @@ constexpr bool heat_vgpr_constants() {
     return sizeof(FT) == 8 && MODEL != MODEL_RICHARDS && M::is_production && !NOICE;
 }
 
-template <typename FT, int MODEL, bool FACTORS, bool PERCOL, typename M, int PF, int MODE, bool NOICE = false, int CPL = 1>
+// Minimum waves per SIMD the register allocator must leave room for in the column kernel: the kernel hides
+// HBM latency by occupancy.  The plain production kernels are held to 64 VGPRs (8 waves/SIMD); the per-column /
+// conductivity-factor variants and the libm debug policy keep what they need (a bound there only produces
+// scratch spills).  One line per class of instantiation, the first match wins.
+template <typename FT, int MODEL, bool FACTORS, bool PERCOL, typename M, int PF, int MODE, bool NOICE = false>
 constexpr int rhs_waves_per_simd() {
-    if (sizeof(FT) == 4 && CPL >= 4) return 4; // (tuning builds: four Float32 columns per lane, 16-byte accesses)
-    // Float64 heat kernels with conductivity factors: 127 VGPRs (4 waves/SIMD, 512-thread workgroups)
-    // with the uniform constants left to the SGPR file and its spills beats 156 VGPRs with the
-    // constants VGPR-resident at 3 waves (f3c64 tendency 0.530 vs 0.554 ms); the step-bound launch
-    // would spill to scratch under that bound and keeps the other arrangement
-    // (Richards with a conductivity factor: 66 VGPRs unconstrained = 6 waves; bounded to 64 for 8 waves it
-    // spills SGPRs to lanes and 12 B to scratch: 0.324 vs 0.307 ms on f3v64 -- left unconstrained)
-#ifndef LH_F64_FACTORS_STAGE_WAVES4
-#define LH_F64_FACTORS_STAGE_WAVES4 0
-#endif
-#ifndef LH_F64_FACTORS_TEND_WAVES
-#define LH_F64_FACTORS_TEND_WAVES 4
-#endif
-    // (round 3: with its column constants pinned in VGPRs the tendency kernel needs 154; they are left to
-    // the SGPR file now, see f32_coupled_vgpr_constants)
-    if (M::is_production && FACTORS && sizeof(FT) == 8 && MODEL != MODEL_RICHARDS && !PERCOL &&
-        (MODE == 0 || (LH_F64_FACTORS_STAGE_WAVES4 && MODE != 4))) return LH_F64_FACTORS_TEND_WAVES;
-    if (!M::is_production || FACTORS) return 1;
+    constexpr bool F64 = sizeof(FT) == 8, RICHARDS = MODEL == MODEL_RICHARDS;
+    // the libm debug policy keeps what it needs
+    if (!M::is_production) return 1;
+    // Float64 heat / coupled tendency with conductivity factors: 127 VGPRs (4 waves/SIMD, 512-thread workgroups)
+    // with the uniform constants left to the SGPR file and its spills beats 156 VGPRs with the constants
+    // VGPR-resident at 3 waves (f3c64 tendency 0.530 vs 0.554 ms; round 3: pinned, the kernel needs 154, see
+    // f32_coupled_vgpr_constants).  The tendency only: the step-bound launch would spill to scratch under that
+    // bound and keeps the other arrangement, the fused stages are left unconstrained (the next line).
+    if (FACTORS && F64 && !RICHARDS && !PERCOL && MODE == 0) return 4;
+    // every other kernel with conductivity factors is left unconstrained.  (Richards: 66 VGPRs = 6 waves;
+    // bounded to 64 for 8 waves it spills SGPRs to lanes and 12 B to scratch, 0.324 vs 0.307 ms on f3v64)
+    if (FACTORS) return 1;
+    // per-column Richards without ice, tendency + step bound (measured on C5): 6 waves (72 VGPRs) 0.511 ms, 8 waves
+    // (64 VGPRs + 20 B of scratch) 0.537 ms
+    if (RICHARDS && NOICE && PERCOL && MODE == 4) return 6;
     // Float64 Richards without ice fits 64 VGPRs (8 waves) in every mode, but asked for only 6 waves (<= 80 VGPRs,
     // 512-thread workgroups, 3 per CU) the max-ILP scheduler uses the room: tendency -1 %, with the step bound -2 %,
-    // C5 -1.6 %, the Dirichlet ensemble C1 -4 %, fused stages equal (round 3, same-process A/B).  Float32 keeps 8
-    // (its fused stages lose 5 % at 6).
-    if (MODEL == MODEL_RICHARDS && NOICE && sizeof(FT) == 8 && !PERCOL) return LH_RHS_F64_WAVES;
-    if (MODEL == MODEL_RICHARDS && NOICE && PERCOL) return MODE == 4 ? LH_PERCOL_DT_WAVES : (sizeof(FT) == 8 ? LH_RHS_F64_WAVES : LH_RHS_WAVES_PER_SIMD); // 62 VGPRs (72 with the dt bound)
+    // C5 -1.6 %, the Dirichlet ensemble C1 -4 %, fused stages equal (round 3, same-process A/B)
+    if (RICHARDS && NOICE && F64) return 6;
+    // Float32 Richards without ice, per-column parameters (62 VGPRs) or not: no ice ring, fits 64 VGPRs in every
+    // mode (its fused stages lose 5 % at 6)
+    if (RICHARDS && NOICE) return 8;
+    // every other kernel with per-column parameters is left unconstrained
     if (PERCOL) return 1;
-    if (MODEL == MODEL_RICHARDS && NOICE) return LH_RHS_WAVES_PER_SIMD; // no ice ring: fits 64 VGPRs in every mode
-    if (MODEL == MODEL_RICHARDS) return PF > 1 ? 7 : LH_RHS_WAVES_PER_SIMD; // a deeper ring costs registers
-    // (the Float32 coupled tendency + step bound needs ~90 VGPRs: held to 72 it spills 18 values
-    // per level to scratch and runs 0.34 instead of 0.2x ms on 1e6 x 64)
-    if (f32_coupled_vgpr_constants<FT, MODEL, FACTORS, PERCOL, M, MODE>()) return sizeof(FT) == 4 ? (MODE == 4 ? LH_F32C_DT_WAVES : 7) : 1;
-    if (sizeof(FT) == 4) return (MODE == 4 && MODEL == MODEL_COUPLED) ? LH_F32C_DT_WAVES_SGPR : LH_RHS_WAVES_PER_SIMD; // coupled/heat Float32
+    // Richards with ice: a deeper ring costs registers
+    if (RICHARDS && PF > 1) return 7;
+    if (RICHARDS) return 8;
+    // coupled tendency with its column constants in VGPRs (f32_coupled_vgpr_constants): Float64 unconstrained ...
+    if (MODEL == MODEL_COUPLED && (MODE == 0 || MODE == 4) && F64) return 1;
+    // ... Float32 with the step bound needs ~90 VGPRs (86 unconstrained): held to 72 it spills 18 values per
+    // level to scratch and runs 0.34 instead of 0.2x ms on 1e6 x 64; 5 waves, see f32_coupled_vgpr_constants
+    if (MODEL == MODEL_COUPLED && MODE == 4) return 5;
+    // ... Float32 plain tendency: 72 rather than 64 VGPRs remove every spill (see rhs_kernel)
+    if (MODEL == MODEL_COUPLED && MODE == 0) return 7;
+    // the other Float32 heat / coupled kernels (heat-only in every mode, the coupled fused stages)
+    if (!F64) return 8;
+    // ... and the Float64 ones keep what they need
     return 1;
 }
 
@@ -122,42 +101,7 @@ constexpr int rhs_min_waves() {
     return WAVES >= 8 ? 8 : (WAVES >= 6 ? 6 : (WAVES >= 4 ? 4 : (WAVES >= 2 ? 2 : 1)));
 }
 
-// trips of the level loop (PF levels each) the compiler is told to unroll (0: its own choice)
-#ifndef LH_RHS_OUTER_UNROLL
-#define LH_RHS_OUTER_UNROLL 0
-#endif
-constexpr int RHS_OUTER_UNROLL = LH_RHS_OUTER_UNROLL;
-
 // ----------------------------------------------------------------- helpers
-
-// native clang vectors (the nontemporal builtins do not take HIP_vector_type)
-template <typename FT, int N> struct Vec;
-template <> struct Vec<double, 1> { using type = double; };
-template <> struct Vec<double, 2> { typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct Vec<float, 1> { using type = float; };
-template <> struct Vec<float, 2> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct Vec<float, 4> { typedef float type __attribute__((ext_vector_type(4))); };
-template <> struct Vec<double, 4> { typedef double type __attribute__((ext_vector_type(4))); };
-
-template <typename FT, int N, bool NT = false>
-__device__ __forceinline__ void vload(const FT* p, FT (&out)[N]) {
-    using V = typename Vec<FT, N>::type;
-    V v = NT ? __builtin_nontemporal_load(reinterpret_cast<const V*>(p))
-             : *reinterpret_cast<const V*>(p);
-    const FT* e = reinterpret_cast<const FT*>(&v);
-#pragma unroll
-    for (int j = 0; j < N; ++j) out[j] = e[j];
-}
-template <typename FT, int N, bool NT = false>
-__device__ __forceinline__ void vstore(FT* p, const FT (&in)[N]) {
-    using V = typename Vec<FT, N>::type;
-    V v;
-    FT* e = reinterpret_cast<FT*>(&v);
-#pragma unroll
-    for (int j = 0; j < N; ++j) e[j] = in[j];
-    if (NT) __builtin_nontemporal_store(v, reinterpret_cast<V*>(p));
-    else *reinterpret_cast<V*>(p) = v;
-}
 
 // Row access through a buffer descriptor: a uniform row pointer (SGPRs) plus a
 // 32-bit lane byte offset -- no 64-bit vector address arithmetic, and loads or
@@ -270,18 +214,9 @@ constexpr bool robust_shape_exists() { return !CFG::NT && !CFG::SEG; }
 // MODE: MathLibm checks the tendency itself (mode 0); the fused stages and the step bound have no such build.
 template <typename M, int MODE>
 constexpr bool rhs_mode_exists() { return M::is_production || MODE == 0; }
-#ifdef LH_TUNING_VARIANTS
-// tuning builds (LH_TUNE cpl= pf= nt=): the launch shapes worth measuring -- plain access only for one
-// column per lane, prefetch deeper than 2 only there too
-constexpr bool tuning_shape_exists(int cpl, int pf, bool nt) {
-    if (pf < 1) return false;
-    if (!nt) return cpl == 1 && pf <= 2;
-    return (cpl == 1 && pf <= 4) || ((cpl == 2 || cpl == 4) && pf <= 2);
-}
-#endif
 template <typename FT, int MODEL, bool FACTORS, bool PERCOL, typename CFG, typename M, int MODE, bool NOICE = false, bool VGF = true>
-__global__ void __launch_bounds__((rhs_max_threads<M, rhs_waves_per_simd<FT, MODEL, FACTORS, PERCOL, M, CFG::PF, MODE, NOICE, CFG::CPL>()>()),
-                                  (rhs_min_waves<M, rhs_waves_per_simd<FT, MODEL, FACTORS, PERCOL, M, CFG::PF, MODE, NOICE, CFG::CPL>()>()))
+__global__ void __launch_bounds__((rhs_max_threads<M, rhs_waves_per_simd<FT, MODEL, FACTORS, PERCOL, M, CFG::PF, MODE, NOICE>()>()),
+                                  (rhs_min_waves<M, rhs_waves_per_simd<FT, MODEL, FACTORS, PERCOL, M, CFG::PF, MODE, NOICE>()>()))
 rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, const Planes<FT> BASE,
            const Planes<FT> OUT, const FT dt_value, const FT* __restrict__ dt_device) {
     constexpr bool WATER = (MODEL != MODEL_HEAT);
@@ -302,23 +237,14 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
             if (FACTORS) { vr(P.gamma); vr(P.T_ref_visc); vr(P.Omega); }
         }
     }
-#ifndef LH_F64_FACTORS_PARTIAL_PIN
-#define LH_F64_FACTORS_PARTIAL_PIN 3
-#endif
     // The Float64 tendency with conductivity factors stays at 4 waves per SIMD (128 registers) with the
     // uniforms in the SGPR file and its spills (see rhs_waves_per_simd) -- but the three constants every
     // cell's T and rho_e_l K use fit beside them: 52 -> fewer v_readlane per two cells, f3c64 0.560 ->
-    // 0.546 ms (same-process A/B; five or eight pinned: no further gain)
-#ifndef LH_F64_FACTORS_PARTIAL_PIN_STAGES
-#define LH_F64_FACTORS_PARTIAL_PIN_STAGES 0 // (the fused stages carry more state: the same pinning costs them a wave, 0.64 -> 0.81 ms)
-#endif
-    if constexpr (LH_F64_FACTORS_PARTIAL_PIN > 0 && heat_vgpr_constants<FT, MODEL, FACTORS, PERCOL, M, NOICE>() &&
-                  (MODE == 0 || (LH_F64_FACTORS_PARTIAL_PIN_STAGES && MODE != 4)) &&
-                  FACTORS && !PERCOL) {
+    // 0.546 ms (same-process A/B; five -- rhocp_i, rho_i too -- or eight -- LH_f0, gamma, Omega too -- pinned: no
+    // further gain).  MODE 0 only: the fused stages carry more state, the same pinning costs them a wave, 0.64 -> 0.81 ms.
+    if constexpr (heat_vgpr_constants<FT, MODEL, FACTORS, PERCOL, M, NOICE>() && MODE == 0 && FACTORS && !PERCOL) {
         auto vr = [](FT& x) { asm volatile("" : "+v"(x)); };
         vr(P.rho_c_ds); vr(P.rhocp_l); vr(P.T_ref);
-        if (LH_F64_FACTORS_PARTIAL_PIN >= 5) { vr(P.rhocp_i); vr(P.rho_i); }
-        if (LH_F64_FACTORS_PARTIAL_PIN >= 8) { vr(P.LH_f0); vr(P.gamma); vr(P.Omega); }
     }
     constexpr int CPL = CFG::CPL, PF = CFG::PF;
     constexpr bool NT = CFG::NT;
@@ -371,15 +297,9 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
     // 32-bit BYTE offset of this lane inside a plane row (lh_create bounds a row to < 4 GiB)
     const unsigned lane_byte = (unsigned)col0 * (unsigned)sizeof(FT);
     const unsigned row_bytes = (unsigned)(stride * (int64_t)sizeof(FT));
-    constexpr bool BUF = (sizeof(FT) * CPL == 8); // production shapes: one 8-byte access per lane
-    auto rload = [&](const FT* row, FT (&out)[CPL]) {
-        if constexpr (BUF) bload<FT, CPL, NT>(row, row_bytes, lane_byte, out);
-        else vload<FT, CPL, NT>(row + col0, out);
-    };
-    auto rstore = [&](FT* row, const FT (&in)[CPL]) {
-        if constexpr (BUF) bstore<FT, CPL, NT>(row, row_bytes, lane_byte, in);
-        else vstore<FT, CPL, NT>(row + col0, in);
-    };
+    // (one 8-byte access per lane: CPL = 1 Float64, 2 Float32)
+    auto rload = [&](const FT* row, FT (&out)[CPL]) { bload<FT, CPL, NT>(row, row_bytes, lane_byte, out); };
+    auto rstore = [&](FT* row, const FT (&in)[CPL]) { bstore<FT, CPL, NT>(row, row_bytes, lane_byte, in); };
 
     // uniform row pointers (level 0); HEAT reads the prescribed water fields from
     // Ya (right_hand_side.jl:200-201); fused stages read theta_i from BASE
@@ -532,9 +452,6 @@ rhs_kernel(const DevParams<FT> P0, const Planes<FT> IN, const Planes<FT> AUX, co
         }
     };
 
-#if LH_RHS_OUTER_UNROLL > 0
-#pragma unroll RHS_OUTER_UNROLL
-#endif
     for (int i0 = i_first; i0 < i_end; i0 += PF) {
 #pragma unroll
       for (int k = 0; k < PF; ++k) {
@@ -1573,7 +1490,7 @@ static void launch_rhs_mode(const DevParams<FT>& P, const Planes<FT>& in, const 
         if constexpr (rhs_mode_exists<M, MODE>()) {
             constexpr auto kernel = rhs_kernel<FT, MODEL, FACTORS, PERCOL, CFG, M, MODE, NOICE, VGF>;
             // workgroup size: the kernel's own (see rhs_max_threads) unless LH_TUNE block= asks for less
-            constexpr int kmax = rhs_max_threads<M, rhs_waves_per_simd<FT, MODEL, FACTORS, PERCOL, M, CFG::PF, MODE, NOICE, CFG::CPL>()>();
+            constexpr int kmax = rhs_max_threads<M, rhs_waves_per_simd<FT, MODEL, FACTORS, PERCOL, M, CFG::PF, MODE, NOICE>()>();
             const int block = (block_req > 0 && block_req <= kmax) ? block_req : kmax;
             const int64_t lanes = (P.ncols + CFG::CPL - 1) / CFG::CPL;
             dim3 g = grid_for(lanes, block), b(block);
@@ -1597,23 +1514,6 @@ static void launch_rhs_model(const DevParams<FT>& P, const Planes<FT>& in, const
     using CFG = typename DefaultCfg<FT>::type;
     const int block = tune.block; // 0: the kernel's own workgroup size
     const bool ni = noice && noice_exists<M>(factors);
-#ifdef LH_TUNING_VARIANTS
-    // tuning builds: alternative columns-per-lane / prefetch depth for the plain tendency kernels
-    // (always VGF = true, whatever vg_fast_all says)
-    if (!factors && !percol && mode == 0 && M::is_production && (tune.cpl > 0 || tune.pf > 0)) {
-        const bool ntv = tune.nt >= 0 ? tune.nt != 0 : true;
-        const int cplv = tune.cpl > 0 ? tune.cpl : CFG::CPL, pfv = tune.pf > 0 ? tune.pf : CFG::PF;
-        if (tuning_shape_exists(cplv, pfv, ntv)) {
-            with_int(int_list<1, 2, 4>{}, cplv, [&](auto c) { with_int(int_list<1, 2, 3, 4>{}, pfv, [&](auto f) { with_bool(ntv, [&](auto n) { with_bool(ni, [&](auto i) {
-                constexpr int C = decltype(c)::value, F = decltype(f)::value;
-                constexpr bool N = decltype(n)::value, NI = decltype(i)::value;
-                if constexpr (tuning_shape_exists(C, F, N) && (!NI || noice_exists<M>(false)))
-                    launch_rhs_mode<FT, MODEL, false, false, KCfg<C, F, N>, M, NI, true>(P, in, aux, base, out, dt, dt_dev, 0, block, s);
-            }); }); }); });
-            return;
-        }
-    }
-#endif
     // Nontemporal access when the launch streams more than the 256 MiB Infinity
     // Cache can hold (measured +4 % on 1e6 x 64 columns); plain access for small
     // ensembles whose planes stay cache-resident between launches.

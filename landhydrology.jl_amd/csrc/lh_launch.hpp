@@ -9,16 +9,14 @@ enum { MATH_FAST = 0, MATH_LIBM = 1 };
 template <int CPL_, int PF_, bool NT_, bool SEG_ = false> struct KCfg;
 // production launch shape per working type (chosen by measurement)
 template <typename FT> struct DefaultCfg;
-#ifndef LH_PF64
-#define LH_PF64 2 // levels in flight ahead of the one computed (Float64): -2..3 % against 1 (profiles/round1_tune_prefetch.txt)
-#endif
-template <> struct DefaultCfg<double> { using type = KCfg<1, LH_PF64, false>; };
+// (Float64: 2 levels in flight ahead of the one computed, -2..3 % against 1, profiles/round1_tune_prefetch.txt)
+template <> struct DefaultCfg<double> { using type = KCfg<1, 2, false>; };
 template <> struct DefaultCfg<float> { using type = KCfg<2, 1, false>; };
 
-// run-time launch overrides (LH_TUNE environment variable; tuning builds only
-// honour cpl/pf/nt, every build honours block)
+// run-time launch overrides (LH_TUNE environment variable, lh_set_tuning): one field per key parse_tune scans for
 struct Tune {
-    int block = 0, cpl = 0, pf = 0, nt = -1;
+    int block = 0; // threads per workgroup of the column kernel (0: the kernel's own, see rhs_max_threads)
+    int nt = -1;   // nontemporal global access (-1: by the bytes the launch streams, see launch_rhs_model)
     int pad = -1; // plane address stagger in bytes (state allocation)
     int arena = 0; // plane slots per device allocation (0 = default)
     int rowpad = -1; // extra elements per plane row (-1 = library default)
@@ -30,9 +28,8 @@ struct Tune {
     int place_mem = 0;  // lh_tune_placement: transient memory bound, percent of free memory (0 = 25)
     int zero = 1;    // use the states' known-zero plane bits (0: always read theta_i and store d theta_i = 0)
     int vgfast = 1;  // Float64: integer-exponent 2^(.) in the water closures when every column allows it (0: v_ldexp form always)
-    // lh_integrate_trbdf2: the stage Newton test kappa in units of 1e-4, its iteration
-    // cap, and (tuning builds) the error solve's matrix (0: J re-formed at Y_1, 1: stage 2's last factorisation)
-    int trk = 0, trn = 0, trf = 0;
+    // lh_integrate_trbdf2: the stage Newton test kappa in units of 1e-4 and its iteration cap
+    int trk = 0, trn = 0;
 };
 
 // mode 0: tendency into `out`; 4: tendency + step bound; 1..3, 5: fused SSPRK33 stages (see rhs_kernel)

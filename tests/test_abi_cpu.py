@@ -197,3 +197,45 @@ def test_julia_shim_ccalls_match_the_abi(pkg):
     assert "upload!(Yad, :T" in body and "upload!(Yad, :ϑ_l" in body and "aux_mask(model)" in body
     # finalizers: a state never calls into a destroyed context
     assert "s.ens.ctx != C_NULL" in text and "e.ctx = C_NULL" in text
+
+
+def test_tune_keys_fields_and_document_agree():
+    """LH_TUNE, checked as text: the keys parse_tune scans for, the fields of struct Tune and the keys
+    INTEGRATION.md section 4c documents are one set -- a key without a field, a field nothing sets and
+    an undocumented knob are all errors.  And the product source has one configuration: no
+    LH_TUNING_VARIANTS build, and no `#ifndef LH_X / #define LH_X <default>` override guard (an
+    experiment is a variant library built from another source tree, tools/build_variant.sh).
+    `#ifndef LH_TU_MODEL`, which defines nothing, only tells the model translation units from the
+    common one."""
+    csrc = os.path.join(g.PKG_DIR, "csrc")
+    strip = lambda s: re.sub(r"//[^\n]*|/\*.*?\*/", "", s, flags=re.S)
+
+    api = open(os.path.join(csrc, "lh_api.hip")).read()
+    body = api[api.index("void parse_tune(Tune& tu, const char* t) {"):]
+    body = strip(body[:body.index("\n}\n")])
+    scanned = set(re.findall(r'strstr\([^,]+,\s*"([a-z_]+)="\)', body))
+    assigned = set(re.findall(r"\btu\.([a-z_]+)\s*=", body))
+    assert scanned == assigned, (sorted(scanned), sorted(assigned))
+
+    launch = open(os.path.join(csrc, "lh_launch.hpp")).read()
+    struct = launch[launch.index("struct Tune {"):]
+    struct = strip(struct[:struct.index("};")])
+    fields = set()
+    for decl in re.findall(r"\bint\s+([^;]+);", struct):
+        fields |= {d.split("=")[0].strip() for d in decl.split(",")}
+
+    doc = open(os.path.join(ROOT, "INTEGRATION.md"), encoding="utf-8").read()
+    sec = doc[doc.index("## 4c."):]
+    sec = sec[:sec.index("\n## ", 1)]
+    documented = set(re.findall(r"`([a-z_]+)=", sec))
+
+    assert len(scanned) >= 15
+    assert scanned == fields, sorted(scanned ^ fields)
+    assert scanned == documented, sorted(scanned ^ documented)
+
+    for f in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, f), errors="ignore").read()
+        assert "LH_TUNING_VARIANTS" not in text, f
+        for m in re.finditer(r"^[ \t]*#[ \t]*ifndef[ \t]+(LH_\w+)[^\n]*\n\s*#[ \t]*define[ \t]+(\w+)(.*)$", text, flags=re.M):
+            include_guard = m.group(1) == m.group(2) and not strip(m.group(3)).strip() and not text[:m.start()].strip(" \t\n")
+            assert include_guard, f"{f}: compile-time override guard {m.group(1)}"

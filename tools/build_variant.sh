@@ -1,7 +1,8 @@
 #!/bin/bash
 # Build an experimental variant of the library next to the product one, for
 # same-process A/B timing with tools/ab_libs.py.
-# usage: tools/build_variant.sh <name> [extra hipcc flags ...]
+# usage: [SRC=<tree with the variant's *.hip and *.hpp>] tools/build_variant.sh <name> [extra hipcc flags ...]
+# (SRC defaults to the product's csrc/: an experiment lives in a copy of it, not behind a switch in the product)
 set -e
 name=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd)

@@ -104,7 +104,7 @@ def probe(case, T, dt_ie, dt_fine, rtols):
 
 
 def variants(case, T, dt_fine, tunes, rtol=1e-4):
-    """TR-BDF2 at reltol rtol under each LH_TUNE string (trf= error-solve matrix, trk= Newton test in 1e-4,
+    """TR-BDF2 at reltol rtol under each LH_TUNE string (trk= Newton test in 1e-4,
     trn= Newton cap; read when the context is created): ms per simulated second, steps, error."""
     out = []
     saved = os.environ.get("LH_TUNE")
@@ -159,10 +159,9 @@ def main():
         sd = sd.value
     rows = probe(c2, 20 * sd, 10 * sd, sd / 4, (1e-3, 1e-4, 1e-5))
     rows += probe(bonan(n_bo), 1200.0, 0.5, 0.25, (1e-3, 1e-4, 1e-5))
-    # the error solve's matrix and the stage Newton's test and cap (defaults: trf=0, trk=100, trn=10), and the
-    # lane divergence of an ensemble whose columns differ (per-column van Genuchten parameters)
-    # (trf=1 takes effect in a `make TUNING=1` library only; the product compiles the re-formed J alone)
-    tunes = ("", "trf=1", "trk=30", "trk=300", "trn=6", "trn=20")
+    # the stage Newton's test and cap (defaults: trk=100, trn=10), and the lane divergence of an ensemble
+    # whose columns differ (per-column van Genuchten parameters)
+    tunes = ("", "trk=30", "trk=300", "trn=6", "trn=20")
     rows += variants(c2, 20 * sd, sd / 4, tunes)
     rows += variants(bonan(n_bo), 1200.0, 0.25, tunes)
     c5 = W.make_case("c5_percol_f64", ncols=n_c2)
@@ -171,7 +170,7 @@ def main():
         sd5 = C.c_double()
         F.check(gm.L.lh_stable_dt(gm.ctx, Y, Ya, 0.5, C.byref(sd5)), gm.ctx)
         sd5 = sd5.value
-    rows += variants(c5, 20 * sd5, sd5 / 4, ("", "trf=1"))
+    rows += variants(c5, 20 * sd5, sd5 / 4, ("",))
     path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "trbdf2_probe.jsonl")
     with open(path, "w") as f:
         for r in rows:

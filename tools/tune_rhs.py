@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Time lh_rhs for a list of launch shapes (LH_TUNE) in ONE process, interleaved
-rounds (cdna guide rule 24).  Needs a library built with `make TUNING=1` for the
-cpl/pf/nt variants; block= works in every build.
-usage: tools/tune_rhs.py [workload] [cfg ...]      cfg like "block=128,pf=2,nt=1"
+rounds (cdna guide rule 24): the block= / nt= sweep, on separately allocated models with
+their own pad= (PADS=0,256,...).  A launch shape the library does not have (columns per
+lane, prefetch depth) is a variant library: tools/build_variant.sh + tools/ab_libs.py.
+usage: tools/tune_rhs.py [workload] [cfg ...]      cfg like "block=128,nt=1"
 """
 import ctypes as C
 import os
@@ -15,9 +16,7 @@ import bench
 import parity_cases as pc
 
 workload = sys.argv[1] if len(sys.argv) > 1 else "c2"
-cfgs = sys.argv[2:] or ["", "block=128", "block=64", "pf=2", "pf=3", "pf=4", "nt=1", "pf=2,nt=1",
-                        "pf=4,nt=1", "cpl=2", "cpl=2,pf=2", "cpl=2,nt=1", "cpl=2,pf=2,nt=1",
-                        "block=128,pf=2", "block=128,cpl=2,pf=2"]
+cfgs = sys.argv[2:] or ["", "block=128", "block=64", "nt=0", "nt=1", "block=128,nt=1"]
 ncols = int(os.environ.get("NCOLS", "1000000"))
 case = bench.build_case(workload, ncols, 0)
 nlev = case.om.nlev
