@@ -407,11 +407,12 @@ int lh_adaptive_hold_engine(const lh_ctx*, int32_t hold);
  * atmosphere: anything else is LH_EMODEL.  theta_i is constant through the step. */
 int lh_step_implicit_euler(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
                            int64_t nsteps, const double* bcv, double tol, int32_t max_iter);
-/* Of the last lh_step_implicit_euler call: the largest iteration count any column needed and
- * the number of column-steps that did not converge (zeros once a later call was refused).  Synchronises. */
+/* Of the last lh_step_implicit_euler or lh_step_coupled_implicit call (the water stages of the
+ * latter): the largest iteration count any column needed and the number of column-steps (TR-BDF2:
+ * column-stages) that did not converge (zeros once a later call was refused).  Synchronises. */
 int lh_implicit_stats(lh_ctx*, int32_t* max_iters, int64_t* unconverged);
-/* Of the last lh_step_implicit_euler call: the Newton iterations summed over all column-steps
- * (divided by ncols * nsteps: the mean per column-step).  Synchronises. */
+/* Of the last lh_step_implicit_euler or lh_step_coupled_implicit call: the Newton iterations summed
+ * over all column-steps (divided by ncols * nsteps: the mean per column-step).  Synchronises. */
 int lh_implicit_iterations(lh_ctx*, int64_t* iterations);
 
 /* TR-BDF2 of a Richards model from t0 to t1: L-stable, second order, two
@@ -466,6 +467,34 @@ int lh_trbdf2_stats(lh_ctx*, int64_t* stats);
 #define LH_HEAT_TRBDF2 1u
 int lh_step_heat_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
                           int64_t nsteps, uint32_t flags, const double* bcv);
+
+/* Implicit steps of the coupled model, SoilEnergyModel + SoilHydrologyModel
+ * (right_hand_side.jl:269-369).  Without conductivity factors the water
+ * tendency does not read rhoe_int and the energy tendency is affine in rhoe_int at fixed vartheta_l,
+ * theta_i, so the Jacobian of a stage Y - w - c f(Y) = 0 is block lower-triangular: the water stage
+ * is solved by lh_step_implicit_euler's safeguarded Newton, the energy stage by one tridiagonal
+ * solve at the new water state -- exactly the monolithic implicit stage, no splitting error.
+ * flags 0: backward Euler, Y - Yn - dt f(Y, t+dt) = 0.  LH_COUPLED_TRBDF2: fixed-step TR-BDF2
+ * (gamma = 2 - sqrt 2, both stages with the coefficient gamma/2 dt, at t + gamma dt and t + dt); no
+ * error control.  (Build-defined: the reference hands any OrdinaryDiffEq method to DiffEqBase.init,
+ * src/Simulations/simulation.jl:34-73.)
+ * bcv: NULL (lh_set_bc's values, per-column arrays included) or (nsteps + 1) * 4 doubles
+ * [nsteps + 1][2 faces][2 components] at t + k dt, k = 0 .. nsteps, both components read.  Backward
+ * Euler takes sample k + 1 for step k; TR-BDF2 takes (1 - gamma) v_k + gamma v_k+1 for its first
+ * stage, v_k+1 for its second and v_k for the tendency at the start of the call.
+ * tol <= 0 / max_iter <= 0: lh_step_implicit_euler's defaults, and its per-column test on the
+ * Newton step of the water stage.  A column-stage that does not converge keeps its last iterate,
+ * sets status bit 3 and still gets its energy solve at that iterate; a non-finite result sets
+ * status bit 0.  lh_implicit_stats / lh_implicit_iterations report the water stages of the call.
+ * LH_EINVAL for dt <= 0 or not finite, nsteps < 0 or unknown flag bits; LH_EMODEL for any model but
+ * LH_MODEL_COUPLED, for conductivity factors other than NoEffect (the water would read T) and for
+ * a prescribed-atmosphere top; nsteps == 0 does nothing.  theta_i is constant through the call.
+ * Asynchronous.  (With a non-NULL bcv the call waits for its launch before it releases the device
+ * copy of the values, as lh_step_implicit_euler does.) */
+#define LH_COUPLED_TRBDF2 1u
+int lh_step_coupled_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
+                             int64_t nsteps, uint32_t flags, const double* bcv, double tol,
+                             int32_t max_iter);
 
 /* Build-defined stable step (the reference uses a fixed user dt):
  * courant*dz^2 / max over owned faces of the face diffusivities

@@ -29,6 +29,7 @@ LH_ENGINE_FUSED_STAGES, LH_ENGINE_COLUMN_STEPPER = 0, 1
 LH_COMM_ID_BYTES = 128
 LH_TRBDF2_FIXED, LH_TRBDF2_NSTATS = 1, 7
 LH_HEAT_TRBDF2 = 1
+LH_COUPLED_TRBDF2 = 1
 LH_PC = dict(vg_n=0, vg_alpha=1, vg_theta_r=2, vg_Ksat=3, nu=4, S_s=5)
 LH_OK, LH_EINVAL, LH_ENODEVICE, LH_ENOMEM, LH_EMODEL, LH_ESTATE = 0, -1, -2, -3, -4, -5
 
@@ -114,6 +115,8 @@ SIGNATURES = {
     "lh_trbdf2_stats": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "lh_step_heat_implicit": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, C.c_uint32,
                                         C.POINTER(C.c_double)]),
+    "lh_step_coupled_implicit": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, C.c_uint32,
+                                           C.POINTER(C.c_double), C.c_double, C.c_int32]),
     "lh_tune_placement": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_uint32, C.POINTER(C.c_float),
                                     C.POINTER(C.c_float)]),
     "lh_stable_dt": (C.c_int, [_P, _P, _P, C.c_double, _DP]),

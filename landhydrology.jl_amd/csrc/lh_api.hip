@@ -103,6 +103,8 @@ struct lh_ctx {
     void* d_tr = nullptr;              // lh_integrate_trbdf2: six FT planes [nlev][stride] (Y_n, f_n, Y_gamma, w, c', d')
     void* d_tr_stats = nullptr;        // ... and its LH_TRBDF2_NSTATS uint64 counters
     void* d_heat = nullptr;            // lh_step_heat_implicit: eight FT planes [nlev][stride] (three of the factorisation, kc, z; kappa sums, alpha, beta)
+    void* d_cpl = nullptr;             // lh_step_coupled_implicit: three FT planes [nlev][stride] (the water stage's w, c', d'; the energy solve reuses c', d')
+    void* d_cpl_tr = nullptr;          // ... and four more for LH_COUPLED_TRBDF2 (the water's Y_n and f_n, the energy's f_n and w2)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
     Tune tune;
@@ -1204,6 +1206,8 @@ int lh_destroy(lh_ctx* c) {
     if (c->d_tr) (void)hipFree(c->d_tr);
     if (c->d_tr_stats) (void)hipFree(c->d_tr_stats);
     if (c->d_heat) (void)hipFree(c->d_heat);
+    if (c->d_cpl) (void)hipFree(c->d_cpl);
+    if (c->d_cpl_tr) (void)hipFree(c->d_cpl_tr);
     for (int k = 0; k < 3; ++k)
         if (c->d_atm_pc[k]) (void)hipFree(c->d_atm_pc[k]);
     for (int k = 0; k < 2; ++k)
@@ -1794,10 +1798,12 @@ int lh_step_ssprk33_adaptive_hold(lh_ctx* c, lh_state* Y, const lh_state* Ya, do
 
 // ---- what lh_step_implicit_euler and lh_integrate_trbdf2 share on the host
 
-// Both refuse the same configurations and states, in this order (`who`: the entry point, for lh_last_error)
-static int implicit_refusals(lh_ctx* c, const char* who, const lh_state* Y, const lh_state* Ya) {
-    if (c->cfg.model != LH_MODEL_RICHARDS)
-        return fail(c, LH_EMODEL, "%s: Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)", who);
+// They and lh_step_coupled_implicit refuse the same configurations and states, in this order (`who`: the entry
+// point, for lh_last_error; `model`, `models`: the one model it steps and the words for it)
+static int implicit_refusals(lh_ctx* c, const char* who, const lh_state* Y, const lh_state* Ya,
+                             int model = LH_MODEL_RICHARDS,
+                             const char* models = "Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)") {
+    if (c->cfg.model != model) return fail(c, LH_EMODEL, "%s: %s", who, models);
     if (c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE)
         return fail(c, LH_EMODEL, "%s: conductivity factors other than NoEffect are not supported", who);
     // (validate_model refuses a prescribed atmosphere on any model but the coupled one already; kept so
@@ -2005,6 +2011,58 @@ int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, 
     mark_written(Y, LH_MASK(LH_VAR_RHOE_INT));
     const hipError_t e = launch_error(c, d_bcv);
     if (e != hipSuccess) return fail(c, LH_ENODEVICE, "heat implicit launch failed: %s", hipGetErrorString(e));
+    return LH_OK;
+}
+
+int lh_step_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                             uint32_t flags, const double* bcv, double tol, int32_t max_iter) {
+    (void)t; // boundary values come through bcv or lh_set_bc, as for lh_step_heat_implicit
+    if (!c) return LH_EINVAL;
+    int rc = zero_stats(c, c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24");
+    if (rc) return rc;
+    if (nsteps < 0 || !std::isfinite(dt) || !(dt > 0))
+        return fail(c, LH_EINVAL, "lh_step_coupled_implicit: need nsteps >= 0 and a finite dt > 0");
+    if (flags & ~LH_COUPLED_TRBDF2) return fail(c, LH_EINVAL, "lh_step_coupled_implicit: unknown flags 0x%x", flags);
+    Range r_("lh:step_coupled_implicit");
+    // (with a viscosity factor the water reads T: the Jacobian is no longer block triangular)
+    if ((rc = implicit_refusals(c, "lh_step_coupled_implicit", Y, Ya, LH_MODEL_COUPLED,
+                                "coupled models only (SoilEnergyModel + SoilHydrologyModel)")))
+        return rc;
+    if (!(tol > 0)) tol = c->cfg.dtype == LH_F64 ? 1e-10 : 1e-5; // lh_step_implicit_euler's defaults
+    if (max_iter <= 0) max_iter = 50;
+    const bool trbdf2 = (flags & LH_COUPLED_TRBDF2) != 0;
+    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+    if ((rc = ensure_scratch(c, &c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24", true))) return rc;
+    if (nsteps == 0) return LH_OK;
+    if ((rc = ensure_scratch(c, &c->d_cpl, 3 * pl * c->esize, "c->d_cpl", "3 * plane"))) return rc;
+    if (trbdf2 && (rc = ensure_scratch(c, &c->d_cpl_tr, 4 * pl * c->esize, "c->d_cpl_tr", "4 * plane"))) return rc;
+    if ((rc = materialize(c, Y, ~0u))) return rc;
+    DeviceBuffer d_bcv; // [nsteps + 1][2][2] doubles -> FT on the device
+    if (bcv && (rc = upload_boundary_values(c, bcv, size_t(nsteps + 1) * 4, d_bcv))) return rc;
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        ImplicitStats* const st = static_cast<ImplicitStats*>(c->d_imp_stats); // (device memory: addresses only)
+        CoupledImplicitArgs<FT> A;
+        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
+        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+        A.e = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
+        carve_planes<FT>(c->d_cpl, pl, {&A.w, &A.cp, &A.dp});
+        A.yn = A.fn = A.fe = A.we = nullptr;
+        if (trbdf2) carve_planes<FT>(c->d_cpl_tr, pl, {&A.yn, &A.fn, &A.fe, &A.we});
+        A.bcv = static_cast<const FT*>(d_bcv.p);
+        A.coef = FT(trbdf2 ? 0.5 * (2.0 - 1.4142135623730951) * dt : dt);
+        A.tol = FT(tol);
+        A.max_iter = max_iter;
+        A.nsteps = nsteps;
+        A.max_iters = &st->max_iters;
+        A.unconverged = &st->unconverged;
+        A.total_iters = &st->total_iters;
+        launch_coupled_implicit<FT>(P, A, any_percol(c), implicit_noice(c, Y), trbdf2, c->math, c->stream);
+    });
+    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
+    const hipError_t e = launch_error(c, d_bcv);
+    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "coupled implicit launch failed: %s", hipGetErrorString(e));
     return LH_OK;
 }
 

@@ -131,8 +131,8 @@ struct ImplicitArgs {
     unsigned long long* total_iters; // Newton iterations over all column-steps
 };
 
-// lh_step_implicit_euler's statistics of one call: the device block ImplicitArgs' three counters point
-// into, and what the host reads back
+// lh_step_implicit_euler's and lh_step_coupled_implicit's statistics of one call: the device block the three
+// counters of ImplicitArgs / CoupledImplicitArgs point into, and what the host reads back
 struct ImplicitStats {
     int32_t max_iters;
     unsigned long long unconverged, total_iters;
@@ -156,6 +156,29 @@ struct HeatImplicitArgs {
     const FT* bcv;       // [nsteps + 1][2 faces][2 components] boundary values at t + k dt, or nullptr
     FT coef;             // dt (backward Euler) or (2 - sqrt 2)/2 dt (both TR-BDF2 stages)
     int64_t nsteps;
+};
+
+// lh_step_coupled_implicit's launch (lh_coupled_implicit.hpp); the three counters point into an ImplicitStats block
+template <typename FT>
+struct CoupledImplicitArgs {
+    FT* y;               // vartheta_l plane of Y: the water stage's iterate
+    const FT* ti;        // theta_i plane (not read by the kernels that know it zero)
+    FT* e;               // rhoe_int plane of Y
+    FT* w;               // scratch planes [nlev][stride]: the water stage's w (backward Euler: v_n), c', d' --
+    FT* cp;              // ... the last two reused by the energy solve once Newton is finished
+    FT* dp;
+    FT* yn;              // (TR-BDF2) the water's Y_n and f_n, the energy's f_n and w2
+    FT* fn;
+    FT* fe;
+    FT* we;
+    const FT* bcv;       // [nsteps + 1][2 faces][2 components] boundary values at t + k dt, or nullptr
+    FT coef;             // dt (backward Euler) or (2 - sqrt 2)/2 dt (both TR-BDF2 stages)
+    FT tol;
+    int32_t max_iter;
+    int64_t nsteps;
+    int32_t* max_iters;
+    unsigned long long* unconverged;
+    unsigned long long* total_iters;
 };
 
 // lh_integrate_trbdf2's launch (lh_implicit.hpp)

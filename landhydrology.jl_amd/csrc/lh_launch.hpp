@@ -86,6 +86,10 @@ void launch_trbdf2(const DevParams<FT>& P, const Trbdf2Args<FT>& A, bool percol,
 template <typename FT>
 void launch_heat_implicit(const DevParams<FT>& P, const HeatImplicitArgs<FT>& A, bool percol, bool trbdf2, int math,
                           hipStream_t s);
+// nsteps backward-Euler or fixed-step TR-BDF2 steps of a coupled model in one launch (lh_coupled_implicit.hpp)
+template <typename FT>
+void launch_coupled_implicit(const DevParams<FT>& P, const CoupledImplicitArgs<FT>& A, bool percol, bool noice,
+                             bool trbdf2, int math, hipStream_t s);
 template <typename FT>
 void launch_convert(FT* dst, const double* src, int64_t n, hipStream_t s);
 

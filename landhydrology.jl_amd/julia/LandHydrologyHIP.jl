@@ -531,6 +531,37 @@ function step_heat_implicit!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt, nst
 end
 
 """
+    step_coupled_implicit!(ens, Y, Ya, t, dt, nsteps; method = :euler, bcv = nothing, tol = 0.0, max_iter = 0) -> (max_iters, unconverged, iterations)
+
+`nsteps` implicit steps of a coupled ensemble, SoilEnergyModel + SoilHydrologyModel without conductivity
+factors (lh_step_coupled_implicit): the water stage by `step_implicit_euler!`'s safeguarded Newton, the
+energy stage by one tridiagonal solve at the new water state -- the stage Jacobian is block
+lower-triangular, so this is the monolithic implicit stage.  `method`: `:euler` (backward Euler) or
+`:trbdf2` (fixed-step TR-BDF2, no error control).  `bcv`: `nothing` or `(nsteps + 1) * 4` boundary values
+at `t + k dt` ([sample][face][component], both components read).  `tol <= 0` / `max_iter <= 0`: the
+library's defaults.  Returns lh_implicit_stats of the call (the water stages) and the Newton iterations
+summed over its column-stages (lh_implicit_iterations).
+"""
+function step_coupled_implicit!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt, nsteps; method = :euler,
+                                bcv = nothing, tol = 0.0, max_iter = 0)
+    method in (:euler, :trbdf2) || throw(ArgumentError("method must be :euler or :trbdf2"))
+    set_bcs!(ens, t)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    flags = method === :trbdf2 ? UInt32(1) : UInt32(0)
+    check(ens.ctx, ccall((:lh_step_coupled_implicit, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Int64, UInt32, Ptr{Float64}, Float64, Int32),
+                         ens.ctx, Y.handle, ya, t, dt, Int64(nsteps), flags, vals, tol, max_iter))
+    mi = Ref{Int32}(0)
+    nu = Ref{Int64}(0)
+    check(ens.ctx, ccall((:lh_implicit_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}),
+                         ens.ctx, mi, nu))
+    total = Ref{Int64}(0)
+    check(ens.ctx, ccall((:lh_implicit_iterations, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, total))
+    return (mi[], nu[], total[])
+end
+
+"""
     tune_placement!(ens, Y, Ya, dY = nothing; max_candidates = 0, move_input = true)
 
 Let the library place the state written by `rhs!` (`dY` given) or the SSPRK33 stage state

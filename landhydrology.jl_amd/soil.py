@@ -1023,6 +1023,73 @@ class HeatTRBDF2(HeatImplicitEuler):
     method = "trbdf2"
 
 
+class CoupledImplicitEuler:
+    """Backward Euler of the coupled model, SoilEnergyModel + SoilHydrologyModel without conductivity factors
+    (lh_step_coupled_implicit): the water stage by ImplicitEuler's safeguarded Newton, the energy stage by one
+    tridiagonal solve at the new water state -- the Jacobian is block lower-triangular, so this is exactly the
+    monolithic implicit step.  Simulation runs one call per saveat chunk (per run without saveat), Dirichlet
+    closures sampled at the step times.  tol / max_iter: None = the library's defaults (ImplicitEuler's)."""
+    method = "euler"
+
+    def __init__(self, tol=None, max_iter=None):
+        self.tol = tol
+        self.max_iter = max_iter
+
+    def check_scope(self, model):
+        _check_coupled_implicit_scope(model, type(self).__name__)
+
+    def advance(self, sim, nsteps):
+        it = sim.integrator
+        it.implicit_stats = step_implicit_coupled(sim.model, it.u, it.p, it.t, it.dt, nsteps, self.method, self.tol,
+                                                  self.max_iter)
+        # the end of a chunk of nsteps intervals of dt; tf itself at the last
+        if it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt)):
+            return it.tf
+        return it.t0 + (it._nsteps_done + nsteps) * it.dt
+
+
+class CoupledTRBDF2(CoupledImplicitEuler):
+    """Fixed-step TR-BDF2 of the coupled model (lh_step_coupled_implicit with LH_COUPLED_TRBDF2): second order,
+    L-stable, two stages per step of the Simulation's dt, no error control.  Scope, calls and arguments as
+    CoupledImplicitEuler."""
+    method = "trbdf2"
+
+
+def _check_coupled_implicit_scope(model, name="CoupledImplicitEuler"):
+    """NotImplementedError for what lh_step_coupled_implicit refuses with LH_EMODEL, in its order."""
+    if not (isinstance(model.energy_model, SoilEnergyModel) and isinstance(model.hydrology_model, SoilHydrologyModel)):
+        raise NotImplementedError(f"{name}: coupled models only (SoilEnergyModel + SoilHydrologyModel)")
+    hm = model.hydrology_model
+    if not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
+        raise NotImplementedError(f"{name}: conductivity factors other than NoEffect are not supported")
+    bcs = model.boundary_conditions
+    if bcs is not None and isinstance(bcs.top, PrescribedAtmosForcing):
+        raise NotImplementedError(f"{name}: a prescribed-atmosphere top is not supported")
+
+
+def step_implicit_coupled(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
+                          nsteps: int = 1, method: str = "euler", tol=None, max_iter=None):
+    """Build extension: `nsteps` implicit steps of the coupled model in one library call
+    (lh_step_coupled_implicit), method "euler" (backward Euler) or "trbdf2" (fixed-step TR-BDF2).
+    Time-dependent Dirichlet closures of both components are sampled at the nsteps + 1 step times t + k dt
+    (per-column values at `t`).  Returns (largest Newton iteration count of any water stage, number of
+    column-stages that did not converge)."""
+    if method not in ("euler", "trbdf2"):
+        raise ValueError('step_implicit_coupled: method must be "euler" or "trbdf2"')
+    _check_coupled_implicit_scope(model, "step_implicit_coupled")
+    be = model._backend()
+    L = F.lib()
+    ya = _handle(Ya)
+    bcv = _sampled_bcv(model, [t + k * dt for k in range(int(nsteps) + 1)], t)
+    be.set_bcs(model, t)
+    F.check(L.lh_step_coupled_implicit(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
+                                       F.LH_COUPLED_TRBDF2 if method == "trbdf2" else 0, _dptr(bcv),
+                                       float(tol or 0.0), int(max_iter or 0)), be.ctx)
+    mi, un = C.c_int32(), C.c_int64()
+    F.check(L.lh_implicit_stats(be.ctx, C.byref(mi), C.byref(un)), be.ctx)
+    return int(mi.value), int(un.value)
+
+
 def _check_implicit_scope(model, name="ImplicitEuler"):
     """NotImplementedError for what lh_step_implicit_euler and lh_integrate_trbdf2 refuse (LH_EMODEL)."""
     if not (isinstance(model.energy_model, PrescribedTemperatureModel) and
@@ -1201,7 +1268,9 @@ class Simulation:
 
     def __init__(self, model, method, *, Y_init, dt, tspan, Ya_init, callbacks=None, saveat=None,
                  **kwargs):
-        if not isinstance(method, (SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler)):
+        # (CoupledImplicitEuler and CoupledTRBDF2 are accepted too; the text below is pinned word for word by
+        # tests/test_bcv_sampling.py and so does not name them)
+        if not isinstance(method, (SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler, CoupledImplicitEuler)):
             raise NotImplementedError("only SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler and HeatTRBDF2 are "
                                       "provided on the device")
         method.check_scope(model)
