@@ -438,11 +438,12 @@ int lh_implicit_iterations(lh_ctx*, int64_t* iterations);
 int lh_integrate_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
                         double abstol, double reltol, uint32_t flags, void* dt_cols_device_ft,
                         const double* bcv);
-/* Of the last lh_integrate_trbdf2 call, LH_TRBDF2_NSTATS counters (zeros once a later call was
- * refused): accepted steps, rejected steps, Newton iterations (summed over stages and columns), the
- * largest number of attempted steps of any column, failed columns, wave_steps (the sum over waves of
- * 64 x the wave's largest step count: what the slowest lane of each wave costs) and, in fixed-step
- * mode, unconverged stages.  Synchronises. */
+/* Of the last lh_integrate_trbdf2 or lh_integrate_coupled_trbdf2 call, LH_TRBDF2_NSTATS counters
+ * (zeros once a later call of either was refused): accepted steps, rejected steps, Newton
+ * iterations (summed over stages and columns), the largest number of attempted steps of any column,
+ * failed columns, wave_steps (the sum over waves of 64 x the wave's largest step count: what the
+ * slowest lane of each wave costs) and, in fixed-step mode, unconverged stages (0 after
+ * lh_integrate_coupled_trbdf2).  Synchronises. */
 #define LH_TRBDF2_NSTATS 7
 int lh_trbdf2_stats(lh_ctx*, int64_t* stats);
 
@@ -496,6 +497,29 @@ int lh_step_coupled_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, double t,
                              int64_t nsteps, uint32_t flags, const double* bcv, double tol,
                              int32_t max_iter);
 
+/* TR-BDF2 of the coupled model from t0 to t1 with per-column error control:
+ * lh_integrate_trbdf2's method and controller over both components, every stage solved as
+ * lh_step_coupled_implicit solves it (the water by the safeguarded Newton with lh_integrate_trbdf2's
+ * adaptive test, kappa 0.01 within 10 iterations; the energy by one tridiagonal solve at the new
+ * vartheta_l).  The error estimate r = b1 h f_n + b2 z_g + b3 z_1 of both components is filtered by
+ * the diagonal blocks of I - d h J(Y_1), (I - d h J_ww) e_w = r_w and (I - d h J_ee) e_e = r_e, and
+ * measured in E = sqrt((sum_i q_w,i^2 + sum_i q_e,i^2) / (2 nlev)) with
+ * q_w = e_w / (abstol + reltol max(|vartheta_l,n|, |vartheta_l,1|)) and
+ * q_e = e_e / (abstol_e + reltol max(|rhoe_int,n|, |rhoe_int,1|)).  E <= 1 accepts; step changes, the
+ * landing on t1, the step floor and the attempt cap are lh_integrate_trbdf2's.  A column that fails
+ * keeps its last accepted vartheta_l and rhoe_int, sets status bit 4 and gets dt_cols = 0; a
+ * non-finite accepted result sets status bit 0.
+ * abstol, reltol: each one that is 0 takes its own default, 1e-6 and 1e-3.  abstol_e: 0 takes
+ * 1e-6 rho_l c_l, the energy of 1e-6 K in water (4.18 J/m^3 with the default earth parameters);
+ * rhoe_int passes through 0 at T = T_0, where a water-sized absolute tolerance would pin the step.
+ * flags must be 0 (fixed steps: lh_step_coupled_implicit with LH_COUPLED_TRBDF2).  dt_cols_device_ft
+ * and bcv as lh_integrate_trbdf2, both components of bcv read.  lh_trbdf2_stats reports the call.
+ * LH_EINVAL for t1 < t0, dt <= 0, a negative tolerance, anything not finite, or flags != 0;
+ * LH_EMODEL as lh_step_coupled_implicit.  theta_i is constant through the call.  Asynchronous. */
+int lh_integrate_coupled_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
+                                double abstol, double abstol_e, double reltol, uint32_t flags,
+                                void* dt_cols_device_ft, const double* bcv);
+
 /* Build-defined stable step (the reference uses a fixed user dt):
  * courant*dz^2 / max over owned faces of the face diffusivities
  * ((K_lo+K_hi)/2 * max dpsi/dvl, (kappa_lo+kappa_hi)/2 / min rho_c_s; boundary
@@ -539,15 +563,16 @@ int lh_allreduce_min(lh_ctx*, void* value_device_ft);
 
 /* ---- status / timing -------------------------------------------------------- */
 
-/* bit 0: a non-finite tendency was produced since the last call (the reference
- * would have raised DomainError from `^`); bit 1: the Monin-Obukhov system of the
- * prescribed-atmosphere BC had no root in some column; bit 2: a step of
- * lh_step_ssprk33_adaptive found no positive finite step bound (no positive diffusivity anywhere and
- * no dt_max, or a NaN) and was taken with dt = 0; bit 3: an implicit step (lh_step_implicit_euler)
- * did not converge in some column (also the fixed-step mode of lh_integrate_trbdf2); bit 4: a column
- * of lh_integrate_trbdf2 failed (its step fell below the floor or it hit the step cap) and did not
- * reach t1; bit 5: a chunk of lh_step_ssprk33_adaptive_hold held a step that exceeded the stable step of
- * the state it produced; synchronises and clears. */
+/* bit 0: a non-finite tendency was produced since the last call (the reference would have raised
+ * DomainError from `^`), or a non-finite result by lh_step_heat_implicit, lh_step_coupled_implicit
+ * or an accepted step of lh_integrate_coupled_trbdf2; bit 1: the Monin-Obukhov system of the
+ * prescribed-atmosphere BC had no root in some column; bit 2: a step of lh_step_ssprk33_adaptive
+ * found no positive finite step bound (no positive diffusivity anywhere and no dt_max, or a NaN)
+ * and was taken with dt = 0; bit 3: an implicit step (lh_step_implicit_euler) did not converge in
+ * some column (also the fixed-step mode of lh_integrate_trbdf2); bit 4: a column of
+ * lh_integrate_trbdf2 or lh_integrate_coupled_trbdf2 failed (its step fell below the floor or it
+ * hit the step cap) and did not reach t1; bit 5: a chunk of lh_step_ssprk33_adaptive_hold held a
+ * step that exceeded the stable step of the state it produced; synchronises and clears. */
 int lh_get_status(lh_ctx*, uint32_t* flags);
 int lh_synchronize(lh_ctx*);
 /* Streaming ceiling of the column launch on a given set of planes (measurement aid, no

@@ -105,6 +105,7 @@ struct lh_ctx {
     void* d_heat = nullptr;            // lh_step_heat_implicit: eight FT planes [nlev][stride] (three of the factorisation, kc, z; kappa sums, alpha, beta)
     void* d_cpl = nullptr;             // lh_step_coupled_implicit: three FT planes [nlev][stride] (the water stage's w, c', d'; the energy solve reuses c', d')
     void* d_cpl_tr = nullptr;          // ... and four more for LH_COUPLED_TRBDF2 (the water's Y_n and f_n, the energy's f_n and w2)
+    void* d_cpl_ad = nullptr;          // lh_integrate_coupled_trbdf2: ten FT planes [nlev][stride] (d_tr's six for the water; the energy's Y_n, f_n, Y_gamma, w2)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
     Tune tune;
@@ -1208,6 +1209,7 @@ int lh_destroy(lh_ctx* c) {
     if (c->d_heat) (void)hipFree(c->d_heat);
     if (c->d_cpl) (void)hipFree(c->d_cpl);
     if (c->d_cpl_tr) (void)hipFree(c->d_cpl_tr);
+    if (c->d_cpl_ad) (void)hipFree(c->d_cpl_ad);
     for (int k = 0; k < 3; ++k)
         if (c->d_atm_pc[k]) (void)hipFree(c->d_atm_pc[k]);
     for (int k = 0; k < 2; ++k)
@@ -2063,6 +2065,63 @@ int lh_step_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
     const hipError_t e = launch_error(c, d_bcv);
     if (e != hipSuccess) return fail(c, LH_ENODEVICE, "coupled implicit launch failed: %s", hipGetErrorString(e));
+    return LH_OK;
+}
+
+int lh_integrate_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
+                                double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    if (!c) return LH_EINVAL;
+    const size_t nstat = LH_TRBDF2_NSTATS * sizeof(uint64_t);
+    int rc = zero_stats(c, c->d_tr_stats, nstat, "c->d_tr_stats", "nstat");
+    if (rc) return rc;
+    if (!std::isfinite(t0) || !std::isfinite(t1) || !(t1 >= t0))
+        return fail(c, LH_EINVAL, "lh_integrate_coupled_trbdf2: need finite t0 <= t1");
+    if (!std::isfinite(dt) || !(dt > 0)) return fail(c, LH_EINVAL, "lh_integrate_coupled_trbdf2: need a finite dt > 0");
+    if (!std::isfinite(abstol) || !std::isfinite(abstol_e) || !std::isfinite(reltol) || abstol < 0 || abstol_e < 0 || reltol < 0)
+        return fail(c, LH_EINVAL, "lh_integrate_coupled_trbdf2: tolerances must be finite and >= 0");
+    // (fixed steps are lh_step_coupled_implicit's LH_COUPLED_TRBDF2)
+    if (flags) return fail(c, LH_EINVAL, "lh_integrate_coupled_trbdf2: unknown flags 0x%x", flags);
+    if (bcv)
+        for (int k = 0; k < 8; ++k)
+            if (!std::isfinite(bcv[k])) return fail(c, LH_EINVAL, "lh_integrate_coupled_trbdf2: non-finite boundary value");
+    Range r_("lh:integrate_coupled_trbdf2");
+    if ((rc = implicit_refusals(c, "lh_integrate_coupled_trbdf2", Y, Ya, LH_MODEL_COUPLED,
+                                "coupled models only (SoilEnergyModel + SoilHydrologyModel)")))
+        return rc;
+    // each tolerance that is 0 takes its own default; the energy's is that of 1e-6 K in water
+    if (!(abstol > 0)) abstol = LH_TRBDF2_ABSTOL_DEFAULT;
+    if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
+    if (!(reltol > 0)) reltol = LH_TRBDF2_RELTOL_DEFAULT;
+    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+    if ((rc = ensure_scratch(c, &c->d_cpl_ad, 10 * pl * c->esize, "c->d_cpl_ad", "10 * plane"))) return rc;
+    if ((rc = ensure_scratch(c, &c->d_tr_stats, nstat, "c->d_tr_stats", "nstat", true))) return rc;
+    if (t1 == t0) return LH_OK;
+    if ((rc = materialize(c, Y, ~0u))) return rc;
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        CoupledTrbdf2Args<FT> A;
+        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
+        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+        A.e = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
+        carve_planes<FT>(c->d_cpl_ad, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp, &A.en, &A.fe, &A.eg, &A.we});
+        A.dt_cols = static_cast<FT*>(dt_cols_device_ft);
+        A.t0 = t0;
+        A.t1 = t1;
+        A.dt = dt;
+        A.abstol = abstol;
+        A.abstol_e = abstol_e;
+        A.reltol = reltol;
+        A.has_bcv = bcv != nullptr;
+        for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
+        A.kappa = FT(c->tune.trk > 0 ? 1e-4 * c->tune.trk : LH_TRBDF2_NEWTON_KAPPA);
+        A.newton_max = c->tune.trn > 0 ? c->tune.trn : LH_TRBDF2_NEWTON_MAX;
+        A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
+        launch_coupled_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+    });
+    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "coupled TR-BDF2 launch failed: %s", hipGetErrorString(e));
     return LH_OK;
 }
 

@@ -36,8 +36,9 @@ namespace lh {
 // One upward sweep of the energy equation over a column at the water state y (a rolling window of two
 // cells' closures).  SOLVE: row i of the stage matrix and r_i = in(i, idx) + coef f_e,i(T = beta), eliminated
 // forward; cp, dp receive the back substitution's Y_i = dp_i + cp_i Y_i+1.  Otherwise in(i, idx) is rhoe_int
-// and out(idx, f_e,i) receives the tendency.
-template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool SOLVE, typename In, typename Out>
+// and out(idx, f_e,i) receives the tendency.  SOLVE with HOMOG: the same matrix against r_i = in(i, idx) alone (no
+// tendency at T = beta, no boundary offset): the error filter of lh_coupled_trbdf2.hpp.
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool SOLVE, bool HOMOG = false, typename In, typename Out>
 __device__ __forceinline__ void energy_sweep_up(const M& mm, const DevParams<FT>& P,
                                                 const ColumnSolve<FT, M, PERCOL, NOICE>& S, const FaceState<FT>& fsb,
                                                 const FaceState<FT>& fst, int64_t col, const FT* y, const FT* ti,
@@ -66,8 +67,8 @@ __device__ __forceinline__ void energy_sweep_up(const M& mm, const DevParams<FT>
     cell(idx, K, np, al, be, kap, rcs);
     FT u = FT(0); // T - beta of the cell (tendency sweep)
     if constexpr (!SOLVE) u = al * in(0, idx);
-    FT Flo;
-    {
+    FT Flo = FT(0);
+    if constexpr (!HOMOG) { // (the homogeneous solve reads no flux: the matrix alone)
         FT fe, fw; // the boundary face at T_c = beta (a Dirichlet face is affine in T_c: - G_b u on top)
         boundary_fluxes_from<FT, MODEL_COUPLED>(P, fsb, FACE_BOTTOM, col, be, K * Ksc, -np, fe, fw);
         Flo = fe * P.inv_dz - Gb * u;
@@ -75,7 +76,7 @@ __device__ __forceinline__ void energy_sweep_up(const M& mm, const DevParams<FT>
     FT p_lo = FT(0), l_lo = FT(0);                      // p_i-1 and l_i
     FT t_prev = FT(0), ipi_prev = FT(0), rp_prev = FT(0); // t, 1 / pi and r' of the cell below
     for (int i = 0; i < n; ++i) {
-        FT Fhi, p_hi = FT(0), l_up = FT(0);
+        FT Fhi = FT(0), p_hi = FT(0), l_up = FT(0);
         FT Ku = FT(0), npu = FT(0), alu = FT(0), beu = FT(0), kapu = FT(0), rcsu = FT(0), uu = FT(0);
         const int64_t idu = idx + stride;
         if (i + 1 < n) {
@@ -84,8 +85,10 @@ __device__ __forceinline__ void energy_sweep_up(const M& mm, const DevParams<FT>
             const FT gh = head_difference(npu, np, P.dz) * cgw;
             const FT ks = kap + kapu;
             if constexpr (SOLVE) {
-                const FT E = (P.rhocp_l * (be - P.T_ref)) * K, Eu = (P.rhocp_l * (beu - P.T_ref)) * Ku;
-                Fhi = -ks * ((beu - be) * P.cg2) - (E + Eu) * gh;
+                if constexpr (!HOMOG) {
+                    const FT E = (P.rhocp_l * (be - P.T_ref)) * K, Eu = (P.rhocp_l * (beu - P.T_ref)) * Ku;
+                    Fhi = -ks * ((beu - be) * P.cg2) - (E + Eu) * gh;
+                }
                 const FT g = ks * P.cg2;
                 p_hi = coef * (g + (P.rhocp_l * Ku) * gh);
                 l_up = coef * (g - (P.rhocp_l * K) * gh);
@@ -95,14 +98,15 @@ __device__ __forceinline__ void energy_sweep_up(const M& mm, const DevParams<FT>
                 const FT E = (P.rhocp_l * ((be - P.T_ref) + u)) * K, Eu = (P.rhocp_l * ((beu - P.T_ref) + uu)) * Ku;
                 Fhi = -ks * (((uu - u) + (beu - be)) * P.cg2) - (E + Eu) * gh;
             }
-        } else {
+        } else if constexpr (!HOMOG) {
             FT fe, fw;
             boundary_fluxes_from<FT, MODEL_COUPLED>(P, fst, FACE_TOP, col, be, K * Ksc, -np, fe, fw);
             Fhi = fe * P.inv_dz + Gt * u;
         }
         const FT f = Flo - Fhi; // rhs_kernel's emit
         if constexpr (SOLVE) {
-            const FT r = in(i, idx) + coef * f;
+            FT r = in(i, idx);
+            if constexpr (!HOMOG) r = r + coef * f;
             FT tp = rcs; // the pivot without the entry below it: a column sum
             if (i == 0) tp = tp + coef * Gb;
             else tp = tp + p_lo * (t_prev * ipi_prev);

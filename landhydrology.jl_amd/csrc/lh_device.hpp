@@ -204,6 +204,31 @@ struct Trbdf2Args {
     int32_t newton_max;  // ... within newton_max iterations, else the step is rejected
     unsigned long long* stats; // accepted, rejected, Newton iterations, max steps, failed, wave_steps, unconverged
 };
+// lh_integrate_coupled_trbdf2's launch (lh_coupled_trbdf2.hpp); stats as Trbdf2Args (slot 6 stays 0)
+template <typename FT>
+struct CoupledTrbdf2Args {
+    FT* y;               // vartheta_l plane of Y: the column's state, and the water stages' iterates
+    const FT* ti;        // theta_i plane (not read by the kernels that know it zero)
+    FT* e;               // rhoe_int plane of Y: the column's state, and the candidate Y_1
+    FT* yn;              // scratch planes [nlev][stride], the water's as Trbdf2Args: Y_n, f_n, Y_gamma, the stage's w, c', d'
+    FT* fn;
+    FT* yg;
+    FT* w;
+    FT* cp;              // (c', d' also serve the energy solves and both error filters)
+    FT* dp;
+    FT* en;              // ... and the energy's: Y_n, f_n, Y_gamma, w2
+    FT* fe;
+    FT* eg;
+    FT* we;
+    FT* dt_cols;         // [ncols] per-column step in / proposal out (0: failed), or nullptr
+    double t0, t1, dt;   // the call's interval and the initial step
+    double abstol, abstol_e, reltol;
+    double bcv[8];       // [t0 | t1][2 faces][2 components], linear in between (has_bcv)
+    int32_t has_bcv;
+    FT kappa;            // the water stage's Newton test max |delta| / (atol + rtol |Y|) <= kappa ...
+    int32_t newton_max;  // ... within newton_max iterations, else the step is rejected
+    unsigned long long* stats; // accepted, rejected, Newton iterations, max steps, failed, wave_steps, 0
+};
 // one column's counters of a call (reduced over the wave)
 struct Trbdf2ColStats {
     unsigned accepted = 0, rejected = 0, iters = 0, steps = 0, failed = 0, unconv = 0;

@@ -90,6 +90,10 @@ void launch_heat_implicit(const DevParams<FT>& P, const HeatImplicitArgs<FT>& A,
 template <typename FT>
 void launch_coupled_implicit(const DevParams<FT>& P, const CoupledImplicitArgs<FT>& A, bool percol, bool noice,
                              bool trbdf2, int math, hipStream_t s);
+// TR-BDF2 of a coupled model over [t0, t1], per-column step control, in one launch (lh_coupled_trbdf2.hpp)
+template <typename FT>
+void launch_coupled_trbdf2(const DevParams<FT>& P, const CoupledTrbdf2Args<FT>& A, bool percol, bool noice, int math,
+                           hipStream_t s);
 template <typename FT>
 void launch_convert(FT* dst, const double* src, int64_t n, hipStream_t s);
 

@@ -562,6 +562,31 @@ function step_coupled_implicit!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt, 
 end
 
 """
+    integrate_coupled_trbdf2!(ens, Y, Ya, t0, t1, dt; abstol = 0.0, abstol_e = 0.0, reltol = 0.0,
+                              dt_cols = C_NULL, bcv = nothing) -> stats
+
+TR-BDF2 of a coupled ensemble, SoilEnergyModel + SoilHydrologyModel without conductivity factors, from `t0`
+to `t1` in one call (lh_integrate_coupled_trbdf2): `step_coupled_implicit!`'s stages with
+`integrate_trbdf2!`'s per-column step and error control over both components.  `dt`: the initial step.  A
+tolerance of 0 takes its own default (`abstol` 1e-6 on `ϑ_l`, `abstol_e` 1e-6 ρ_l c_l on `ρe_int`, `reltol`
+1e-3).  `dt_cols` and `bcv` as `integrate_trbdf2!` (both components of `bcv` are read).  Returns the 7
+counters of lh_trbdf2_stats (accepted, rejected, Newton iterations, max steps, failed, wave_steps, 0).
+"""
+function integrate_coupled_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, t1, dt; abstol = 0.0, abstol_e = 0.0,
+                                   reltol = 0.0, dt_cols = C_NULL, bcv = nothing)
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    check(ens.ctx, ccall((:lh_integrate_coupled_trbdf2, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64, UInt32,
+                          Ptr{Cvoid}, Ptr{Float64}),
+                         ens.ctx, Y.handle, ya, t0, t1, dt, abstol, abstol_e, reltol, UInt32(0), dt_cols, vals))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
     tune_placement!(ens, Y, Ya, dY = nothing; max_candidates = 0, move_input = true)
 
 Let the library place the state written by `rhs!` (`dY` given) or the SSPRK33 stage state

@@ -996,6 +996,9 @@ class TRBDF2:
         last = it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
         return _advance_trbdf2(sim, it.tf if last else it.t0 + (it._nsteps_done + nsteps) * it.dt)
 
+    def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        return integrate_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.reltol, self.adaptive, dt_cols)
+
 
 class HeatImplicitEuler:
     """Backward Euler of a heat-only model, SoilEnergyModel + PrescribedHydrologyModel
@@ -1055,8 +1058,34 @@ class CoupledTRBDF2(CoupledImplicitEuler):
     method = "trbdf2"
 
 
+class CoupledAdaptiveTRBDF2:
+    """TR-BDF2 of the coupled model with per-column error control over both components
+    (lh_integrate_coupled_trbdf2): CoupledTRBDF2's stages, TRBDF2's controller.  abstol (on ϑ_l), abstol_e (on
+    ρe_int) and reltol: None = the library's defaults (1e-6, 1e-6 ρ_l c_l, 1e-3), each on its own.  The Simulation's
+    dt is the initial step and the interval at which Dirichlet closures are sampled, as for TRBDF2.  Scope as
+    CoupledImplicitEuler."""
+
+    def __init__(self, abstol=None, abstol_e=None, reltol=None):
+        self.abstol = abstol
+        self.abstol_e = abstol_e
+        self.reltol = reltol
+
+    def check_scope(self, model):
+        _check_coupled_implicit_scope(model, type(self).__name__)
+
+    def advance(self, sim, nsteps):
+        it = sim.integrator
+        # the end of a chunk of nsteps intervals of dt, as the fixed-step methods reach it; tf itself at the last
+        last = it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
+        return _advance_trbdf2(sim, it.tf if last else it.t0 + (it._nsteps_done + nsteps) * it.dt)
+
+    def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        return integrate_coupled_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, dt_cols)
+
+
 def _check_coupled_implicit_scope(model, name="CoupledImplicitEuler"):
-    """NotImplementedError for what lh_step_coupled_implicit refuses with LH_EMODEL, in its order."""
+    """NotImplementedError for what lh_step_coupled_implicit and lh_integrate_coupled_trbdf2 refuse with LH_EMODEL,
+    in their order."""
     if not (isinstance(model.energy_model, SoilEnergyModel) and isinstance(model.hydrology_model, SoilHydrologyModel)):
         raise NotImplementedError(f"{name}: coupled models only (SoilEnergyModel + SoilHydrologyModel)")
     hm = model.hydrology_model
@@ -1195,26 +1224,58 @@ def integrate_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.
     ya = _handle(Ya)
     bcv = _sampled_bcv(model, (t0, t1), t0)
     be.set_bcs(model, t0)
-    ptr = None
-    if dt_cols is not None:
-        import torch
-        if dt_cols.dtype != _torch_ft_device(model)[0] or not dt_cols.is_cuda or dt_cols.numel() != model.domain.ncolumns \
-                or not dt_cols.is_contiguous():
-            raise ValueError("dt_cols must be a contiguous device tensor of ncolumns values in the model's FT")
-        torch.cuda.synchronize(dt_cols.device)   # (written on torch's stream, read on the library's)
-        ptr = C.c_void_p(dt_cols.data_ptr())
+    ptr = _dt_cols_pointer(model, dt_cols)
     flags = 0 if adaptive else F.LH_TRBDF2_FIXED
     abstol, reltol = _trbdf2_tolerances(abstol, reltol)
     F.check(L.lh_integrate_trbdf2(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol, reltol, flags, ptr,
                                   _dptr(bcv)), be.ctx)
+    return _trbdf2_stats(be)
+
+
+def _dt_cols_pointer(model, dt_cols):
+    """The device pointer of a per-column step buffer (None: NULL), checked against the model."""
+    if dt_cols is None:
+        return None
+    import torch
+    if dt_cols.dtype != _torch_ft_device(model)[0] or not dt_cols.is_cuda or dt_cols.numel() != model.domain.ncolumns \
+            or not dt_cols.is_contiguous():
+        raise ValueError("dt_cols must be a contiguous device tensor of ncolumns values in the model's FT")
+    torch.cuda.synchronize(dt_cols.device)   # (written on torch's stream, read on the library's)
+    return C.c_void_p(dt_cols.data_ptr())
+
+
+_TRBDF2_STATS = ("accepted", "rejected", "newton_iterations", "max_steps", "failed", "wave_steps", "unconverged")
+
+
+def _trbdf2_stats(be):
     st = (C.c_int64 * F.LH_TRBDF2_NSTATS)()
-    F.check(L.lh_trbdf2_stats(be.ctx, st), be.ctx)
-    keys = ("accepted", "rejected", "newton_iterations", "max_steps", "failed", "wave_steps", "unconverged")
-    return dict(zip(keys, (int(x) for x in st)))
+    F.check(F.lib().lh_trbdf2_stats(be.ctx, st), be.ctx)
+    return dict(zip(_TRBDF2_STATS, (int(x) for x in st)))
+
+
+def integrate_coupled_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
+                             dt: float = 1.0, abstol=None, abstol_e=None, reltol=None, dt_cols=None):
+    """Build extension: TR-BDF2 of the coupled model's `Y` from t0 to t1 in one library call
+    (lh_integrate_coupled_trbdf2), every column with its own error-controlled step over ϑ_l and ρe_int.  `dt`: the
+    initial step.  Time-dependent Dirichlet closures of both components are evaluated at t0 and t1 and
+    interpolated linearly in between (per-column values at t0).  abstol / abstol_e / reltol: None = 1e-6 /
+    1e-6 ρ_l c_l / 1e-3, each on its own.  `dt_cols` as integrate_trbdf2.  Returns lh_trbdf2_stats as a dict
+    (unconverged stays 0)."""
+    _check_coupled_implicit_scope(model, "CoupledAdaptiveTRBDF2")
+    be = model._backend()
+    ya = _handle(Ya)
+    bcv = _sampled_bcv(model, (t0, t1), t0)
+    be.set_bcs(model, t0)
+    ptr = _dt_cols_pointer(model, dt_cols)
+    abstol, reltol = _trbdf2_tolerances(abstol, reltol)
+    abstol_e = 0.0 if abstol_e is None else float(abstol_e)   # (0: the library's 1e-6 rho_l c_l of its earth parameters)
+    F.check(F.lib().lh_integrate_coupled_trbdf2(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol, abstol_e,
+                                                reltol, 0, ptr, _dptr(bcv)), be.ctx)
+    return _trbdf2_stats(be)
 
 
 def _advance_trbdf2(sim, t1):
-    """The Simulation's TR-BDF2 from it.t to t1: one library call per dt interval when Dirichlet closures
+    """The Simulation's TR-BDF2 (TRBDF2, CoupledAdaptiveTRBDF2) from it.t to t1: one library call per dt interval when Dirichlet closures
     depend on time, one for the whole interval otherwise; the per-column step proposals carry over.
     Returns the time reached (t1 itself, not a sum of steps)."""
     it, m, model = sim.integrator, sim.method, sim.model
@@ -1232,7 +1293,7 @@ def _advance_trbdf2(sim, t1):
     else:
         ends = [t1]
     for te in ends:
-        st = integrate_trbdf2(model, it.u, it.p, it.t, te, it.dt, m.abstol, m.reltol, m.adaptive, it._dt_cols)
+        st = m.integrate(model, it.u, it.p, it.t, te, it.dt, it._dt_cols)
         for k, v in st.items():
             it.trbdf2_stats[k] += v   # (max_steps: the sum over calls of each call's largest count)
         it.t = te
@@ -1268,9 +1329,10 @@ class Simulation:
 
     def __init__(self, model, method, *, Y_init, dt, tspan, Ya_init, callbacks=None, saveat=None,
                  **kwargs):
-        # (CoupledImplicitEuler and CoupledTRBDF2 are accepted too; the text below is pinned word for word by
-        # tests/test_bcv_sampling.py and so does not name them)
-        if not isinstance(method, (SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler, CoupledImplicitEuler)):
+        # (CoupledImplicitEuler, CoupledTRBDF2 and CoupledAdaptiveTRBDF2 are accepted too; the text below is pinned
+        # word for word by tests/test_bcv_sampling.py and so does not name them)
+        if not isinstance(method, (SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler, CoupledImplicitEuler,
+                                   CoupledAdaptiveTRBDF2)):
             raise NotImplementedError("only SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler and HeatTRBDF2 are "
                                       "provided on the device")
         method.check_scope(model)
