@@ -131,6 +131,13 @@ typedef struct {
     double n, alpha, theta_r, Ksat;
 } lh_vg_params;
 
+/* One soil class of a layered soil (build extension: lh_set_soil_classes): the van Genuchten
+ * parameters and the two SoilParams fields that lh_set_percol_param can vary per column. */
+#define LH_MAX_SOIL_CLASSES 16
+typedef struct {
+    double n, alpha, theta_r, Ksat, nu, S_s;
+} lh_soil_class;
+
 /* PrescribedAtmosForcing{FT} (boundary_conditions.jl:119-132: the first six fields), the
  * roughness lengths it reads from SoilParams (parameters.jl:38-41), and the CLIMAParameters
  * constants compute_turbulent_surface_fluxes (:553-620) consumes on top of lh_earth_params
@@ -162,6 +169,23 @@ int lh_set_vg_params(lh_ctx*, const lh_vg_params*);         /* hydrology.hydraul
 /* per-column override of one parameter (host array of ncols doubles); NULL
  * restores the scalar.  Build extension: the reference has one column. */
 int lh_set_percol_param(lh_ctx*, int32_t param_id, const double* host_values);
+/* Layered soils.  Build extension: the reference has one SoilParams and one vanGenuchten per model.
+ * A soil class is the six numbers lh_set_percol_param knows; a context holds up to LH_MAX_SOIL_CLASSES.
+ * nclasses = 0 removes the classes and the class map.  LH_EINVAL for nclasses outside
+ * 0 .. LH_MAX_SOIL_CLASSES, for a NULL array, and for fewer classes than the map in place uses. */
+int lh_set_soil_classes(lh_ctx*, int32_t nclasses, const lh_soil_class* classes);
+/* The class of every cell (build extension): the byte of (column, level) is
+ * host_map[column * col_stride + level * lev_stride], strides in elements as in lh_upload.  NULL removes
+ * the map.  LH_EMODEL when no classes are set or the model is not LH_MODEL_RICHARDS; LH_EINVAL, naming
+ * the first offending (column, level), for a byte >= nclasses.  While a map is set, lh_rhs,
+ * lh_ssprk33_stage, lh_step_ssprk33 (fused stages), lh_stable_dt, lh_stable_dt_device, lh_diagnostics
+ * and lh_boundary_fluxes evaluate every cell with its class's parameters; they are LH_EMODEL together
+ * with a per-column parameter array or LH_MATH_LIBM, and every other tendency, stepping and tuning entry
+ * point (lh_rhs_stable_dt, lh_step_ssprk33_device_dt, the adaptive SSPRK33 calls, the implicit and
+ * TR-BDF2 integrators, lh_tune_placement) is LH_EMODEL.  Without a map nothing changes. */
+int lh_set_soil_class_map(lh_ctx*, const uint8_t* host_map, int64_t lev_stride, int64_t col_stride);
+/* the number of classes set and whether a class map is in place (build extension); either may be NULL */
+int lh_soil_class_info(const lh_ctx*, int32_t* nclasses, int32_t* has_map);
 /* SoilHydrologyModel.viscosity_factor / .impedance_factor (models.jl:28-33) */
 int lh_set_conductivity_factors(lh_ctx*, int32_t viscosity_kind, double gamma, double T_ref,
                                 int32_t impedance_kind, double Omega);

@@ -13,7 +13,7 @@ from .soil import (Column, CoupledAdaptiveTRBDF2, CoupledImplicitEuler, CoupledT
                    EarthParameterSet, FieldVector, Float32, Float64, FreeDrainage, HeatImplicitEuler,
                    HeatTRBDF2, IceImpedance, ImplicitEuler, NoBC, NoEffect, PrescribedAtmosForcing,
                    PrescribedHydrologyModel, PrescribedTemperatureModel, Simulation, SoilColumnBC,
-                   SoilComponentBC, SoilEnergyModel, SoilHydrologyModel, SoilModel, SoilParams, SSPRK33,
+                   SoilClass, SoilClasses, SoilComponentBC, SoilEnergyModel, SoilHydrologyModel, SoilModel, SoilParams, SSPRK33,
                    TemperatureDependentViscosity, TRBDF2, VerticalFlux, boundary_fluxes,
                    compute_turbulent_surface_fluxes, coordinates, default_initial_conditions,
                    initialize_states, integrate_coupled_trbdf2, integrate_trbdf2, make_function_space,

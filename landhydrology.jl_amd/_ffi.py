@@ -30,6 +30,7 @@ LH_COMM_ID_BYTES = 128
 LH_TRBDF2_FIXED, LH_TRBDF2_NSTATS = 1, 7
 LH_HEAT_TRBDF2 = 1
 LH_COUPLED_TRBDF2 = 1
+LH_MAX_SOIL_CLASSES = 16
 LH_PC = dict(vg_n=0, vg_alpha=1, vg_theta_r=2, vg_Ksat=3, nu=4, S_s=5)
 LH_OK, LH_EINVAL, LH_ENODEVICE, LH_ENOMEM, LH_EMODEL, LH_ESTATE = 0, -1, -2, -3, -4, -5
 
@@ -56,6 +57,10 @@ class lh_vg_params(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("n", "alpha", "theta_r", "Ksat")]
 
 
+class lh_soil_class(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("n", "alpha", "theta_r", "Ksat", "nu", "S_s")]
+
+
 class lh_atmos_forcing(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("u_atm", "theta_atm", "z_atm", "theta_scale", "rho_a_sfc", "q_atm", "z_0m", "z_0s",
@@ -75,6 +80,9 @@ SIGNATURES = {
     "lh_set_soil_params": (C.c_int, [_P, C.POINTER(lh_soil_params)]),
     "lh_set_vg_params": (C.c_int, [_P, C.POINTER(lh_vg_params)]),
     "lh_set_percol_param": (C.c_int, [_P, C.c_int32, _DP]),
+    "lh_set_soil_classes": (C.c_int, [_P, C.c_int32, C.POINTER(lh_soil_class)]),
+    "lh_set_soil_class_map": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int64, C.c_int64]),
+    "lh_soil_class_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lh_set_conductivity_factors": (C.c_int, [_P, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                               C.c_double]),
     "lh_set_bc": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, _DP]),

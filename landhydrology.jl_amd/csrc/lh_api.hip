@@ -3,6 +3,7 @@
 // There is no CPU fallback: without a HIP device lh_create fails loudly.
 #include "../../include/landhydro.h"
 #include "lh_launch.hpp"
+#include "lh_layered.hpp"
 #include "lh_fastmath.hpp"
 #include "lh_closures.hpp"
 
@@ -105,6 +106,12 @@ struct lh_ctx {
     void* d_heat = nullptr;            // lh_step_heat_implicit: eight FT planes [nlev][stride] (three of the factorisation, kc, z; kappa sums, alpha, beta)
     void* d_cpl = nullptr;             // lh_step_coupled_implicit: three FT planes [nlev][stride] (the water stage's w, c', d'; the energy solve reuses c', d')
     void* d_cpl_tr = nullptr;          // ... and four more for LH_COUPLED_TRBDF2 (the water's Y_n and f_n, the energy's f_n and w2)
+    // layered soils (lh_layered.hpp): the classes as given, their ColC<FT> table on the device, and the class
+    // plane [nlev][stride] bytes; a context is "layered" while it holds a map
+    std::vector<lh_soil_class> soil_classes;
+    void* d_cls_table = nullptr;
+    uint8_t* d_cls_map = nullptr;
+    int cls_map_max = 0;               // the largest class index of the map in place
     void* d_cpl_ad = nullptr;          // lh_integrate_coupled_trbdf2: ten FT planes [nlev][stride] (d_tr's six for the water; the energy's Y_n, f_n, Y_gamma, w2)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
@@ -427,6 +434,53 @@ bool any_percol(const lh_ctx* c) {
     return false;
 }
 
+// ---- layered soils: a class map is in place (lh_set_soil_class_map)
+bool layered(const lh_ctx* c) { return c->d_cls_map != nullptr; }
+
+// what a layered context cannot be combined with, checked by every entry point that takes the layered kernels
+int layered_check(lh_ctx* c, const char* who) {
+    if (!layered(c)) return LH_OK;
+    if (c->cfg.model != LH_MODEL_RICHARDS) // (lh_set_soil_class_map refuses it already)
+        return fail(c, LH_EMODEL, "%s: soil classes are for LH_MODEL_RICHARDS only (the heat closures read nu)", who);
+    if (any_percol(c))
+        return fail(c, LH_EMODEL, "%s: soil classes (a class map is set) cannot be combined with per-column parameter arrays (lh_set_percol_param)", who);
+    if (c->math == MATH_LIBM)
+        return fail(c, LH_EMODEL, "%s: soil classes (a class map is set) have no LH_MATH_LIBM kernels", who);
+    return LH_OK;
+}
+// ... and the entry points that have no layered kernels
+int layered_unsupported(lh_ctx* c, const char* who) {
+    if (!layered(c)) return LH_OK;
+    return fail(c, LH_EMODEL, "%s is not available with soil classes (a class map is set): lh_rhs, lh_ssprk33_stage, lh_step_ssprk33, "
+                              "lh_stable_dt, lh_diagnostics and lh_boundary_fluxes are", who);
+}
+// vg_fast_all over the classes: whether EVERY class may take the integer-exponent 2^(.) (the same interval test)
+bool classes_vg_fast(const lh_ctx* c) {
+    for (const lh_soil_class& k : c->soil_classes) {
+        const double m = 1.0 - 1.0 / k.n;
+        if (!(k.n > 1.0 && k.n < 1e30 && m >= LH_VG_FAST_MIN_M * 1.001 && k.alpha > 1.01e-20 && k.alpha < 0.99e20 &&
+              k.nu - k.theta_r >= 1.01e-5 && k.nu - k.theta_r <= 1.0))
+            return false;
+    }
+    return true;
+}
+template <typename FT>
+LayeredArgs<FT> layered_args(const lh_ctx* c) {
+    LayeredArgs<FT> L;
+    L.cls = c->d_cls_map;
+    L.table = static_cast<const ColC<FT>*>(c->d_cls_table);
+    L.ncls = int32_t(c->soil_classes.size());
+    L.pad_ = 0;
+    return L;
+}
+// the launch argument of a layered launch: unsegmented, no profile in LDS, the closure form decided over the classes
+template <typename FT>
+void layered_params(const lh_ctx* c, DevParams<FT>& P) {
+    P.seg_len = 0;
+    for (int i = 0; i < 4; ++i) P.aux_prof[i] = nullptr;
+    P.vg_fast_all = (c->tune.vgfast != 0 && classes_vg_fast(c)) ? 1 : 0;
+}
+
 bool model_water(int m) { return m != LH_MODEL_HEAT; }
 bool model_heat(int m) { return m != LH_MODEL_RICHARDS; }
 
@@ -548,9 +602,9 @@ int do_rhs(lh_ctx* c, const lh_state* in, const lh_state* aux, const lh_state* b
     {   // level-uniform variables: Ya's prescribed profiles go to the kernel as they are, the rest become planes
         int rc;
         if ((rc = materialize(c, in, ~0u)) || (rc = materialize(c, base, ~0u)) || (rc = materialize(c, out, ~0u)) ||
-            (rc = materialize(c, aux, ~aux_profile_vars(c, aux))))
+            (rc = materialize(c, aux, layered(c) ? ~0u : ~aux_profile_vars(c, aux))))
             return rc;
-        set_aux_profiles<FT>(c, aux, P);
+        if (!layered(c)) set_aux_profiles<FT>(c, aux, P);
     }
     P.xcd_remap = c->tune.xcd;
     if (bc_override)
@@ -587,8 +641,13 @@ int do_rhs(lh_ctx* c, const lh_state* in, const lh_state* aux, const lh_state* b
         mark_written(out, ti_bit);
         mark_zero(out, LH_VAR_THETA_I);
     }
-    launch_rhs<FT>(P, planes_of<FT>(in), planes_of<FT>(aux), planes_of<FT>(base), planes_of<FT>(out),
-                   FT(dt), static_cast<const FT*>(dt_device), mode, factors, any_percol(c), noice, c->math, c->tune, c->stream);
+    if (layered(c)) { // (the entry points let modes 0..3 with the step by value through, nothing else)
+        layered_params<FT>(c, P);
+        launch_layered_rhs<FT>(P, layered_args<FT>(c), planes_of<FT>(in), planes_of<FT>(aux), planes_of<FT>(base),
+                               planes_of<FT>(out), FT(dt), mode, factors, noice, c->stream);
+    } else
+        launch_rhs<FT>(P, planes_of<FT>(in), planes_of<FT>(aux), planes_of<FT>(base), planes_of<FT>(out),
+                       FT(dt), static_cast<const FT*>(dt_device), mode, factors, any_percol(c), noice, c->math, c->tune, c->stream);
     LH_HIP(c, hipGetLastError());
     // what the launch wrote: vartheta_l / rhoe_int values
     if (water) mark_written(out, LH_MASK(LH_VAR_VARTHETA_L));
@@ -1045,8 +1104,13 @@ int boundary_fluxes_impl(lh_ctx* c, const lh_state* Y, const lh_state* Ya, int32
         P.bc_pc[LH_FACE_TOP][LH_COMP_HYDROLOGY] = static_cast<const FT*>(c->d_atm_flux[1]);
     }
     const bool factors = c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE;
-    launch_boundary_fluxes<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), face, d_out, d_out + n, factors, any_percol(c),
-                               c->math, c->stream);
+    if (layered(c)) {
+        layered_params<FT>(c, P);
+        launch_layered_boundary_fluxes<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), face, d_out, d_out + n,
+                                           factors, c->stream);
+    } else
+        launch_boundary_fluxes<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), face, d_out, d_out + n, factors, any_percol(c),
+                                   c->math, c->stream);
     hipError_t e = hipGetLastError();
     std::vector<FT> h(size_t(n) * 2);
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(FT), hipMemcpyDeviceToHost, c->stream);
@@ -1059,6 +1123,37 @@ int boundary_fluxes_impl(lh_ctx* c, const lh_state* Y, const lh_state* Ya, int32
         if (f_water) f_water[i] = double(h[size_t(n + i)]);
     }
     return LH_OK;
+}
+
+} // namespace
+
+// ---- layered soils: what the three entry points share
+namespace {
+
+// the class map goes with its classes
+int drop_class_map(lh_ctx* c) {
+    if (!c->d_cls_map) return LH_OK;
+    LH_HIP(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(c->d_cls_map);
+    c->d_cls_map = nullptr;
+    c->cls_map_max = 0;
+    return LH_OK;
+}
+
+// The ColC<FT> of one class, by the arithmetic make_params applies to the scalar parameters: a context whose
+// six scalars are the class's gets exactly this entry as its DevParams::uc
+template <typename FT>
+ColC<FT> class_colc(lh_ctx* c, const lh_soil_class& k) {
+    const HostParams saved = c->hp;
+    c->hp.vg.n = k.n;
+    c->hp.vg.alpha = k.alpha;
+    c->hp.vg.theta_r = k.theta_r;
+    c->hp.vg.Ksat = k.Ksat;
+    c->hp.soil.nu = k.nu;
+    c->hp.soil.S_s = k.S_s;
+    const ColC<FT> u = make_params<FT>(c).uc;
+    c->hp = saved;
+    return u;
 }
 
 } // namespace
@@ -1210,6 +1305,8 @@ int lh_destroy(lh_ctx* c) {
     if (c->d_cpl) (void)hipFree(c->d_cpl);
     if (c->d_cpl_tr) (void)hipFree(c->d_cpl_tr);
     if (c->d_cpl_ad) (void)hipFree(c->d_cpl_ad);
+    if (c->d_cls_table) (void)hipFree(c->d_cls_table);
+    if (c->d_cls_map) (void)hipFree(c->d_cls_map);
     for (int k = 0; k < 3; ++k)
         if (c->d_atm_pc[k]) (void)hipFree(c->d_atm_pc[k]);
     for (int k = 0; k < 2; ++k)
@@ -1259,6 +1356,76 @@ int lh_set_percol_param(lh_ctx* c, int32_t id, const double* host) {
         c->pc_hi[id] = nan ? NAN : hi;
     }
     return upload_percol(c, &c->d_pc[id], host);
+}
+
+// ---- layered soils (build extension; kernels in lh_layered.hpp)
+
+int lh_set_soil_classes(lh_ctx* c, int32_t nclasses, const lh_soil_class* classes) {
+    if (!c) return LH_EINVAL;
+    if (nclasses < 0 || nclasses > LH_MAX_SOIL_CLASSES)
+        return fail(c, LH_EINVAL, "lh_set_soil_classes: nclasses must be 0 .. %d, got %d", int(LH_MAX_SOIL_CLASSES), int(nclasses));
+    (void)hipSetDevice(c->device);
+    if (nclasses == 0) { // the classes and the map go
+        if (int rc = drop_class_map(c)) return rc;
+        c->soil_classes.clear();
+        return LH_OK;
+    }
+    // (what lh_set_vg_params / lh_set_soil_params refuse is a NULL argument; parameter values are not judged
+    // here either: nu <= theta_r poisons the class's cells like a column's, make_params)
+    if (!classes) return fail(c, LH_EINVAL, "lh_set_soil_classes: NULL argument (class 0 of %d)", int(nclasses));
+    if (c->d_cls_map && c->cls_map_max >= nclasses)
+        return fail(c, LH_EINVAL, "lh_set_soil_classes: the class map in place uses class %d, %d classes given", c->cls_map_max, int(nclasses));
+    static_assert(LH_MAX_SOIL_CLASSES == LH_LAYERED_MAX_CLASSES, "the header's limit is the kernels' table size");
+    if (!c->d_cls_table)
+        LH_HIP(c, hipMalloc(&c->d_cls_table, size_t(LH_MAX_SOIL_CLASSES) * sizeof(ColC<double>)));
+    std::vector<char> tab(size_t(nclasses) * sizeof(ColC<double>));
+    size_t bytes = 0;
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        for (int k = 0; k < nclasses; ++k) {
+            const ColC<FT> u = class_colc<FT>(c, classes[k]);
+            memcpy(tab.data() + size_t(k) * sizeof u, &u, sizeof u);
+        }
+        bytes = size_t(nclasses) * sizeof(ColC<FT>);
+    });
+    LH_HIP(c, hipStreamSynchronize(c->stream)); // launches in flight read the table in place
+    LH_HIP(c, hipMemcpy(c->d_cls_table, tab.data(), bytes, hipMemcpyHostToDevice));
+    c->soil_classes.assign(classes, classes + nclasses);
+    return LH_OK;
+}
+
+int lh_set_soil_class_map(lh_ctx* c, const uint8_t* host_map, int64_t lev_stride, int64_t col_stride) {
+    if (!c) return LH_EINVAL;
+    (void)hipSetDevice(c->device);
+    if (!host_map) return drop_class_map(c);
+    if (c->soil_classes.empty()) return fail(c, LH_EMODEL, "lh_set_soil_class_map: no soil classes are set (lh_set_soil_classes)");
+    if (c->cfg.model != LH_MODEL_RICHARDS)
+        return fail(c, LH_EMODEL, "lh_set_soil_class_map: soil classes are for LH_MODEL_RICHARDS only (the heat closures read nu)");
+    const int64_t ncols = c->cfg.ncols;
+    const int nlev = c->cfg.nlev, ncls = int(c->soil_classes.size());
+    std::vector<uint8_t> plane(size_t(nlev) * size_t(c->stride), uint8_t(0)); // pad columns: class 0
+    int top = 0;
+    for (int64_t col = 0; col < ncols; ++col)
+        for (int lev = 0; lev < nlev; ++lev) {
+            const uint8_t k = host_map[col * col_stride + int64_t(lev) * lev_stride];
+            if (k >= ncls)
+                return fail(c, LH_EINVAL, "lh_set_soil_class_map: class %d at (column %lld, level %d), %d classes are set", int(k),
+                            (long long)col, lev, ncls);
+            top = k > top ? k : top;
+            plane[size_t(lev) * size_t(c->stride) + size_t(col)] = k;
+        }
+    if (!c->d_cls_map) LH_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cls_map), plane.size()));
+    LH_HIP(c, hipStreamSynchronize(c->stream)); // launches in flight read the map in place
+    LH_HIP(c, hipMemcpy(c->d_cls_map, plane.data(), plane.size(), hipMemcpyHostToDevice));
+    c->cls_map_max = top;
+    return LH_OK;
+}
+
+int lh_soil_class_info(const lh_ctx* c, int32_t* nclasses, int32_t* has_map) {
+    if (!c) return LH_EINVAL;
+    if (nclasses) *nclasses = int32_t(c->soil_classes.size());
+    if (has_map) *has_map = c->d_cls_map ? 1 : 0;
+    return LH_OK;
 }
 
 int lh_set_conductivity_factors(lh_ctx* c, int32_t vk, double gamma, double T_ref, int32_t ik, double Omega) {
@@ -1579,6 +1746,7 @@ int lh_rhs(lh_ctx* c, double t, const lh_state* Y, const lh_state* Ya, lh_state*
     if (!c) return LH_EINVAL;
     int rc = validate_model(c);
     if (rc) return rc;
+    if ((rc = layered_check(c, "lh_rhs"))) return rc;
     const uint32_t pm = prognostic_mask(c->cfg.model);
     if ((rc = check_state(c, Y, pm, "Y"))) return rc;
     if ((rc = check_state(c, dY, pm, "dY"))) return rc;
@@ -1594,6 +1762,7 @@ int lh_rhs_stable_dt(lh_ctx* c, double t, const lh_state* Y, const lh_state* Ya,
     if (!(courant > 0)) return fail(c, LH_EINVAL, "lh_rhs_stable_dt: courant must be > 0");
     int rc = validate_model(c);
     if (rc) return rc;
+    if ((rc = layered_unsupported(c, "lh_rhs_stable_dt"))) return rc;
     const uint32_t pm = prognostic_mask(c->cfg.model);
     if ((rc = check_state(c, Y, pm, "Y"))) return rc;
     if ((rc = check_state(c, dY, pm, "dY"))) return rc;
@@ -1612,6 +1781,7 @@ int lh_boundary_fluxes(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double 
     if (!f_energy && !f_water) return fail(c, LH_EINVAL, "lh_boundary_fluxes: both outputs are NULL");
     int rc = validate_model(c);
     if (rc) return rc;
+    if ((rc = layered_check(c, "lh_boundary_fluxes"))) return rc;
     if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
     if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
     (void)hipSetDevice(c->device);
@@ -1628,12 +1798,17 @@ int lh_diagnostics(lh_ctx* c, const lh_state* Y, const lh_state* Ya, lh_state* o
     if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
     if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
     if ((rc = check_state(c, out, 0xFu, "diagnostic"))) return rc;
+    if ((rc = layered_check(c, "lh_diagnostics"))) return rc;
     (void)hipSetDevice(c->device);
     if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u))) return rc;
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
-        launch_diag<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), planes_of<FT>(out), any_percol(c), c->math, c->stream);
+        if (layered(c)) {
+            layered_params<FT>(c, P);
+            launch_layered_diag<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), planes_of<FT>(out), c->stream);
+        } else
+            launch_diag<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), planes_of<FT>(out), any_percol(c), c->math, c->stream);
     });
     LH_HIP(c, hipGetLastError());
     mark_written(out, ~0u);
@@ -1642,6 +1817,7 @@ int lh_diagnostics(lh_ctx* c, const lh_state* Y, const lh_state* Ya, lh_state* o
 
 int lh_step_engine(const lh_ctx* c, int64_t nsteps, int32_t per_stage_boundary_values) {
     if (!c || nsteps < 0) return LH_EINVAL;
+    if (layered(c)) return LH_ENGINE_FUSED_STAGES; // the layered kernels have no persistent stepper
     return use_column_stepper(c, nsteps, per_stage_boundary_values != 0) ? LH_ENGINE_COLUMN_STEPPER : LH_ENGINE_FUSED_STAGES;
 }
 
@@ -1653,6 +1829,14 @@ int lh_step_ssprk33(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double
     Range r_("lh:step_ssprk33");
     int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
+    if (layered(c)) { // three unsegmented fused-stage launches per step, the stage state updated in place
+        if ((rc = layered_check(c, "lh_step_ssprk33"))) return rc;
+        lh_state* U1;
+        if ((rc = stage_states(c, &U1, nullptr))) return rc;
+        for (int64_t s = 0; s < nsteps; ++s)
+            if ((rc = fused_ssprk33_step(c, Y, Ya, U1, U1, dt, nullptr, bcv ? bcv + s * 12 : nullptr))) return rc;
+        return LH_OK;
+    }
     // Default: all nsteps in ONE launch of the persistent column stepper (state in registers,
     // no plane traffic between stages or steps; column_stepper_kernel)
     if (use_column_stepper(c, nsteps, bcv != nullptr)) return run_column_stepper(c, Y, Ya, dt, nullptr, nsteps, bcv);
@@ -1673,6 +1857,7 @@ int lh_ssprk33_stage(lh_ctx* c, int32_t stage, lh_state* Y, lh_state* U, const l
     if (!(dt > 0)) return fail(c, LH_EINVAL, "lh_ssprk33_stage: need dt > 0");
     int rc = validate_model(c);
     if (rc) return rc;
+    if ((rc = layered_check(c, "lh_ssprk33_stage"))) return rc;
     const uint32_t pm = prognostic_mask(c->cfg.model);
     if ((rc = check_state(c, Y, pm, "Y"))) return rc;
     if ((rc = check_state(c, U, pm & ~LH_MASK(LH_VAR_THETA_I), "U"))) return rc;
@@ -1691,6 +1876,7 @@ int lh_step_ssprk33_device_dt(lh_ctx* c, lh_state* Y, const lh_state* Ya, double
     if (!c || !dt_device_ft) return fail(c, LH_EINVAL, "lh_step_ssprk33_device_dt: NULL argument");
     int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
+    if ((rc = layered_unsupported(c, "lh_step_ssprk33_device_dt"))) return rc;
     if (use_column_stepper(c, 1, bcv != nullptr)) return run_column_stepper(c, Y, Ya, 0.0, dt_device_ft, 1, bcv);
     lh_state *U1, *U2;
     if ((rc = stage_states(c, &U1, &U2))) return rc;
@@ -1705,6 +1891,7 @@ int lh_step_ssprk33_adaptive(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
     Range r_("lh:step_ssprk33_adaptive");
     int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
+    if ((rc = layered_unsupported(c, "lh_step_ssprk33_adaptive"))) return rc;
     if (!c->scratch_k1 && (rc = state_alloc(c, prognostic_mask(c->cfg.model), &c->scratch_k1))) return rc;
     lh_state* K1 = c->scratch_k1;
     // With a prescribed atmosphere the surface fluxes of a stage come from the stage state's top
@@ -1758,6 +1945,7 @@ int lh_step_ssprk33_adaptive_hold(lh_ctx* c, lh_state* Y, const lh_state* Ya, do
     Range r_("lh:step_ssprk33_adaptive_hold");
     int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
+    if ((rc = layered_unsupported(c, "lh_step_ssprk33_adaptive_hold"))) return rc;
     if (nchunks == 0) return LH_OK;
     if (!c->scratch_k1 && (rc = state_alloc(c, prognostic_mask(c->cfg.model), &c->scratch_k1))) return rc;
     lh_state* K1 = c->scratch_k1; // the tendency the bound's launch writes with it: not used
@@ -1806,6 +1994,7 @@ static int implicit_refusals(lh_ctx* c, const char* who, const lh_state* Y, cons
                              int model = LH_MODEL_RICHARDS,
                              const char* models = "Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)") {
     if (c->cfg.model != model) return fail(c, LH_EMODEL, "%s: %s", who, models);
+    if (int rc = layered_unsupported(c, who)) return rc;
     if (c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE)
         return fail(c, LH_EMODEL, "%s: conductivity factors other than NoEffect are not supported", who);
     // (validate_model refuses a prescribed atmosphere on any model but the coupled one already; kept so
@@ -2132,12 +2321,18 @@ int lh_stable_dt_device(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double
         return fail(c, LH_EINVAL, "earth parameters (lh_set_earth_params) are required by the energy model");
     if ((rc = check_state(c, Y, prognostic_mask(c->cfg.model), "Y"))) return rc;
     if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;
+    if ((rc = layered_check(c, "lh_stable_dt"))) return rc;
     (void)hipSetDevice(c->device);
     if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u))) return rc;
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
-        launch_stable_dt<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), FT(courant), d_out, any_percol(c), c->stream);
+        if (layered(c)) {
+            layered_params<FT>(c, P);
+            launch_fill<FT>(static_cast<FT*>(d_out), 1, FT(INFINITY), c->stream); // the minimum starts at +inf
+            launch_layered_stable_dt<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), FT(courant), d_out, c->stream);
+        } else
+            launch_stable_dt<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), FT(courant), d_out, any_percol(c), c->stream);
     });
     LH_HIP(c, hipGetLastError());
     return allreduce_min(c, d_out); // the global minimum when a communicator is attached
@@ -2177,6 +2372,7 @@ int lh_tune_placement(lh_ctx* c, lh_state* Y, const lh_state* Ya, lh_state* dY, 
     if (!c) return LH_EINVAL;
     int rc = validate_model(c);
     if (rc) return rc;
+    if ((rc = layered_unsupported(c, "lh_tune_placement"))) return rc;
     const uint32_t pm = prognostic_mask(c->cfg.model);
     if ((rc = check_state(c, Y, pm, "Y"))) return rc;
     if ((rc = check_state(c, Ya, aux_mask(c), "Ya"))) return rc;

@@ -1,0 +1,6 @@
+// gfx950 layered-soil kernels (lh_layered.hpp: per-cell soil classes, Richards model), double
+#define LH_LAYERED_TU
+#include "lh_layered.hpp"
+namespace lh {
+LH_INSTANTIATE_LAYERED(double)
+}

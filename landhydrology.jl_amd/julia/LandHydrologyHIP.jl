@@ -68,6 +68,9 @@ end
 struct lh_vg_params
     n::Float64; alpha::Float64; theta_r::Float64; Ksat::Float64
 end
+struct lh_soil_class             # one class of a layered soil (build extension)
+    n::Float64; alpha::Float64; theta_r::Float64; Ksat::Float64; nu::Float64; S_s::Float64
+end
 struct lh_atmos_forcing          # PrescribedAtmosForcing + z_0m, z_0s + the constants of :553-620
     u_atm::Float64; theta_atm::Float64; z_atm::Float64; theta_scale::Float64; rho_a_sfc::Float64
     q_atm::Float64; z_0m::Float64; z_0s::Float64
@@ -602,6 +605,37 @@ function tune_placement!(ens::ColumnEnsemble, Y::DeviceState, Ya, dY = nothing; 
                          ens.ctx, Y.handle, ya, dY === nothing ? C_NULL : dY.handle, max_candidates,
                          move_input ? UInt32(1) : UInt32(0), b, a))
     return b[], a[]
+end
+
+"""
+    set_soil_classes!(ens, classes, class_map)
+
+Layered soils (build extension, Richards models): `classes` is a vector of
+`(n, α, θr, Ksat, ν, S_s)` tuples (at most 16), `class_map` a `Matrix{UInt8}` `[nelements, ncolumns]` of
+ZERO-BASED indices into it (or a `Vector{UInt8}` of `nelements`: the same horizons in every column).
+While a map is set, the tendency, the SSPRK33 stepping, `stable_dt`, the diagnostics and the boundary
+fluxes evaluate every cell with its class's parameters.  `set_soil_classes!(ens, nothing)` removes both.
+"""
+function set_soil_classes!(ens::ColumnEnsemble, classes, class_map = nothing)
+    if classes === nothing
+        check(ens.ctx, ccall((:lh_set_soil_classes, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{lh_soil_class}),
+                             ens.ctx, Int32(0), C_NULL))
+        return ens
+    end
+    cls = [lh_soil_class(Float64.(k)...) for k in classes]
+    check(ens.ctx, ccall((:lh_set_soil_classes, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{lh_soil_class}),
+                         ens.ctx, Int32(length(cls)), cls))
+    class_map === nothing && return ens
+    m = class_map isa AbstractVector ? Vector{UInt8}(class_map) : Matrix{UInt8}(class_map)
+    cs = m isa AbstractVector ? 0 : size(m, 1)    # a vector is broadcast over the columns
+    check(ens.ctx, ccall((:lh_set_soil_class_map, lib), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int64, Int64),
+                         ens.ctx, m, 1, cs))
+    return ens
+end
+function soil_class_info(ens::ColumnEnsemble)
+    n, has = Ref{Int32}(0), Ref{Int32}(0)
+    check(ens.ctx, ccall((:lh_soil_class_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), ens.ctx, n, has))
+    return Int(n[]), has[] != 0
 end
 
 function stable_dt(ens::ColumnEnsemble, Y::DeviceState, Ya = nothing; courant = 0.5)

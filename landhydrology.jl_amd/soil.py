@@ -160,6 +160,79 @@ class vanGenuchten:
     θr = property(lambda s: s.theta_r)
 
 
+class SoilClass:
+    """One soil class of a layered soil (build extension: the reference has one SoilParams and one
+    vanGenuchten per model): a hydraulic model and the two SoilParams fields a texture changes,
+    SoilClass(hydraulic_model=vanGenuchten(...), nu=, S_s=).  Scalars only."""
+
+    def __init__(self, FT=Float64, *, hydraulic_model, nu=None, S_s=None, **kw):
+        self.FT = np.dtype(FT).type
+        nu = kw.pop("ν", nu)
+        if kw:
+            raise TypeError(f"SoilClass has no field(s) {sorted(kw)}")
+        self.hydraulic_model = hydraulic_model
+        self.nu = _SOIL_DEFAULTS["nu"] if nu is None else nu
+        self.S_s = _SOIL_DEFAULTS["S_s"] if S_s is None else S_s
+        for k, v in zip(("n", "alpha", "theta_r", "Ksat", "nu", "S_s"), self.numbers()):
+            if np.ndim(v) != 0:
+                raise ValueError(f"SoilClass: {k} must be a scalar (a class is one texture)")
+
+    def numbers(self):
+        """(n, alpha, theta_r, Ksat, nu, S_s): lh_soil_class"""
+        hm = self.hydraulic_model
+        return hm.n, hm.alpha, hm.theta_r, hm.Ksat, self.nu, self.S_s
+
+    ν = property(lambda s: s.nu)
+
+
+MAX_SOIL_CLASSES = 16   # LH_MAX_SOIL_CLASSES
+
+
+class SoilClasses:
+    """Layered soil (build extension): up to 16 SoilClass and the class of every cell, zero-based indices
+    into `classes`.  `class_map` is [nelements] (bottom first; the same horizons in every column) or
+    [ncolumns, nelements].  SoilModel(..., soil_classes=SoilClasses(...)), Richards models only."""
+
+    def __init__(self, classes, class_map):
+        self.classes = list(classes)
+        if not 1 <= len(self.classes) <= MAX_SOIL_CLASSES:
+            raise F.ModelError(F.LH_EINVAL, f"soil classes: 1 .. {MAX_SOIL_CLASSES} classes, got {len(self.classes)}")
+        if not all(isinstance(k, SoilClass) for k in self.classes):
+            raise TypeError("SoilClasses takes SoilClass objects")
+        m = np.asarray(class_map)
+        if m.ndim not in (1, 2) or not np.issubdtype(m.dtype, np.integer):
+            raise ValueError("soil classes: class_map is an integer array [nelements] or [ncolumns, nelements]")
+        if m.size and (m.min() < 0 or m.max() >= len(self.classes)):
+            bad = np.argwhere((m < 0) | (m >= len(self.classes)))[0]
+            raise F.ModelError(F.LH_EINVAL, f"soil classes: class {int(m[tuple(bad)])} at index {tuple(int(b) for b in bad)} "
+                                            f"of the class map, {len(self.classes)} classes are set")
+        self.class_map = np.ascontiguousarray(m, dtype=np.uint8)
+
+
+def _check_soil_classes(model):
+    """What the library refuses for a layered context (LH_EMODEL), raised when the model is built."""
+    sc = model.soil_classes
+    if not isinstance(sc, SoilClasses):
+        raise TypeError("soil_classes must be a SoilClasses")
+    if not (isinstance(model.energy_model, PrescribedTemperatureModel) and isinstance(model.hydrology_model, SoilHydrologyModel)):
+        raise F.ModelError(F.LH_EMODEL, "soil classes are for Richards models only (SoilHydrologyModel + "
+                                        "PrescribedTemperatureModel): the heat closures read the porosity")
+    hm, sp = model.hydrology_model.hydraulic_model, model.soil_param_set
+    for name, v in (("n", hm.n), ("alpha", hm.alpha), ("theta_r", hm.theta_r), ("Ksat", hm.Ksat), ("nu", sp.nu), ("S_s", sp.S_s)):
+        if np.ndim(v) != 0:
+            raise F.ModelError(F.LH_EMODEL, f"soil classes cannot be combined with per-column parameter arrays ({name})")
+    d = model.domain
+    if sc.class_map.shape not in ((d.nelements,), (d.ncolumns, d.nelements)):
+        raise ValueError(f"soil classes: class_map has shape {sc.class_map.shape}, expected ({d.nelements},) or "
+                         f"({d.ncolumns}, {d.nelements})")
+
+
+def _refuse_soil_classes(model, name):
+    """The integrators and tools that have no layered kernels (LH_EMODEL in the library)."""
+    if getattr(model, "soil_classes", None) is not None:
+        raise NotImplementedError(f"{name} is not available with soil classes (layered soils step with SSPRK33)")
+
+
 class NoEffect:
     """SoilWaterParameterizations.jl:38"""
 
@@ -523,6 +596,13 @@ class _Backend:
             F.check(L.lh_set_conductivity_factors(
                 ctx, int(vk), vf.gamma if vk else 2.64e-2, vf.T_ref if vk else 288.0, int(ik),
                 imf.Omega if ik else 7.0), ctx)
+        sc = getattr(model, "soil_classes", None)
+        if sc is not None:
+            arr = (F.lh_soil_class * len(sc.classes))(*[F.lh_soil_class(*[float(x) for x in k.numbers()]) for k in sc.classes])
+            F.check(L.lh_set_soil_classes(ctx, len(sc.classes), arr), ctx)
+            m = sc.class_map    # [nelements]: a zero column stride broadcasts it over the columns
+            F.check(L.lh_set_soil_class_map(ctx, m.ctypes.data_as(C.POINTER(C.c_uint8)), 1,
+                                            0 if m.ndim == 1 else d.nelements), ctx)
         self.time_dependent_bc = False
         self.set_bcs(model, 0.0)
 
@@ -607,7 +687,7 @@ class SoilModel:
     soil_param_set, earth_param_set, name) -- models.jl:90-135."""
 
     def __init__(self, FT=Float64, *, domain, energy_model, hydrology_model, boundary_conditions,
-                 soil_param_set=None, earth_param_set, name="soil", stream=None, device=-1):
+                 soil_param_set=None, earth_param_set, name="soil", stream=None, device=-1, soil_classes=None):
         self.FT = np.dtype(FT).type
         if np.dtype(domain.FT) != np.dtype(self.FT):
             raise TypeError("domain FT differs from the model FT")   # AbstractVerticalDomain{FT}
@@ -620,6 +700,10 @@ class SoilModel:
         self.name = name
         self._stream, self._device = stream, device
         self._be = None
+        # layered soils (build extension): SoilClasses, or None for the one soil of soil_param_set
+        self.soil_classes = soil_classes
+        if soil_classes is not None:
+            _check_soil_classes(self)
 
     def _backend(self) -> _Backend:
         if self._be is None:
@@ -764,7 +848,7 @@ PLACEMENT_TUNE_MIN_PLANE_BYTES = 32 << 20
 
 def _placement_tuning_wanted(model: SoilModel) -> bool:
     d = model.domain
-    if os.environ.get("LH_PLACEMENT_TUNE", "0") != "1":
+    if os.environ.get("LH_PLACEMENT_TUNE", "0") != "1" or getattr(model, "soil_classes", None) is not None:
         return False
     return d.ncolumns * d.nelements * np.dtype(d.FT).itemsize >= PLACEMENT_TUNE_MIN_PLANE_BYTES
 
@@ -775,6 +859,7 @@ def tune_placement(model: SoilModel, Y: "FieldVector", Ya=None, dY: Optional["Fi
     timing the real launch, where in HBM the state written by rhs! (dY given) or the
     SSPRK33 stage state (dY=None) lives -- lh_tune_placement.  Returns the launch
     time in ms before and after.  Results of later calls do not depend on it."""
+    _refuse_soil_classes(model, "tune_placement")
     be = model._backend()
     ya = _handle(Ya)
     be.set_bcs(model, 0.0)
@@ -908,6 +993,7 @@ def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, c
     Returns (simulated time advanced, last dt)."""
     if int(hold) < 1:
         raise ValueError("step_adaptive: hold must be >= 1")
+    _refuse_soil_classes(model, "step_adaptive")
     if _time_dependent(model):
         raise ValueError("step_adaptive needs boundary values that do not depend on time")
     if _device_reads_aux(model, Ya):
@@ -1088,6 +1174,7 @@ def _check_coupled_implicit_scope(model, name="CoupledImplicitEuler"):
     in their order."""
     if not (isinstance(model.energy_model, SoilEnergyModel) and isinstance(model.hydrology_model, SoilHydrologyModel)):
         raise NotImplementedError(f"{name}: coupled models only (SoilEnergyModel + SoilHydrologyModel)")
+    _refuse_soil_classes(model, name)
     hm = model.hydrology_model
     if not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
         raise NotImplementedError(f"{name}: conductivity factors other than NoEffect are not supported")
@@ -1125,6 +1212,7 @@ def _check_implicit_scope(model, name="ImplicitEuler"):
             isinstance(model.hydrology_model, SoilHydrologyModel)):
         raise NotImplementedError(f"{name} is provided for Richards models only "
                                   "(SoilHydrologyModel + PrescribedTemperatureModel)")
+    _refuse_soil_classes(model, name)
     hm = model.hydrology_model
     if not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
         raise NotImplementedError(f"{name} supports the NoEffect conductivity factors only")
@@ -1159,6 +1247,7 @@ def _check_heat_implicit_scope(model, name="HeatImplicitEuler"):
             isinstance(model.hydrology_model, PrescribedHydrologyModel)):
         raise NotImplementedError(f"{name} is provided for heat-only models only "
                                   "(SoilEnergyModel + PrescribedHydrologyModel)")
+    _refuse_soil_classes(model, name)
 
 
 def step_implicit_heat(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,

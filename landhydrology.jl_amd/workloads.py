@@ -384,6 +384,35 @@ class GpuModel:
                     p = pc.ctypes.data_as(C.POINTER(C.c_double))
                 F.check(L.lh_set_bc(ctx, f, k, kind, float(val), p), ctx)
 
+    def set_soil_classes(self, classes, class_map=None):
+        """Layered soils: `classes` is a sequence of (n, alpha, theta_r, Ksat, nu, S_s), `class_map` an
+        integer array [ncols, nlev] or [nlev] (the same horizons in every column) of indices into it;
+        classes = None removes both, class_map = None leaves (or, after new classes, keeps) the map."""
+        F, L, ctx = self.F, self.L, self.ctx
+        if classes is None:
+            F.check(L.lh_set_soil_classes(ctx, 0, None), ctx)
+            return
+        arr = (F.lh_soil_class * len(classes))(*[F.lh_soil_class(*[float(x) for x in k]) for k in classes])
+        F.check(L.lh_set_soil_classes(ctx, len(classes), arr), ctx)
+        if class_map is not None:
+            self.set_soil_class_map(class_map)
+
+    def set_soil_class_map(self, class_map):
+        F, L, ctx = self.F, self.L, self.ctx
+        if class_map is None:
+            F.check(L.lh_set_soil_class_map(ctx, None, 0, 0), ctx)
+            return
+        m = np.asarray(class_map)
+        if m.ndim == 1:     # one profile of horizons for every column: a zero column stride
+            m = np.ascontiguousarray(m, dtype=np.uint8)
+            assert m.shape == (self.case.om.nlev,)
+            ls, cs = 1, 0
+        else:
+            m = np.ascontiguousarray(m, dtype=np.uint8)
+            assert m.shape == (self.case.ncols, self.case.om.nlev)
+            ls, cs = 1, self.case.om.nlev
+        F.check(L.lh_set_soil_class_map(ctx, m.ctypes.data_as(C.POINTER(C.c_uint8)), ls, cs), ctx)
+
     def state(self, mask=0, **fields):
         h = C.c_void_p()
         self.F.check(self.L.lh_state_create(self.ctx, mask, C.byref(h)), self.ctx)
