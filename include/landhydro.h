@@ -431,12 +431,14 @@ int lh_adaptive_hold_engine(const lh_ctx*, int32_t hold);
  * atmosphere: anything else is LH_EMODEL.  theta_i is constant through the step. */
 int lh_step_implicit_euler(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
                            int64_t nsteps, const double* bcv, double tol, int32_t max_iter);
-/* Of the last lh_step_implicit_euler or lh_step_coupled_implicit call (the water stages of the
- * latter): the largest iteration count any column needed and the number of column-steps (TR-BDF2:
- * column-stages) that did not converge (zeros once a later call was refused).  Synchronises. */
+/* Of the last lh_step_implicit_euler, lh_step_layered_implicit_euler or lh_step_coupled_implicit call
+ * (the water stages of the last): the largest iteration count any column needed and the number of
+ * column-steps (TR-BDF2: column-stages) that did not converge (zeros once a later call was refused).
+ * Synchronises. */
 int lh_implicit_stats(lh_ctx*, int32_t* max_iters, int64_t* unconverged);
-/* Of the last lh_step_implicit_euler or lh_step_coupled_implicit call: the Newton iterations summed
- * over all column-steps (divided by ncols * nsteps: the mean per column-step).  Synchronises. */
+/* Of the last lh_step_implicit_euler, lh_step_layered_implicit_euler or lh_step_coupled_implicit call:
+ * the Newton iterations summed over all column-steps (divided by ncols * nsteps: the mean per
+ * column-step).  Synchronises. */
 int lh_implicit_iterations(lh_ctx*, int64_t* iterations);
 
 /* TR-BDF2 of a Richards model from t0 to t1: L-stable, second order, two
@@ -462,14 +464,32 @@ int lh_implicit_iterations(lh_ctx*, int64_t* iterations);
 int lh_integrate_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
                         double abstol, double reltol, uint32_t flags, void* dt_cols_device_ft,
                         const double* bcv);
-/* Of the last lh_integrate_trbdf2 or lh_integrate_coupled_trbdf2 call, LH_TRBDF2_NSTATS counters
- * (zeros once a later call of either was refused): accepted steps, rejected steps, Newton
- * iterations (summed over stages and columns), the largest number of attempted steps of any column,
+/* Of the last lh_integrate_trbdf2, lh_integrate_layered_trbdf2 or lh_integrate_coupled_trbdf2 call,
+ * LH_TRBDF2_NSTATS counters (zeros once a later call of any of them was refused): accepted steps,
+ * rejected steps, Newton iterations (summed over stages and columns), the largest number of
+ * attempted steps of any column,
  * failed columns, wave_steps (the sum over waves of 64 x the wave's largest step count: what the
  * slowest lane of each wave costs) and, in fixed-step mode, unconverged stages (0 after
  * lh_integrate_coupled_trbdf2).  Synchronises. */
 #define LH_TRBDF2_NSTATS 7
 int lh_trbdf2_stats(lh_ctx*, int64_t* stats);
+
+/* lh_step_implicit_euler and lh_integrate_trbdf2 for layered soils (a class map is set,
+ * lh_set_soil_class_map): the same arguments, defaults, bcv layouts, flags,
+ * statistics (lh_implicit_stats / lh_implicit_iterations, lh_trbdf2_stats) and status bits 3 and 4.
+ * f is lh_rhs's tendency of the same context; the Newton Jacobian takes the two conductivities and the
+ * two slopes of a face from its two cells' classes, and the safeguard (half of nu - theta_r per
+ * iteration, half way to theta_r, a stop on nu - theta_i) and backward Euler's convergence test
+ * max_i |dY_i| <= tol max(|Y_i|, nu) use each cell's own class.
+ * LH_EMODEL, in this order: any model but LH_MODEL_RICHARDS, a context without a class map (use the
+ * call without `layered`), what
+ * every layered call refuses (per-column parameter arrays, LH_MATH_LIBM), conductivity factors other
+ * than NoEffect, a prescribed atmosphere.  LH_EINVAL as the scalar calls.  Asynchronous. */
+int lh_step_layered_implicit_euler(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
+                                   int64_t nsteps, const double* bcv, double tol, int32_t max_iter);
+int lh_integrate_layered_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1,
+                                double dt, double abstol, double reltol, uint32_t flags,
+                                void* dt_cols_device_ft, const double* bcv);
 
 /* Implicit steps of the heat-only model, SoilEnergyModel + PrescribedHydrologyModel
  * (right_hand_side.jl:192-263).  With vartheta_l and theta_i prescribed the

@@ -11,13 +11,14 @@ from ._ffi import LandHydroError, ModelError
 from .parameterizations import *  # noqa: F401,F403
 from .soil import (Column, CoupledAdaptiveTRBDF2, CoupledImplicitEuler, CoupledTRBDF2, Dirichlet,
                    EarthParameterSet, FieldVector, Float32, Float64, FreeDrainage, HeatImplicitEuler,
-                   HeatTRBDF2, IceImpedance, ImplicitEuler, NoBC, NoEffect, PrescribedAtmosForcing,
+                   HeatTRBDF2, IceImpedance, ImplicitEuler, LayeredImplicitEuler, LayeredTRBDF2, NoBC, NoEffect,
+                   PrescribedAtmosForcing,
                    PrescribedHydrologyModel, PrescribedTemperatureModel, Simulation, SoilColumnBC,
                    SoilClass, SoilClasses, SoilComponentBC, SoilEnergyModel, SoilHydrologyModel, SoilModel, SoilParams, SSPRK33,
                    TemperatureDependentViscosity, TRBDF2, VerticalFlux, boundary_fluxes,
                    compute_turbulent_surface_fluxes, coordinates, default_initial_conditions,
-                   initialize_states, integrate_coupled_trbdf2, integrate_trbdf2, make_function_space,
-                   make_rhs, make_update_aux, run, stable_dt, step, step_adaptive, step_implicit,
-                   step_implicit_coupled, step_implicit_heat, tune_placement, vanGenuchten)
+                   initialize_states, integrate_coupled_trbdf2, integrate_layered_trbdf2, integrate_trbdf2,
+                   make_function_space, make_rhs, make_update_aux, run, stable_dt, step, step_adaptive, step_implicit,
+                   step_implicit_coupled, step_implicit_heat, step_implicit_layered, tune_placement, vanGenuchten)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

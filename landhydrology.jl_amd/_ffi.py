@@ -121,6 +121,10 @@ SIGNATURES = {
     "lh_integrate_trbdf2": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                       C.c_uint32, _P, _DP]),
     "lh_trbdf2_stats": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "lh_step_layered_implicit_euler": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, _DP, C.c_double,
+                                                 C.c_int32]),
+    "lh_integrate_layered_trbdf2": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
+                                              C.c_double, C.c_uint32, _P, _DP]),
     "lh_integrate_coupled_trbdf2": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
                                               C.c_double, C.c_double, C.c_uint32, _P, _DP]),
     "lh_step_heat_implicit": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, C.c_uint32,

@@ -4,6 +4,7 @@
 #include "../../include/landhydro.h"
 #include "lh_launch.hpp"
 #include "lh_layered.hpp"
+#include "lh_layered_implicit.hpp"
 #include "lh_fastmath.hpp"
 #include "lh_closures.hpp"
 
@@ -452,7 +453,8 @@ int layered_check(lh_ctx* c, const char* who) {
 int layered_unsupported(lh_ctx* c, const char* who) {
     if (!layered(c)) return LH_OK;
     return fail(c, LH_EMODEL, "%s is not available with soil classes (a class map is set): lh_rhs, lh_ssprk33_stage, lh_step_ssprk33, "
-                              "lh_stable_dt, lh_diagnostics and lh_boundary_fluxes are", who);
+                              "lh_stable_dt, lh_diagnostics and lh_boundary_fluxes are, and lh_step_layered_implicit_euler and "
+                              "lh_integrate_layered_trbdf2 step implicitly", who);
 }
 // vg_fast_all over the classes: whether EVERY class may take the integer-exponent 2^(.) (the same interval test)
 bool classes_vg_fast(const lh_ctx* c) {
@@ -2164,6 +2166,122 @@ int lh_trbdf2_stats(lh_ctx* c, int64_t* stats) {
     const int rc = read_stats(c, c->d_tr_stats, u, sizeof u, "c->d_tr_stats");
     for (int k = 0; k < LH_TRBDF2_NSTATS; ++k) stats[k] = int64_t(u[k]);
     return rc;
+}
+
+// ---- the implicit integrators of layered soils (lh_layered_implicit.hpp): the two calls above
+// with the layered kernels, on the same scratch and statistics blocks
+
+// implicit_refusals' order for a context that must hold a class map (`scalar`: the call for one that does not)
+static int layered_implicit_refusals(lh_ctx* c, const char* who, const char* scalar, const lh_state* Y, const lh_state* Ya) {
+    if (c->cfg.model != LH_MODEL_RICHARDS)
+        return fail(c, LH_EMODEL, "%s: Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)", who);
+    if (!layered(c))
+        return fail(c, LH_EMODEL, "%s: the context has no class map (lh_set_soil_class_map); %s steps a model without soil classes",
+                    who, scalar);
+    if (int rc = layered_check(c, who)) return rc;
+    if (c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE)
+        return fail(c, LH_EMODEL, "%s: conductivity factors other than NoEffect are not supported", who);
+    if (c->hp.atmos_on) return fail(c, LH_EMODEL, "%s: a prescribed-atmosphere top is not supported", who);
+    return stepping_preamble(c, Y, Ya);
+}
+
+int lh_step_layered_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                                   const double* bcv, double tol, int32_t max_iter) {
+    (void)t; // boundary values of t_{n+1} come through bcv or lh_set_bc, as for lh_step_implicit_euler
+    if (!c) return LH_EINVAL;
+    int rc = zero_stats(c, c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24");
+    if (rc) return rc;
+    if (nsteps < 0 || !(dt > 0)) return fail(c, LH_EINVAL, "lh_step_layered_implicit_euler: need nsteps >= 0 and dt > 0");
+    Range r_("lh:step_layered_implicit_euler");
+    if ((rc = layered_implicit_refusals(c, "lh_step_layered_implicit_euler", "lh_step_implicit_euler", Y, Ya))) return rc;
+    if (!(tol > 0)) tol = c->cfg.dtype == LH_F64 ? 1e-10 : 1e-5;
+    if (max_iter <= 0) max_iter = 50;
+    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+    if ((rc = ensure_scratch(c, &c->d_imp, 3 * pl * c->esize, "c->d_imp", "3 * plane"))) return rc;
+    if ((rc = ensure_scratch(c, &c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24", true))) return rc;
+    if (nsteps == 0) return LH_OK;
+    if ((rc = materialize(c, Y, ~0u))) return rc;
+    DeviceBuffer d_bcv; // [nsteps][2][2] doubles -> FT on the device
+    if (bcv && (rc = upload_boundary_values(c, bcv, size_t(nsteps) * 4, d_bcv))) return rc;
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        layered_params<FT>(c, P);
+        ImplicitStats* const st = static_cast<ImplicitStats*>(c->d_imp_stats); // (device memory: addresses only)
+        ImplicitArgs<FT> A;
+        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
+        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+        carve_planes<FT>(c->d_imp, pl, {&A.yn, &A.cp, &A.dp});
+        A.bcv = static_cast<const FT*>(d_bcv.p);
+        A.dt = FT(dt);
+        A.tol = FT(tol);
+        A.max_iter = max_iter;
+        A.nsteps = nsteps;
+        A.max_iters = &st->max_iters;
+        A.unconverged = &st->unconverged;
+        A.total_iters = &st->total_iters;
+        launch_layered_implicit_euler<FT>(P, layered_args<FT>(c), A, implicit_noice(c, Y), c->stream);
+    });
+    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
+    const hipError_t e = launch_error(c, d_bcv);
+    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "layered implicit Euler launch failed: %s", hipGetErrorString(e));
+    return LH_OK;
+}
+
+int lh_integrate_layered_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
+                                double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    if (!c) return LH_EINVAL;
+    const size_t nstat = LH_TRBDF2_NSTATS * sizeof(uint64_t);
+    int rc = zero_stats(c, c->d_tr_stats, nstat, "c->d_tr_stats", "nstat");
+    if (rc) return rc;
+    if (!std::isfinite(t0) || !std::isfinite(t1) || !(t1 >= t0))
+        return fail(c, LH_EINVAL, "lh_integrate_layered_trbdf2: need finite t0 <= t1");
+    if (!std::isfinite(dt) || !(dt > 0)) return fail(c, LH_EINVAL, "lh_integrate_layered_trbdf2: need a finite dt > 0");
+    if (!std::isfinite(abstol) || !std::isfinite(reltol) || abstol < 0 || reltol < 0)
+        return fail(c, LH_EINVAL, "lh_integrate_layered_trbdf2: tolerances must be finite and >= 0");
+    if (flags & ~LH_TRBDF2_FIXED) return fail(c, LH_EINVAL, "lh_integrate_layered_trbdf2: unknown flags 0x%x", flags);
+    if (bcv)
+        for (int k = 0; k < 8; ++k)
+            if (!std::isfinite(bcv[k])) return fail(c, LH_EINVAL, "lh_integrate_layered_trbdf2: non-finite boundary value");
+    Range r_("lh:integrate_layered_trbdf2");
+    if ((rc = layered_implicit_refusals(c, "lh_integrate_layered_trbdf2", "lh_integrate_trbdf2", Y, Ya))) return rc;
+    const bool fixed = (flags & LH_TRBDF2_FIXED) != 0;
+    // each tolerance that is 0 takes its own default, as lh_integrate_trbdf2's
+    if (!(abstol > 0)) abstol = LH_TRBDF2_ABSTOL_DEFAULT;
+    if (!(reltol > 0)) reltol = LH_TRBDF2_RELTOL_DEFAULT;
+    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+    if ((rc = ensure_scratch(c, &c->d_tr, 6 * pl * c->esize, "c->d_tr", "6 * plane"))) return rc;
+    if ((rc = ensure_scratch(c, &c->d_tr_stats, nstat, "c->d_tr_stats", "nstat", true))) return rc;
+    if (t1 == t0) return LH_OK;
+    if ((rc = materialize(c, Y, ~0u))) return rc;
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        layered_params<FT>(c, P);
+        Trbdf2Args<FT> A;
+        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
+        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+        carve_planes<FT>(c->d_tr, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp});
+        A.dt_cols = static_cast<FT*>(dt_cols_device_ft);
+        A.t0 = t0;
+        A.t1 = t1;
+        A.dt = dt;
+        A.abstol = abstol;
+        A.reltol = reltol;
+        A.has_bcv = bcv != nullptr;
+        for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
+        A.fixed = fixed;
+        A.tol = FT(sizeof(FT) == 8 ? 1e-10 : 1e-5); // (fixed mode: lh_step_implicit_euler's defaults)
+        A.max_iter = 50;
+        A.kappa = FT(c->tune.trk > 0 ? 1e-4 * c->tune.trk : LH_TRBDF2_NEWTON_KAPPA);
+        A.newton_max = c->tune.trn > 0 ? c->tune.trn : LH_TRBDF2_NEWTON_MAX;
+        A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
+        launch_layered_trbdf2<FT>(P, layered_args<FT>(c), A, implicit_noice(c, Y), c->stream);
+    });
+    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "layered TR-BDF2 launch failed: %s", hipGetErrorString(e));
+    return LH_OK;
 }
 
 int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,

@@ -230,7 +230,8 @@ def _check_soil_classes(model):
 def _refuse_soil_classes(model, name):
     """The integrators and tools that have no layered kernels (LH_EMODEL in the library)."""
     if getattr(model, "soil_classes", None) is not None:
-        raise NotImplementedError(f"{name} is not available with soil classes (layered soils step with SSPRK33)")
+        raise NotImplementedError(f"{name} is not available with soil classes (layered soils step with SSPRK33, "
+                                  "LayeredImplicitEuler or LayeredTRBDF2)")
 
 
 class NoEffect:
@@ -1086,6 +1087,29 @@ class TRBDF2:
         return integrate_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.reltol, self.adaptive, dt_cols)
 
 
+class LayeredImplicitEuler(ImplicitEuler):
+    """ImplicitEuler for a Richards model with soil_classes (lh_step_layered_implicit_euler): the same Newton,
+    with the Jacobian, the safeguard and the convergence test taking every cell's own class."""
+
+    def check_scope(self, model):
+        _check_implicit_scope(model, "LayeredImplicitEuler", layered=True)
+
+    def advance(self, sim, nsteps):
+        it = sim.integrator
+        step_implicit_layered(sim.model, it.u, it.p, it.t, it.dt, nsteps, self.tol, self.max_iter)
+
+
+class LayeredTRBDF2(TRBDF2):
+    """TRBDF2 for a Richards model with soil_classes (lh_integrate_layered_trbdf2): the same stages, error
+    estimate and per-column controller over LayeredImplicitEuler's Newton."""
+
+    def check_scope(self, model):
+        _check_implicit_scope(model, "LayeredTRBDF2", layered=True)
+
+    def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        return integrate_layered_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.reltol, self.adaptive, dt_cols)
+
+
 class HeatImplicitEuler:
     """Backward Euler of a heat-only model, SoilEnergyModel + PrescribedHydrologyModel
     (lh_step_heat_implicit): the tendency is affine in ρe_int, so a step is one exact tridiagonal solve
@@ -1206,13 +1230,18 @@ def step_implicit_coupled(model: SoilModel, Y: "FieldVector", Ya=None, t: float 
     return int(mi.value), int(un.value)
 
 
-def _check_implicit_scope(model, name="ImplicitEuler"):
-    """NotImplementedError for what lh_step_implicit_euler and lh_integrate_trbdf2 refuse (LH_EMODEL)."""
+def _check_implicit_scope(model, name="ImplicitEuler", layered=False):
+    """NotImplementedError for what lh_step_implicit_euler and lh_integrate_trbdf2 refuse (LH_EMODEL); layered: for
+    what lh_step_layered_implicit_euler and lh_integrate_layered_trbdf2 refuse."""
     if not (isinstance(model.energy_model, PrescribedTemperatureModel) and
             isinstance(model.hydrology_model, SoilHydrologyModel)):
         raise NotImplementedError(f"{name} is provided for Richards models only "
                                   "(SoilHydrologyModel + PrescribedTemperatureModel)")
-    _refuse_soil_classes(model, name)
+    if layered:
+        if getattr(model, "soil_classes", None) is None:
+            raise NotImplementedError(f"{name} is provided for models with soil_classes (without them: ImplicitEuler, TRBDF2)")
+    else:
+        _refuse_soil_classes(model, name)
     hm = model.hydrology_model
     if not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
         raise NotImplementedError(f"{name} supports the NoEffect conductivity factors only")
@@ -1276,15 +1305,27 @@ def step_implicit(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, d
     evaluated at t_{n+1} of every step (per-column values at `t`).  Returns
     (largest Newton iteration count of any column-step, number of column-steps that did not converge)."""
     _check_implicit_scope(model)
+    return _backward_euler(F.lib().lh_step_implicit_euler, model, Y, Ya, t, dt, nsteps, tol, max_iter)
+
+
+def step_implicit_layered(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0, nsteps: int = 1,
+                          tol=None, max_iter=None):
+    """Build extension: step_implicit for a Richards model with soil_classes (lh_step_layered_implicit_euler);
+    arguments and return value as step_implicit."""
+    _check_implicit_scope(model, "LayeredImplicitEuler", layered=True)
+    return _backward_euler(F.lib().lh_step_layered_implicit_euler, model, Y, Ya, t, dt, nsteps, tol, max_iter)
+
+
+def _backward_euler(call, model, Y, Ya, t, dt, nsteps, tol, max_iter):
+    """step_implicit's and step_implicit_layered's library call and its statistics"""
     be = model._backend()
-    L = F.lib()
     ya = _handle(Ya)
     bcv = _sampled_bcv(model, [t + (k + 1) * dt for k in range(int(nsteps))], t)   # t_{n+1} of every step
     be.set_bcs(model, t)
-    F.check(L.lh_step_implicit_euler(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
-                                     _dptr(bcv), float(tol or 0.0), int(max_iter or 0)), be.ctx)
+    F.check(call(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
+                 _dptr(bcv), float(tol or 0.0), int(max_iter or 0)), be.ctx)
     mi, un = C.c_int32(), C.c_int64()
-    F.check(L.lh_implicit_stats(be.ctx, C.byref(mi), C.byref(un)), be.ctx)
+    F.check(F.lib().lh_implicit_stats(be.ctx, C.byref(mi), C.byref(un)), be.ctx)
     return int(mi.value), int(un.value)
 
 
@@ -1308,16 +1349,27 @@ def integrate_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.
     the next proposals (0: failed column); with adaptive=False it is not read and receives dt.
     Returns lh_trbdf2_stats as a dict."""
     _check_implicit_scope(model, "TRBDF2")
+    return _trbdf2(F.lib().lh_integrate_trbdf2, model, Y, Ya, t0, t1, dt, abstol, reltol, adaptive, dt_cols)
+
+
+def integrate_layered_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
+                             dt: float = 1.0, abstol=None, reltol=None, adaptive=True, dt_cols=None):
+    """Build extension: integrate_trbdf2 for a Richards model with soil_classes (lh_integrate_layered_trbdf2);
+    arguments and return value as integrate_trbdf2."""
+    _check_implicit_scope(model, "LayeredTRBDF2", layered=True)
+    return _trbdf2(F.lib().lh_integrate_layered_trbdf2, model, Y, Ya, t0, t1, dt, abstol, reltol, adaptive, dt_cols)
+
+
+def _trbdf2(call, model, Y, Ya, t0, t1, dt, abstol, reltol, adaptive, dt_cols):
+    """integrate_trbdf2's and integrate_layered_trbdf2's library call and its statistics"""
     be = model._backend()
-    L = F.lib()
     ya = _handle(Ya)
     bcv = _sampled_bcv(model, (t0, t1), t0)
     be.set_bcs(model, t0)
     ptr = _dt_cols_pointer(model, dt_cols)
     flags = 0 if adaptive else F.LH_TRBDF2_FIXED
     abstol, reltol = _trbdf2_tolerances(abstol, reltol)
-    F.check(L.lh_integrate_trbdf2(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol, reltol, flags, ptr,
-                                  _dptr(bcv)), be.ctx)
+    F.check(call(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol, reltol, flags, ptr, _dptr(bcv)), be.ctx)
     return _trbdf2_stats(be)
 
 
