@@ -318,6 +318,18 @@ int lh_step_ssprk33(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double d
 enum { LH_ENGINE_FUSED_STAGES = 0, LH_ENGINE_COLUMN_STEPPER = 1 };
 int lh_step_engine(const lh_ctx*, int64_t nsteps, int32_t per_stage_boundary_values);
 
+/* Which form of the table-driven 2^(.) the water closures of the next launch take (no counterpart in the
+ * reference; for logs, benches and tests): LH_CLOSURE_INTEGER_EXPONENT = the exponent put in place by
+ * integer addition, taken while every column (every soil class, while a class map is set) keeps every
+ * power a normal number -- an interval test over the scalar parameters, the ranges of the per-column
+ * arrays or the class table; LH_CLOSURE_LDEXP = the v_ldexp form, for clay-like ensembles (some
+ * m = 1 - 1/n below about 0.07), porosity or alpha out of range, a NaN parameter, or "vgfast=0" in
+ * LH_TUNE / lh_set_tuning; LH_CLOSURE_NOT_APPLICABLE = Float32, LH_MODEL_HEAT and LH_MATH_LIBM have one
+ * form only (the stepping launches of an LH_MATH_LIBM context run the production math and are given the same
+ * decision as without it).  It is the value the launch itself is given.  Returns the form (>= 0) or a negative LH_E* code. */
+enum { LH_CLOSURE_LDEXP = 0, LH_CLOSURE_INTEGER_EXPONENT = 1, LH_CLOSURE_NOT_APPLICABLE = 2 };
+int lh_closure_form(const lh_ctx*);
+
 /* One stage of that step (OrdinaryDiffEq SSPRK33, Shu-Osher form), for hosts that must refresh
  * Ya between the stage evaluations: the reference's rhs! calls update_aux_en!/update_aux_hydr!
  * with the STAGE time at every evaluation (right_hand_side.jl:37-42, 54-81), so a prescribed

@@ -26,6 +26,7 @@ LH_DIAG_K, LH_DIAG_PSI, LH_DIAG_KAPPA, LH_DIAG_T = 0, 1, 2, 3
 LH_MATH_FAST, LH_MATH_LIBM = 0, 1
 LH_PLACE_MOVE_INPUT = 1
 LH_ENGINE_FUSED_STAGES, LH_ENGINE_COLUMN_STEPPER = 0, 1
+LH_CLOSURE_LDEXP, LH_CLOSURE_INTEGER_EXPONENT, LH_CLOSURE_NOT_APPLICABLE = 0, 1, 2
 LH_COMM_ID_BYTES = 128
 LH_TRBDF2_FIXED, LH_TRBDF2_NSTATS = 1, 7
 LH_HEAT_TRBDF2 = 1
@@ -109,6 +110,7 @@ SIGNATURES = {
     "lh_diagnostics": (C.c_int, [_P, _P, _P, _P]),
     "lh_step_ssprk33": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, _DP]),
     "lh_step_engine": (C.c_int, [_P, C.c_int64, C.c_int32]),
+    "lh_closure_form": (C.c_int, [_P]),
     "lh_ssprk33_stage": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_double, _DP]),
     "lh_step_ssprk33_device_dt": (C.c_int, [_P, _P, _P, C.c_double, _P, _DP]),
     "lh_step_ssprk33_adaptive": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int64, _P, _P]),

@@ -250,7 +250,7 @@ int segment_length(const lh_ctx* c) {
     return len < nlev ? len : 0;
 }
 
-bool vg_fast_all(const lh_ctx* c);
+bool closure_integer_exponent(const lh_ctx* c);
 
 template <typename FT>
 DevParams<FT> make_params(const lh_ctx* c) {
@@ -353,7 +353,7 @@ DevParams<FT> make_params(const lh_ctx* c) {
     P.xcd_remap = 0;
     P.seg_len = segment_length(c);
     P.cs_cpb = c->tune.cpb;
-    P.vg_fast_all = (c->tune.vgfast != 0 && vg_fast_all(c)) ? 1 : 0;
+    P.vg_fast_all = closure_integer_exponent(c) ? 1 : 0;
     return P;
 }
 
@@ -466,6 +466,11 @@ bool classes_vg_fast(const lh_ctx* c) {
     }
     return true;
 }
+// DevParams::vg_fast_all of the next water launch, for make_params, layered_params and lh_closure_form alike:
+// the tuning key first, then the interval test over the classes while a class map is set, over the columns otherwise
+bool closure_integer_exponent(const lh_ctx* c) {
+    return c->tune.vgfast != 0 && (layered(c) ? classes_vg_fast(c) : vg_fast_all(c));
+}
 template <typename FT>
 LayeredArgs<FT> layered_args(const lh_ctx* c) {
     LayeredArgs<FT> L;
@@ -480,7 +485,7 @@ template <typename FT>
 void layered_params(const lh_ctx* c, DevParams<FT>& P) {
     P.seg_len = 0;
     for (int i = 0; i < 4; ++i) P.aux_prof[i] = nullptr;
-    P.vg_fast_all = (c->tune.vgfast != 0 && classes_vg_fast(c)) ? 1 : 0;
+    P.vg_fast_all = closure_integer_exponent(c) ? 1 : 0;
 }
 
 bool model_water(int m) { return m != LH_MODEL_HEAT; }
@@ -1821,6 +1826,13 @@ int lh_step_engine(const lh_ctx* c, int64_t nsteps, int32_t per_stage_boundary_v
     if (!c || nsteps < 0) return LH_EINVAL;
     if (layered(c)) return LH_ENGINE_FUSED_STAGES; // the layered kernels have no persistent stepper
     return use_column_stepper(c, nsteps, per_stage_boundary_values != 0) ? LH_ENGINE_COLUMN_STEPPER : LH_ENGINE_FUSED_STAGES;
+}
+
+int lh_closure_form(const lh_ctx* c) {
+    if (!c) return LH_EINVAL;
+    // (robust_vg_exists: only the Float64 production math of a model with water has two forms)
+    if (c->cfg.dtype != LH_F64 || c->cfg.model == LH_MODEL_HEAT || c->math == MATH_LIBM) return LH_CLOSURE_NOT_APPLICABLE;
+    return closure_integer_exponent(c) ? LH_CLOSURE_INTEGER_EXPONENT : LH_CLOSURE_LDEXP;
 }
 
 int lh_step_ssprk33(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,

@@ -41,7 +41,7 @@ import LandHydrology.SoilInterface: make_rhs
 
 export HIPBackend, ColumnEnsemble, upload, download, device_rhs!, step_ssprk33!, stable_dt,
     rhs_stable_dt!, step_ssprk33_device_dt!, block_range, comm_unique_id, attach_comm!, detach_comm!,
-    step_engine
+    step_engine, closure_form
 
 const lib = get(ENV, "LANDHYDRO_HIP_LIB", "liblandhydro_hip.so")
 
@@ -390,6 +390,19 @@ function step_engine(ens::ColumnEnsemble, nsteps::Integer; per_stage_boundary_va
               Int32(per_stage_boundary_values))
     e < 0 && check(ens.ctx, e)
     return e == 1 ? :column_stepper : :fused_stages
+end
+
+"""
+    closure_form(ens)
+
+`:integer_exponent`, `:ldexp` or `:not_applicable`: the form of the table-driven `2^(.)` the Float64 water
+closures of the next launch take (`:ldexp` for clay-like ensembles, parameters out of range or `vgfast=0`;
+`:not_applicable` for Float32, the heat-only model and the libm math mode).
+"""
+function closure_form(ens::ColumnEnsemble)
+    f = ccall((:lh_closure_form, lib), Cint, (Ptr{Cvoid},), ens.ctx)
+    f < 0 && check(ens.ctx, f)
+    return f == 1 ? :integer_exponent : f == 0 ? :ldexp : :not_applicable
 end
 
 "rhs! plus this rank's stable-step bound (one FT value at the device pointer `dt_dev`) in one launch"

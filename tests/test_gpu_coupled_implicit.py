@@ -500,3 +500,20 @@ def test_reference_coupled_equilibrium_in_twelve_steps():
     assert a < 1e-3 and b < 1e-3                                     # coupled.jl:117-118
     f = C.c_uint32()
     assert lh._ffi.lib().lh_get_status(model._backend().ctx, C.byref(f)) == 0 and f.value == 0
+
+
+# ------------------------------------------------------------------ the same in the v_ldexp closure form
+# (Float64 only: Float32 has one form.  ldexp_form: every context of the test is created under `vgfast=0` and
+# asserts lh_closure_form == LH_CLOSURE_LDEXP when it is left; assertions and bounds are those of the tests above.)
+from closure_form import ldexp_form  # noqa: E402,F401
+
+
+@pytest.mark.parametrize("variant", ["plain", "ice", "percol"])
+@pytest.mark.parametrize("kinds", CR.KINDS)
+def test_residual_through_the_tendency_ldexp_form(kinds, variant, ldexp_form):
+    test_residual_through_the_tendency(kinds, variant, np.float64)
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_parity_with_the_cpu_reference_ldexp_form(method, ldexp_form):
+    test_parity_with_the_cpu_reference(method, np.float64)

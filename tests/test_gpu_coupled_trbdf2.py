@@ -525,3 +525,14 @@ def test_reference_coupled_equilibrium_with_error_control():
     assert 0 < stats["accepted"] < 138240   # (the reference's SSPRK33 steps of 20 s)
     f = C.c_uint32()
     assert lh._ffi.lib().lh_get_status(model._backend().ctx, C.byref(f)) == 0 and f.value == 0
+
+
+# ------------------------------------------------------------------ the same in the v_ldexp closure form
+# (Float64 only: Float32 has one form.  ldexp_form: every context of the test is created under `vgfast=0` and
+# asserts lh_closure_form == LH_CLOSURE_LDEXP when it is left; assertions and bounds are those of the tests above.)
+from closure_form import ldexp_form  # noqa: E402,F401
+
+
+@pytest.mark.parametrize("mult", [0.25, 1.0, 4.0, 16.0])
+def test_one_step_against_the_cpu_reference_ldexp_form(mult, ldexp_form):
+    test_one_step_against_the_cpu_reference(mult)

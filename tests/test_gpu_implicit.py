@@ -313,3 +313,18 @@ def test_refusals():
     for model in models:
         with pytest.raises(NotImplementedError):
             lh.Simulation(model, lh.ImplicitEuler(), Y_init=object(), dt=1.0, tspan=(0.0, 1.0), Ya_init=None)
+
+
+# ------------------------------------------------------------------ the same in the v_ldexp closure form
+# (Float64 only: Float32 has one form.  ldexp_form: every context of the test is created under `vgfast=0` and
+# asserts lh_closure_form == LH_CLOSURE_LDEXP when it is left; assertions and bounds are those of the tests above.)
+from closure_form import ldexp_form  # noqa: E402,F401
+
+
+@pytest.mark.parametrize("kinds,variant", VARIANTS)
+def test_residual_through_the_tendency_ldexp_form(kinds, variant, ldexp_form):
+    test_residual_through_the_tendency(np.float64, kinds, variant)
+
+
+def test_parity_with_the_cpu_reference_ldexp_form(ldexp_form):
+    test_parity_with_the_cpu_reference(np.float64)

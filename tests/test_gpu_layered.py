@@ -521,3 +521,24 @@ def test_host_mirror_three_horizons_through_simulation():
     assert np.array_equal(np.array(dY2.soil.ϑ_l), d)
     model.close()
     model2.close()
+
+
+# ------------------------------------------------------------------ the same in the v_ldexp closure form
+# (Float64 only: Float32 has one form.  ldexp_form: every context of the test is created under `vgfast=0` and
+# asserts lh_closure_form == LH_CLOSURE_LDEXP when it is left; assertions and bounds are those of the tests above.)
+from closure_form import ldexp_form  # noqa: E402,F401
+
+
+@pytest.mark.parametrize("bc", ["flux_drain", "dirichlet", "dirichlet_consistent", "flux"])
+@pytest.mark.parametrize("factors,ice", [(False, False), (False, True), (True, False), (True, True)],
+                         ids=["plain", "ice", "factors", "factors_ice"])
+def test_column_uniform_maps_match_the_oracle_ldexp_form(bc, factors, ice, ldexp_form):
+    test_column_uniform_maps_match_the_oracle(np.float64, bc, factors, ice)
+
+
+def test_layered_matches_the_numpy_reference_ldexp_form(ldexp_form):
+    test_layered_matches_the_numpy_reference(np.float64)
+
+
+def test_step_ssprk33_matches_the_reference_and_is_reproducible_ldexp_form(ldexp_form):
+    test_step_ssprk33_matches_the_reference_and_is_reproducible(np.float64)

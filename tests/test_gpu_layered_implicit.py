@@ -577,3 +577,30 @@ def test_scale_1e6_columns():
         v1 = g.download(Y, F.LH_VAR_VARTHETA_L)
         assert un.value == 0 and g.status() == 0 and mi.value >= 1, (mi.value, un.value)
     assert np.all(np.isfinite(v1)) and np.any(v1 != lay.case.vl)
+
+
+# ------------------------------------------------------------------ the same in the v_ldexp closure form
+# (Float64 only: Float32 has one form.  ldexp_form: every context of the test is created under `vgfast=0` and
+# asserts lh_closure_form == LH_CLOSURE_LDEXP when it is left; assertions and bounds are those of the tests above.)
+from closure_form import ldexp_form  # noqa: E402,F401
+
+
+@pytest.mark.parametrize("ice", [False, True], ids=["plain", "ice"])
+@pytest.mark.parametrize("bc", ["flux_drain", "dirichlet", "dirichlet_consistent", "flux"])
+def test_residual_through_the_tendency_ldexp_form(bc, ice, ldexp_form):
+    test_residual_through_the_tendency(np.float64, bc, ice)
+
+
+@pytest.mark.parametrize("bc", ["flux_drain", "dirichlet"])
+def test_parity_with_the_numpy_reference_ldexp_form(bc, ldexp_form):
+    test_parity_with_the_numpy_reference(np.float64, bc)
+
+
+@pytest.mark.parametrize("ice", [False, True], ids=["plain", "ice"])
+@pytest.mark.parametrize("bc", ["flux_drain", "dirichlet"])
+def test_fixed_step_trbdf2_parity_with_the_numpy_reference_ldexp_form(bc, ice, ldexp_form):
+    test_fixed_step_trbdf2_parity_with_the_numpy_reference(np.float64, bc, ice)
+
+
+def test_one_adaptive_step_against_the_numpy_reference_ldexp_form(ldexp_form):
+    test_one_adaptive_step_against_the_numpy_reference()

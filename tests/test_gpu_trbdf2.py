@@ -337,3 +337,18 @@ def test_fixed_mode_ignores_dt_cols():
     np.testing.assert_array_equal(v1, v0)
     assert st1["accepted"] == st0["accepted"] == 3 * 64
     np.testing.assert_array_equal(c1, np.full(64, dt))
+
+
+# ------------------------------------------------------------------ the same in the v_ldexp closure form
+# (Float64 only: Float32 has one form.  ldexp_form: every context of the test is created under `vgfast=0` and
+# asserts lh_closure_form == LH_CLOSURE_LDEXP when it is left; assertions and bounds are those of the tests above.)
+from closure_form import ldexp_form  # noqa: E402,F401
+
+
+@pytest.mark.parametrize("kinds,variant", VARIANTS)
+def test_fixed_step_parity_with_the_cpu_reference_ldexp_form(kinds, variant, ldexp_form):
+    test_fixed_step_parity_with_the_cpu_reference(np.float64, kinds, variant)
+
+
+def test_one_adaptive_step_against_the_cpu_reference_ldexp_form(ldexp_form):
+    test_one_adaptive_step_against_the_cpu_reference()
