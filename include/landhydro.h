@@ -137,6 +137,13 @@ typedef struct {
 typedef struct {
     double n, alpha, theta_r, Ksat, nu, S_s;
 } lh_soil_class;
+/* The thermal supplement of one soil class (build extension: lh_set_soil_class_thermal): the SoilParams
+ * fields a texture changes and the heat path reads.  a, b, kappa_dry_parameter, the earth parameters and
+ * the conductivity factors stay scalars of the context. */
+typedef struct {
+    double rho_c_ds, kappa_solid, rho_p, kappa_sat_unfrozen, kappa_sat_frozen,
+           nu_ss_gravel, nu_ss_om, nu_ss_quartz;
+} lh_soil_class_thermal;
 
 /* PrescribedAtmosForcing{FT} (boundary_conditions.jl:119-132: the first six fields), the
  * roughness lengths it reads from SoilParams (parameters.jl:38-41), and the CLIMAParameters
@@ -172,20 +179,36 @@ int lh_set_percol_param(lh_ctx*, int32_t param_id, const double* host_values);
 /* Layered soils.  Build extension: the reference has one SoilParams and one vanGenuchten per model.
  * A soil class is the six numbers lh_set_percol_param knows; a context holds up to LH_MAX_SOIL_CLASSES.
  * nclasses = 0 removes the classes and the class map.  LH_EINVAL for nclasses outside
- * 0 .. LH_MAX_SOIL_CLASSES, for a NULL array, and for fewer classes than the map in place uses. */
+ * 0 .. LH_MAX_SOIL_CLASSES, for a NULL array, and for fewer classes than the map in place uses.  The call
+ * drops the thermal supplement (the count may change), so it is LH_EMODEL while a map is in place on a
+ * context that is not LH_MODEL_RICHARDS: remove the map first. */
 int lh_set_soil_classes(lh_ctx*, int32_t nclasses, const lh_soil_class* classes);
+/* The thermal supplement of the classes (build extension), one entry per class set by lh_set_soil_classes:
+ * with it a class map is accepted by LH_MODEL_COUPLED and LH_MODEL_HEAT, whose heat closures then take
+ * rho_c_ds, the saturated conductivities, the Kersten exponents, 1 - nu_om and k_dry (from the class's own
+ * nu, rho_p, kappa_solid) per cell.  LH_EINVAL, naming both counts, when nclasses is not the number of
+ * classes set, and for a NULL array with nclasses > 0.  nclasses = 0 removes the supplement (LH_EMODEL
+ * while a map is in place on a model other than LH_MODEL_RICHARDS).  Values are not judged.  A Richards
+ * context ignores the supplement.  What a class's constants take from the context's scalars (a,
+ * kappa_dry_parameter, K_therm) follows lh_set_soil_params and lh_set_earth_params: these may be called
+ * before or after the classes are set. */
+int lh_set_soil_class_thermal(lh_ctx*, int32_t nclasses, const lh_soil_class_thermal* classes);
 /* The class of every cell (build extension): the byte of (column, level) is
  * host_map[column * col_stride + level * lev_stride], strides in elements as in lh_upload.  NULL removes
- * the map.  LH_EMODEL when no classes are set or the model is not LH_MODEL_RICHARDS; LH_EINVAL, naming
+ * the map.  LH_EMODEL when no classes are set, and for LH_MODEL_COUPLED / LH_MODEL_HEAT unless the classes
+ * carry their thermal supplement (lh_set_soil_class_thermal); LH_EINVAL, naming
  * the first offending (column, level), for a byte >= nclasses.  While a map is set, lh_rhs,
  * lh_ssprk33_stage, lh_step_ssprk33 (fused stages), lh_stable_dt, lh_stable_dt_device, lh_diagnostics
  * and lh_boundary_fluxes evaluate every cell with its class's parameters; they are LH_EMODEL together
- * with a per-column parameter array or LH_MATH_LIBM, and every other tendency, stepping and tuning entry
- * point (lh_rhs_stable_dt, lh_step_ssprk33_device_dt, the adaptive SSPRK33 calls, the implicit and
- * TR-BDF2 integrators, lh_tune_placement) is LH_EMODEL.  Without a map nothing changes. */
+ * with a per-column parameter array, LH_MATH_LIBM or a prescribed-atmosphere top, and every other
+ * tendency, stepping and tuning entry point (lh_rhs_stable_dt, lh_step_ssprk33_device_dt, the adaptive
+ * SSPRK33 calls, the implicit and TR-BDF2 integrators -- the two layered ones step Richards contexts
+ * only --, lh_tune_placement) is LH_EMODEL.  Without a map nothing changes. */
 int lh_set_soil_class_map(lh_ctx*, const uint8_t* host_map, int64_t lev_stride, int64_t col_stride);
 /* the number of classes set and whether a class map is in place (build extension); either may be NULL */
 int lh_soil_class_info(const lh_ctx*, int32_t* nclasses, int32_t* has_map);
+/* whether the classes carry their thermal supplement (build extension) */
+int lh_soil_class_thermal_info(const lh_ctx*, int32_t* has_thermal);
 /* SoilHydrologyModel.viscosity_factor / .impedance_factor (models.jl:28-33) */
 int lh_set_conductivity_factors(lh_ctx*, int32_t viscosity_kind, double gamma, double T_ref,
                                 int32_t impedance_kind, double Omega);

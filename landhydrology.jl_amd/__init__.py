@@ -14,7 +14,8 @@ from .soil import (Column, CoupledAdaptiveTRBDF2, CoupledImplicitEuler, CoupledT
                    HeatTRBDF2, IceImpedance, ImplicitEuler, LayeredImplicitEuler, LayeredTRBDF2, NoBC, NoEffect,
                    PrescribedAtmosForcing,
                    PrescribedHydrologyModel, PrescribedTemperatureModel, Simulation, SoilColumnBC,
-                   SoilClass, SoilClasses, SoilComponentBC, SoilEnergyModel, SoilHydrologyModel, SoilModel, SoilParams, SSPRK33,
+                   SoilClass, SoilClasses, SoilComponentBC, SoilEnergyModel, SoilHydrologyModel, SoilModel, SoilParams,
+                   SoilThermal, SSPRK33,
                    TemperatureDependentViscosity, TRBDF2, VerticalFlux, boundary_fluxes,
                    compute_turbulent_surface_fluxes, coordinates, default_initial_conditions,
                    initialize_states, integrate_coupled_trbdf2, integrate_layered_trbdf2, integrate_trbdf2,

@@ -62,6 +62,12 @@ class lh_soil_class(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("n", "alpha", "theta_r", "Ksat", "nu", "S_s")]
 
 
+class lh_soil_class_thermal(C.Structure):
+    _fields_ = [(n, C.c_double) for n in
+                ("rho_c_ds", "kappa_solid", "rho_p", "kappa_sat_unfrozen", "kappa_sat_frozen",
+                 "nu_ss_gravel", "nu_ss_om", "nu_ss_quartz")]
+
+
 class lh_atmos_forcing(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("u_atm", "theta_atm", "z_atm", "theta_scale", "rho_a_sfc", "q_atm", "z_0m", "z_0s",
@@ -84,6 +90,8 @@ SIGNATURES = {
     "lh_set_soil_classes": (C.c_int, [_P, C.c_int32, C.POINTER(lh_soil_class)]),
     "lh_set_soil_class_map": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int64, C.c_int64]),
     "lh_soil_class_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "lh_set_soil_class_thermal": (C.c_int, [_P, C.c_int32, C.POINTER(lh_soil_class_thermal)]),
+    "lh_soil_class_thermal_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "lh_set_conductivity_factors": (C.c_int, [_P, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                               C.c_double]),
     "lh_set_bc": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, _DP]),

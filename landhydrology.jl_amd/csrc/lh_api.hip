@@ -5,6 +5,7 @@
 #include "lh_launch.hpp"
 #include "lh_layered.hpp"
 #include "lh_layered_implicit.hpp"
+#include "lh_layered_heat.hpp"
 #include "lh_fastmath.hpp"
 #include "lh_closures.hpp"
 
@@ -113,6 +114,10 @@ struct lh_ctx {
     void* d_cls_table = nullptr;
     uint8_t* d_cls_map = nullptr;
     int cls_map_max = 0;               // the largest class index of the map in place
+    // ... and their thermal supplement (lh_layered_heat.hpp): one entry per class, or none; its ThermC<FT> table
+    std::vector<lh_soil_class_thermal> soil_thermal;
+    void* d_cls_therm = nullptr;
+    bool cls_any_om = false;           // some class has 1 - nu_om != 1 in the working type
     void* d_cpl_ad = nullptr;          // lh_integrate_coupled_trbdf2: ten FT planes [nlev][stride] (d_tr's six for the water; the energy's Y_n, f_n, Y_gamma, w2)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
@@ -441,8 +446,10 @@ bool layered(const lh_ctx* c) { return c->d_cls_map != nullptr; }
 // what a layered context cannot be combined with, checked by every entry point that takes the layered kernels
 int layered_check(lh_ctx* c, const char* who) {
     if (!layered(c)) return LH_OK;
-    if (c->cfg.model != LH_MODEL_RICHARDS) // (lh_set_soil_class_map refuses it already)
+    if (c->cfg.model != LH_MODEL_RICHARDS && c->soil_thermal.empty()) // (lh_set_soil_class_map refuses it already)
         return fail(c, LH_EMODEL, "%s: soil classes are for LH_MODEL_RICHARDS only (the heat closures read nu)", who);
+    if (c->hp.atmos_on && c->cfg.model != LH_MODEL_RICHARDS) // (a Richards context: validate_model's refusal, as before)
+        return fail(c, LH_EMODEL, "%s: soil classes (a class map is set) cannot be combined with a prescribed-atmosphere top (lh_set_atmos_forcing)", who);
     if (any_percol(c))
         return fail(c, LH_EMODEL, "%s: soil classes (a class map is set) cannot be combined with per-column parameter arrays (lh_set_percol_param)", who);
     if (c->math == MATH_LIBM)
@@ -452,6 +459,9 @@ int layered_check(lh_ctx* c, const char* who) {
 // ... and the entry points that have no layered kernels
 int layered_unsupported(lh_ctx* c, const char* who) {
     if (!layered(c)) return LH_OK;
+    if (c->cfg.model != LH_MODEL_RICHARDS) // (the layered implicit integrators step Richards contexts only)
+        return fail(c, LH_EMODEL, "%s is not available with soil classes (a class map is set): lh_rhs, lh_ssprk33_stage, "
+                                  "lh_step_ssprk33, lh_stable_dt, lh_diagnostics and lh_boundary_fluxes are", who);
     return fail(c, LH_EMODEL, "%s is not available with soil classes (a class map is set): lh_rhs, lh_ssprk33_stage, lh_step_ssprk33, "
                               "lh_stable_dt, lh_diagnostics and lh_boundary_fluxes are, and lh_step_layered_implicit_euler and "
                               "lh_integrate_layered_trbdf2 step implicitly", who);
@@ -470,6 +480,18 @@ bool classes_vg_fast(const lh_ctx* c) {
 // the tuning key first, then the interval test over the classes while a class map is set, over the columns otherwise
 bool closure_integer_exponent(const lh_ctx* c) {
     return c->tune.vgfast != 0 && (layered(c) ? classes_vg_fast(c) : vg_fast_all(c));
+}
+// the coupled and the heat-only model with a map take the kernels of lh_layered_heat.hpp
+bool layered_heat(const lh_ctx* c) { return layered(c) && c->cfg.model != LH_MODEL_RICHARDS; }
+template <typename FT>
+LayeredHeatArgs<FT> layered_heat_args(const lh_ctx* c) {
+    LayeredHeatArgs<FT> L;
+    L.cls = c->d_cls_map;
+    L.table = static_cast<const ColC<FT>*>(c->d_cls_table);
+    L.therm = static_cast<const ThermC<FT>*>(c->d_cls_therm);
+    L.ncls = int32_t(c->soil_classes.size());
+    L.any_om = c->cls_any_om ? 1 : 0;
+    return L;
 }
 template <typename FT>
 LayeredArgs<FT> layered_args(const lh_ctx* c) {
@@ -650,8 +672,12 @@ int do_rhs(lh_ctx* c, const lh_state* in, const lh_state* aux, const lh_state* b
     }
     if (layered(c)) { // (the entry points let modes 0..3 with the step by value through, nothing else)
         layered_params<FT>(c, P);
-        launch_layered_rhs<FT>(P, layered_args<FT>(c), planes_of<FT>(in), planes_of<FT>(aux), planes_of<FT>(base),
-                               planes_of<FT>(out), FT(dt), mode, factors, noice, c->stream);
+        if (layered_heat(c))
+            launch_layered_heat_rhs<FT>(P, layered_heat_args<FT>(c), planes_of<FT>(in), planes_of<FT>(aux), planes_of<FT>(base),
+                                        planes_of<FT>(out), FT(dt), mode, c->cfg.model, factors, noice, c->stream);
+        else
+            launch_layered_rhs<FT>(P, layered_args<FT>(c), planes_of<FT>(in), planes_of<FT>(aux), planes_of<FT>(base),
+                                   planes_of<FT>(out), FT(dt), mode, factors, noice, c->stream);
     } else
         launch_rhs<FT>(P, planes_of<FT>(in), planes_of<FT>(aux), planes_of<FT>(base), planes_of<FT>(out),
                        FT(dt), static_cast<const FT*>(dt_device), mode, factors, any_percol(c), noice, c->math, c->tune, c->stream);
@@ -1113,8 +1139,12 @@ int boundary_fluxes_impl(lh_ctx* c, const lh_state* Y, const lh_state* Ya, int32
     const bool factors = c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE;
     if (layered(c)) {
         layered_params<FT>(c, P);
-        launch_layered_boundary_fluxes<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), face, d_out, d_out + n,
-                                           factors, c->stream);
+        if (layered_heat(c))
+            launch_layered_heat_boundary_fluxes<FT>(P, layered_heat_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), face, d_out,
+                                                    d_out + n, c->cfg.model, factors, c->stream);
+        else
+            launch_layered_boundary_fluxes<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), face, d_out, d_out + n,
+                                               factors, c->stream);
     } else
         launch_boundary_fluxes<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), face, d_out, d_out + n, factors, any_percol(c),
                                    c->math, c->stream);
@@ -1149,8 +1179,10 @@ int drop_class_map(lh_ctx* c) {
 
 // The ColC<FT> of one class, by the arithmetic make_params applies to the scalar parameters: a context whose
 // six scalars are the class's gets exactly this entry as its DevParams::uc
+// With the class's thermal supplement `t` the eight fields it holds replace the context's too: k_dry then comes from
+// the class's own nu, rho_p, kappa_solid, and the returned block holds the class's thermal constants.
 template <typename FT>
-ColC<FT> class_colc(lh_ctx* c, const lh_soil_class& k) {
+DevParams<FT> class_params(lh_ctx* c, const lh_soil_class& k, const lh_soil_class_thermal* t) {
     const HostParams saved = c->hp;
     c->hp.vg.n = k.n;
     c->hp.vg.alpha = k.alpha;
@@ -1158,9 +1190,67 @@ ColC<FT> class_colc(lh_ctx* c, const lh_soil_class& k) {
     c->hp.vg.Ksat = k.Ksat;
     c->hp.soil.nu = k.nu;
     c->hp.soil.S_s = k.S_s;
-    const ColC<FT> u = make_params<FT>(c).uc;
+    if (t) {
+        c->hp.soil.rho_c_ds = t->rho_c_ds;
+        c->hp.soil.kappa_solid = t->kappa_solid;
+        c->hp.soil.rho_p = t->rho_p;
+        c->hp.soil.kappa_sat_unfrozen = t->kappa_sat_unfrozen;
+        c->hp.soil.kappa_sat_frozen = t->kappa_sat_frozen;
+        c->hp.soil.nu_ss_gravel = t->nu_ss_gravel;
+        c->hp.soil.nu_ss_om = t->nu_ss_om;
+        c->hp.soil.nu_ss_quartz = t->nu_ss_quartz;
+    }
+    const DevParams<FT> P = make_params<FT>(c);
     c->hp = saved;
-    return u;
+    return P;
+}
+template <typename FT>
+ColC<FT> class_colc(lh_ctx* c, const lh_soil_class& k) { return class_params<FT>(c, k, nullptr).uc; }
+
+// the class table (and, with a supplement, the thermal table) of the classes and supplement given, to the device
+int upload_class_tables(lh_ctx* c, int nclasses, const lh_soil_class* classes, const lh_soil_class_thermal* thermal) {
+    static_assert(LH_MAX_SOIL_CLASSES == LH_LAYERED_MAX_CLASSES, "the header's limit is the kernels' table size");
+    if (!c->d_cls_table)
+        LH_HIP(c, hipMalloc(&c->d_cls_table, size_t(LH_MAX_SOIL_CLASSES) * sizeof(ColC<double>)));
+    if (thermal && !c->d_cls_therm)
+        LH_HIP(c, hipMalloc(&c->d_cls_therm, size_t(LH_MAX_SOIL_CLASSES) * sizeof(ThermC<double>)));
+    std::vector<char> tab(size_t(nclasses) * sizeof(ColC<double>)), th(size_t(nclasses) * sizeof(ThermC<double>));
+    size_t bytes = 0, th_bytes = 0;
+    bool any_om = false;
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        for (int k = 0; k < nclasses; ++k) {
+            const DevParams<FT> P = class_params<FT>(c, classes[k], thermal ? thermal + k : nullptr);
+            memcpy(tab.data() + size_t(k) * sizeof P.uc, &P.uc, sizeof P.uc);
+            ThermC<FT> t;
+            t.rho_c_ds = P.rho_c_ds;
+            t.kappa_sat_unfrozen = P.kappa_sat_unfrozen;
+            t.kappa_sat_frozen = P.kappa_sat_frozen;
+            t.l2_kappa_sat_unfrozen = P.l2_kappa_sat_unfrozen;
+            t.l2_kappa_sat_frozen = P.l2_kappa_sat_frozen;
+            t.kersten_exp_unfrozen = P.kersten_exp_unfrozen;
+            t.kersten_exp_frozen = P.kersten_exp_frozen;
+            t.one_minus_om = P.one_minus_om;
+            memcpy(th.data() + size_t(k) * sizeof t, &t, sizeof t);
+            any_om = any_om || (thermal && P.one_minus_om != FT(1));
+        }
+        bytes = size_t(nclasses) * sizeof(ColC<FT>);
+        th_bytes = size_t(nclasses) * sizeof(ThermC<FT>);
+    });
+    LH_HIP(c, hipStreamSynchronize(c->stream)); // launches in flight read the tables in place
+    LH_HIP(c, hipMemcpy(c->d_cls_table, tab.data(), bytes, hipMemcpyHostToDevice));
+    if (thermal) LH_HIP(c, hipMemcpy(c->d_cls_therm, th.data(), th_bytes, hipMemcpyHostToDevice));
+    c->cls_any_om = any_om;
+    return LH_OK;
+}
+
+// The tables hold what make_params forms from the classes AND the context's scalars (a, kappa_dry_parameter, the
+// air's conductivity: the Kersten exponent and k_dry), so a setter of those scalars forms them again
+int refresh_class_tables(lh_ctx* c) {
+    if (c->soil_classes.empty()) return LH_OK;
+    (void)hipSetDevice(c->device);
+    return upload_class_tables(c, int(c->soil_classes.size()), c->soil_classes.data(),
+                               c->soil_thermal.empty() ? nullptr : c->soil_thermal.data());
 }
 
 } // namespace
@@ -1314,6 +1404,7 @@ int lh_destroy(lh_ctx* c) {
     if (c->d_cpl_ad) (void)hipFree(c->d_cpl_ad);
     if (c->d_cls_table) (void)hipFree(c->d_cls_table);
     if (c->d_cls_map) (void)hipFree(c->d_cls_map);
+    if (c->d_cls_therm) (void)hipFree(c->d_cls_therm);
     for (int k = 0; k < 3; ++k)
         if (c->d_atm_pc[k]) (void)hipFree(c->d_atm_pc[k]);
     for (int k = 0; k < 2; ++k)
@@ -1331,13 +1422,13 @@ int lh_set_earth_params(lh_ctx* c, const lh_earth_params* p) {
     if (!c || !p) return fail(c, LH_EINVAL, "lh_set_earth_params: NULL argument");
     c->hp.earth = *p;
     c->hp.earth_set = true;
-    return LH_OK;
+    return refresh_class_tables(c);
 }
 
 int lh_set_soil_params(lh_ctx* c, const lh_soil_params* p) {
     if (!c || !p) return fail(c, LH_EINVAL, "lh_set_soil_params: NULL argument");
     c->hp.soil = *p;
-    return LH_OK;
+    return refresh_class_tables(c);
 }
 
 int lh_set_vg_params(lh_ctx* c, const lh_vg_params* p) {
@@ -1372,9 +1463,15 @@ int lh_set_soil_classes(lh_ctx* c, int32_t nclasses, const lh_soil_class* classe
     if (nclasses < 0 || nclasses > LH_MAX_SOIL_CLASSES)
         return fail(c, LH_EINVAL, "lh_set_soil_classes: nclasses must be 0 .. %d, got %d", int(LH_MAX_SOIL_CLASSES), int(nclasses));
     (void)hipSetDevice(c->device);
-    if (nclasses == 0) { // the classes and the map go
+    // (the call drops the thermal supplement, which a map on a coupled or heat-only context cannot be without)
+    if (layered_heat(c))
+        return fail(c, LH_EMODEL, "lh_set_soil_classes: class map in place needs thermal properties (remove the map first: "
+                                  "lh_set_soil_class_map(NULL), then lh_set_soil_classes and lh_set_soil_class_thermal)");
+    if (nclasses == 0) { // the classes, their supplement and the map go
         if (int rc = drop_class_map(c)) return rc;
         c->soil_classes.clear();
+        c->soil_thermal.clear();
+        c->cls_any_om = false;
         return LH_OK;
     }
     // (what lh_set_vg_params / lh_set_soil_params refuse is a NULL argument; parameter values are not judged
@@ -1382,22 +1479,38 @@ int lh_set_soil_classes(lh_ctx* c, int32_t nclasses, const lh_soil_class* classe
     if (!classes) return fail(c, LH_EINVAL, "lh_set_soil_classes: NULL argument (class 0 of %d)", int(nclasses));
     if (c->d_cls_map && c->cls_map_max >= nclasses)
         return fail(c, LH_EINVAL, "lh_set_soil_classes: the class map in place uses class %d, %d classes given", c->cls_map_max, int(nclasses));
-    static_assert(LH_MAX_SOIL_CLASSES == LH_LAYERED_MAX_CLASSES, "the header's limit is the kernels' table size");
-    if (!c->d_cls_table)
-        LH_HIP(c, hipMalloc(&c->d_cls_table, size_t(LH_MAX_SOIL_CLASSES) * sizeof(ColC<double>)));
-    std::vector<char> tab(size_t(nclasses) * sizeof(ColC<double>));
-    size_t bytes = 0;
-    with_ft(c, [&](auto ft) {
-        using FT = decltype(ft);
-        for (int k = 0; k < nclasses; ++k) {
-            const ColC<FT> u = class_colc<FT>(c, classes[k]);
-            memcpy(tab.data() + size_t(k) * sizeof u, &u, sizeof u);
-        }
-        bytes = size_t(nclasses) * sizeof(ColC<FT>);
-    });
-    LH_HIP(c, hipStreamSynchronize(c->stream)); // launches in flight read the table in place
-    LH_HIP(c, hipMemcpy(c->d_cls_table, tab.data(), bytes, hipMemcpyHostToDevice));
+    if (int rc = upload_class_tables(c, nclasses, classes, nullptr)) return rc;
     c->soil_classes.assign(classes, classes + nclasses);
+    c->soil_thermal.clear();
+    return LH_OK;
+}
+
+int lh_set_soil_class_thermal(lh_ctx* c, int32_t nclasses, const lh_soil_class_thermal* classes) {
+    if (!c) return LH_EINVAL;
+    (void)hipSetDevice(c->device);
+    const int have = int(c->soil_classes.size());
+    if (nclasses == 0) { // the supplement goes: the class table is the one lh_set_soil_classes built
+        if (layered_heat(c))
+            return fail(c, LH_EMODEL, "lh_set_soil_class_thermal: the class map in place needs the thermal properties of the soil "
+                                      "classes (remove the map first: lh_set_soil_class_map(NULL))");
+        if (c->soil_thermal.empty()) return LH_OK;
+        if (int rc = upload_class_tables(c, have, c->soil_classes.data(), nullptr)) return rc;
+        c->soil_thermal.clear();
+        return LH_OK;
+    }
+    if (nclasses != have)
+        return fail(c, LH_EINVAL, "lh_set_soil_class_thermal: %d thermal classes given, %d soil classes are set (lh_set_soil_classes)",
+                    int(nclasses), have);
+    if (!classes) return fail(c, LH_EINVAL, "lh_set_soil_class_thermal: NULL argument (class 0 of %d)", int(nclasses));
+    // (values are not judged, as in lh_set_soil_params)
+    if (int rc = upload_class_tables(c, have, c->soil_classes.data(), classes)) return rc;
+    c->soil_thermal.assign(classes, classes + nclasses);
+    return LH_OK;
+}
+
+int lh_soil_class_thermal_info(const lh_ctx* c, int32_t* has_thermal) {
+    if (!c) return LH_EINVAL;
+    if (has_thermal) *has_thermal = c->soil_thermal.empty() ? 0 : 1;
     return LH_OK;
 }
 
@@ -1406,8 +1519,9 @@ int lh_set_soil_class_map(lh_ctx* c, const uint8_t* host_map, int64_t lev_stride
     (void)hipSetDevice(c->device);
     if (!host_map) return drop_class_map(c);
     if (c->soil_classes.empty()) return fail(c, LH_EMODEL, "lh_set_soil_class_map: no soil classes are set (lh_set_soil_classes)");
-    if (c->cfg.model != LH_MODEL_RICHARDS)
-        return fail(c, LH_EMODEL, "lh_set_soil_class_map: soil classes are for LH_MODEL_RICHARDS only (the heat closures read nu)");
+    if (c->cfg.model != LH_MODEL_RICHARDS && c->soil_thermal.empty())
+        return fail(c, LH_EMODEL, "lh_set_soil_class_map: soil classes are for LH_MODEL_RICHARDS only (the heat closures read nu) "
+                                  "unless they carry their thermal properties (lh_set_soil_class_thermal)");
     const int64_t ncols = c->cfg.ncols;
     const int nlev = c->cfg.nlev, ncls = int(c->soil_classes.size());
     std::vector<uint8_t> plane(size_t(nlev) * size_t(c->stride), uint8_t(0)); // pad columns: class 0
@@ -1813,7 +1927,11 @@ int lh_diagnostics(lh_ctx* c, const lh_state* Y, const lh_state* Ya, lh_state* o
         DevParams<FT> P = make_params<FT>(c);
         if (layered(c)) {
             layered_params<FT>(c, P);
-            launch_layered_diag<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), planes_of<FT>(out), c->stream);
+            if (layered_heat(c))
+                launch_layered_heat_diag<FT>(P, layered_heat_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), planes_of<FT>(out),
+                                             c->cfg.model, c->stream);
+            else
+                launch_layered_diag<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), planes_of<FT>(out), c->stream);
         } else
             launch_diag<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), planes_of<FT>(out), any_percol(c), c->math, c->stream);
     });
@@ -2185,6 +2303,9 @@ int lh_trbdf2_stats(lh_ctx* c, int64_t* stats) {
 
 // implicit_refusals' order for a context that must hold a class map (`scalar`: the call for one that does not)
 static int layered_implicit_refusals(lh_ctx* c, const char* who, const char* scalar, const lh_state* Y, const lh_state* Ya) {
+    if (c->cfg.model != LH_MODEL_RICHARDS && layered(c))
+        return fail(c, LH_EMODEL, "%s is not available with soil classes (a class map is set) on this model: it steps Richards models "
+                                  "only (SoilHydrologyModel + PrescribedTemperatureModel)", who);
     if (c->cfg.model != LH_MODEL_RICHARDS)
         return fail(c, LH_EMODEL, "%s: Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)", who);
     if (!layered(c))
@@ -2308,6 +2429,7 @@ int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, 
         return fail(c, LH_EMODEL, "lh_step_heat_implicit: heat-only models (SoilEnergyModel + PrescribedHydrologyModel)");
     int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
+    if ((rc = layered_unsupported(c, "lh_step_heat_implicit"))) return rc;
     if (nsteps == 0) return LH_OK;
     const bool trbdf2 = (flags & LH_HEAT_TRBDF2) != 0;
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
@@ -2460,7 +2582,11 @@ int lh_stable_dt_device(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double
         if (layered(c)) {
             layered_params<FT>(c, P);
             launch_fill<FT>(static_cast<FT*>(d_out), 1, FT(INFINITY), c->stream); // the minimum starts at +inf
-            launch_layered_stable_dt<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), FT(courant), d_out, c->stream);
+            if (layered_heat(c))
+                launch_layered_heat_stable_dt<FT>(P, layered_heat_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), FT(courant), d_out,
+                                                  c->cfg.model, c->stream);
+            else
+                launch_layered_stable_dt<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), FT(courant), d_out, c->stream);
         } else
             launch_stable_dt<FT>(P, planes_of<FT>(Y), planes_of<FT>(Ya), FT(courant), d_out, any_percol(c), c->stream);
     });

@@ -1,0 +1,7 @@
+// gfx950 layered-soil heat kernels (lh_layered_heat.hpp: per-cell soil classes, coupled and heat-only models), float
+#define LH_LAYERED_TU
+#define LH_LAYERED_HEAT_TU
+#include "lh_layered_heat.hpp"
+namespace lh {
+LH_INSTANTIATE_LAYERED_HEAT(float)
+}

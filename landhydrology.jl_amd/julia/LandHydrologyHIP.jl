@@ -71,6 +71,10 @@ end
 struct lh_soil_class             # one class of a layered soil (build extension)
     n::Float64; alpha::Float64; theta_r::Float64; Ksat::Float64; nu::Float64; S_s::Float64
 end
+struct lh_soil_class_thermal     # the thermal supplement of one class (build extension)
+    rho_c_ds::Float64; kappa_solid::Float64; rho_p::Float64; kappa_sat_unfrozen::Float64; kappa_sat_frozen::Float64
+    nu_ss_gravel::Float64; nu_ss_om::Float64; nu_ss_quartz::Float64
+end
 struct lh_atmos_forcing          # PrescribedAtmosForcing + z_0m, z_0s + the constants of :553-620
     u_atm::Float64; theta_atm::Float64; z_atm::Float64; theta_scale::Float64; rho_a_sfc::Float64
     q_atm::Float64; z_0m::Float64; z_0s::Float64
@@ -667,15 +671,36 @@ function tune_placement!(ens::ColumnEnsemble, Y::DeviceState, Ya, dY = nothing; 
 end
 
 """
-    set_soil_classes!(ens, classes, class_map)
+    SoilThermal(; ρc_ds, κ_solid, ρp, κ_sat_unfrozen, κ_sat_frozen, ν_ss_gravel, ν_ss_om, ν_ss_quartz)
 
-Layered soils (build extension, Richards models): `classes` is a vector of
+The thermal supplement of a soil class (build extension), with the defaults and spellings of `SoilParams`: what a
+texture changes and the heat path reads.  `a`, `b` and `κ_dry_parameter` stay scalars of the model's `SoilParams`.
+"""
+Base.@kwdef struct SoilThermal
+    ρc_ds::Float64 = 2700.0
+    κ_solid::Float64 = 3.97
+    ρp::Float64 = 2700.0
+    κ_sat_unfrozen::Float64 = 1.72
+    κ_sat_frozen::Float64 = 3.13
+    ν_ss_gravel::Float64 = 0.0
+    ν_ss_om::Float64 = 0.0
+    ν_ss_quartz::Float64 = 0.41
+end
+lh_soil_class_thermal(t::SoilThermal) = lh_soil_class_thermal(t.ρc_ds, t.κ_solid, t.ρp, t.κ_sat_unfrozen, t.κ_sat_frozen,
+                                                              t.ν_ss_gravel, t.ν_ss_om, t.ν_ss_quartz)
+
+"""
+    set_soil_classes!(ens, classes, class_map; thermal = nothing)
+
+Layered soils (build extension): Richards models, and -- with `thermal`, one `SoilThermal` per class -- the
+coupled and the heat-only model, whose heat closures then take ρc_ds, the saturated conductivities, the Kersten
+exponents, the organic fraction and κ_dry per cell.  `classes` is a vector of
 `(n, α, θr, Ksat, ν, S_s)` tuples (at most 16), `class_map` a `Matrix{UInt8}` `[nelements, ncolumns]` of
 ZERO-BASED indices into it (or a `Vector{UInt8}` of `nelements`: the same horizons in every column).
 While a map is set, the tendency, the SSPRK33 stepping, `stable_dt`, the diagnostics and the boundary
 fluxes evaluate every cell with its class's parameters.  `set_soil_classes!(ens, nothing)` removes both.
 """
-function set_soil_classes!(ens::ColumnEnsemble, classes, class_map = nothing)
+function set_soil_classes!(ens::ColumnEnsemble, classes, class_map = nothing; thermal = nothing)
     if classes === nothing
         check(ens.ctx, ccall((:lh_set_soil_classes, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{lh_soil_class}),
                              ens.ctx, Int32(0), C_NULL))
@@ -684,6 +709,11 @@ function set_soil_classes!(ens::ColumnEnsemble, classes, class_map = nothing)
     cls = [lh_soil_class(Float64.(k)...) for k in classes]
     check(ens.ctx, ccall((:lh_set_soil_classes, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{lh_soil_class}),
                          ens.ctx, Int32(length(cls)), cls))
+    if thermal !== nothing     # (before the map: a coupled or heat-only context accepts a map only with it)
+        th = [lh_soil_class_thermal(t) for t in thermal]
+        check(ens.ctx, ccall((:lh_set_soil_class_thermal, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{lh_soil_class_thermal}),
+                             ens.ctx, Int32(length(th)), th))
+    end
     class_map === nothing && return ens
     m = class_map isa AbstractVector ? Vector{UInt8}(class_map) : Matrix{UInt8}(class_map)
     cs = m isa AbstractVector ? 0 : size(m, 1)    # a vector is broadcast over the columns
@@ -695,6 +725,12 @@ function soil_class_info(ens::ColumnEnsemble)
     n, has = Ref{Int32}(0), Ref{Int32}(0)
     check(ens.ctx, ccall((:lh_soil_class_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), ens.ctx, n, has))
     return Int(n[]), has[] != 0
+end
+
+function soil_class_thermal_info(ens::ColumnEnsemble)
+    has = Ref{Int32}(0)
+    check(ens.ctx, ccall((:lh_soil_class_thermal_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}), ens.ctx, has))
+    return has[] != 0
 end
 
 function stable_dt(ens::ColumnEnsemble, Y::DeviceState, Ya = nothing; courant = 0.5)

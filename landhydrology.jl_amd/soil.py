@@ -160,16 +160,56 @@ class vanGenuchten:
     θr = property(lambda s: s.theta_r)
 
 
+_THERMAL_FIELDS = ("rho_c_ds", "kappa_solid", "rho_p", "kappa_sat_unfrozen", "kappa_sat_frozen", "nu_ss_gravel",
+                   "nu_ss_om", "nu_ss_quartz")   # lh_soil_class_thermal, in its order
+
+
+class SoilThermal:
+    """The thermal supplement of a soil class (build extension): the SoilParams fields a texture changes and
+    the heat path reads, SoilThermal(FT; ρc_ds, κ_solid, ρp, κ_sat_unfrozen, κ_sat_frozen, ν_ss_gravel, ν_ss_om,
+    ν_ss_quartz) with the defaults and spellings of SoilParams.  a, b and κ_dry_parameter stay scalars of the
+    model's SoilParams.  Scalars only."""
+
+    def __init__(self, FT=Float64, **kw):
+        self.FT = np.dtype(FT).type
+        vals = {k: _SOIL_DEFAULTS[k] for k in _THERMAL_FIELDS}
+        for k, v in kw.items():
+            k = _SOIL_ALIASES.get(k, k)
+            if k not in vals:
+                raise TypeError(f"SoilThermal has no field {k!r}")
+            if np.ndim(v) != 0:
+                raise ValueError(f"SoilThermal: {k} must be a scalar (a class is one texture)")
+            vals[k] = v
+        self.__dict__.update(vals)
+
+    def numbers(self):
+        """lh_soil_class_thermal"""
+        return tuple(getattr(self, k) for k in _THERMAL_FIELDS)
+
+    ρc_ds = property(lambda s: s.rho_c_ds)
+    κ_solid = property(lambda s: s.kappa_solid)
+    ρp = property(lambda s: s.rho_p)
+    κ_sat_unfrozen = property(lambda s: s.kappa_sat_unfrozen)
+    κ_sat_frozen = property(lambda s: s.kappa_sat_frozen)
+    ν_ss_gravel = property(lambda s: s.nu_ss_gravel)
+    ν_ss_om = property(lambda s: s.nu_ss_om)
+    ν_ss_quartz = property(lambda s: s.nu_ss_quartz)
+
+
 class SoilClass:
     """One soil class of a layered soil (build extension: the reference has one SoilParams and one
     vanGenuchten per model): a hydraulic model and the two SoilParams fields a texture changes,
-    SoilClass(hydraulic_model=vanGenuchten(...), nu=, S_s=).  Scalars only."""
+    SoilClass(hydraulic_model=vanGenuchten(...), nu=, S_s=), and optionally its thermal supplement
+    (thermal=SoilThermal(...)), which a model with a SoilEnergyModel needs of every class.  Scalars only."""
 
-    def __init__(self, FT=Float64, *, hydraulic_model, nu=None, S_s=None, **kw):
+    def __init__(self, FT=Float64, *, hydraulic_model, nu=None, S_s=None, thermal=None, **kw):
         self.FT = np.dtype(FT).type
         nu = kw.pop("ν", nu)
         if kw:
             raise TypeError(f"SoilClass has no field(s) {sorted(kw)}")
+        if thermal is not None and not isinstance(thermal, SoilThermal):
+            raise TypeError("SoilClass: thermal must be a SoilThermal")
+        self.thermal = thermal
         self.hydraulic_model = hydraulic_model
         self.nu = _SOIL_DEFAULTS["nu"] if nu is None else nu
         self.S_s = _SOIL_DEFAULTS["S_s"] if S_s is None else S_s
@@ -191,7 +231,8 @@ MAX_SOIL_CLASSES = 16   # LH_MAX_SOIL_CLASSES
 class SoilClasses:
     """Layered soil (build extension): up to 16 SoilClass and the class of every cell, zero-based indices
     into `classes`.  `class_map` is [nelements] (bottom first; the same horizons in every column) or
-    [ncolumns, nelements].  SoilModel(..., soil_classes=SoilClasses(...)), Richards models only."""
+    [ncolumns, nelements].  SoilModel(..., soil_classes=SoilClasses(...)): Richards models, and models with a
+    SoilEnergyModel when every class carries its thermal supplement (SoilClass(..., thermal=SoilThermal(...)))."""
 
     def __init__(self, classes, class_map):
         self.classes = list(classes)
@@ -208,16 +249,28 @@ class SoilClasses:
                                             f"of the class map, {len(self.classes)} classes are set")
         self.class_map = np.ascontiguousarray(m, dtype=np.uint8)
 
+    @property
+    def has_thermal(self):
+        """every class carries its thermal supplement"""
+        return all(k.thermal is not None for k in self.classes)
+
 
 def _check_soil_classes(model):
     """What the library refuses for a layered context (LH_EMODEL), raised when the model is built."""
     sc = model.soil_classes
     if not isinstance(sc, SoilClasses):
         raise TypeError("soil_classes must be a SoilClasses")
-    if not (isinstance(model.energy_model, PrescribedTemperatureModel) and isinstance(model.hydrology_model, SoilHydrologyModel)):
+    richards = isinstance(model.energy_model, PrescribedTemperatureModel) and isinstance(model.hydrology_model, SoilHydrologyModel)
+    if not richards and not (isinstance(model.energy_model, SoilEnergyModel) and sc.has_thermal):
         raise F.ModelError(F.LH_EMODEL, "soil classes are for Richards models only (SoilHydrologyModel + "
-                                        "PrescribedTemperatureModel): the heat closures read the porosity")
-    hm, sp = model.hydrology_model.hydraulic_model, model.soil_param_set
+                                        "PrescribedTemperatureModel): the heat closures read the porosity -- unless every "
+                                        "class carries its thermal supplement (SoilClass(..., thermal=SoilThermal(...)))")
+    bcs = model.boundary_conditions
+    if bcs is not None and isinstance(bcs.top, PrescribedAtmosForcing):
+        raise F.ModelError(F.LH_EMODEL, "soil classes cannot be combined with a prescribed-atmosphere top")
+    sp = model.soil_param_set
+    vg = getattr(model.hydrology_model, "hydraulic_model", None)
+    hm = vg if vg is not None else vanGenuchten(sp.FT)
     for name, v in (("n", hm.n), ("alpha", hm.alpha), ("theta_r", hm.theta_r), ("Ksat", hm.Ksat), ("nu", sp.nu), ("S_s", sp.S_s)):
         if np.ndim(v) != 0:
             raise F.ModelError(F.LH_EMODEL, f"soil classes cannot be combined with per-column parameter arrays ({name})")
@@ -230,6 +283,9 @@ def _check_soil_classes(model):
 def _refuse_soil_classes(model, name):
     """The integrators and tools that have no layered kernels (LH_EMODEL in the library)."""
     if getattr(model, "soil_classes", None) is not None:
+        if isinstance(model.energy_model, SoilEnergyModel):    # (the layered implicit integrators step Richards models)
+            raise NotImplementedError(f"{name} is not available with soil classes (a layered coupled or heat-only model "
+                                      "steps with SSPRK33)")
         raise NotImplementedError(f"{name} is not available with soil classes (layered soils step with SSPRK33, "
                                   "LayeredImplicitEuler or LayeredTRBDF2)")
 
@@ -601,6 +657,10 @@ class _Backend:
         if sc is not None:
             arr = (F.lh_soil_class * len(sc.classes))(*[F.lh_soil_class(*[float(x) for x in k.numbers()]) for k in sc.classes])
             F.check(L.lh_set_soil_classes(ctx, len(sc.classes), arr), ctx)
+            if sc.has_thermal:   # (a Richards context ignores it; a model with an energy component needs it for the map)
+                th = (F.lh_soil_class_thermal * len(sc.classes))(
+                    *[F.lh_soil_class_thermal(*[float(x) for x in k.thermal.numbers()]) for k in sc.classes])
+                F.check(L.lh_set_soil_class_thermal(ctx, len(sc.classes), th), ctx)
             m = sc.class_map    # [nelements]: a zero column stride broadcasts it over the columns
             F.check(L.lh_set_soil_class_map(ctx, m.ctypes.data_as(C.POINTER(C.c_uint8)), 1,
                                             0 if m.ndim == 1 else d.nelements), ctx)

@@ -384,18 +384,30 @@ class GpuModel:
                     p = pc.ctypes.data_as(C.POINTER(C.c_double))
                 F.check(L.lh_set_bc(ctx, f, k, kind, float(val), p), ctx)
 
-    def set_soil_classes(self, classes, class_map=None):
+    def set_soil_classes(self, classes, class_map=None, thermal=None):
         """Layered soils: `classes` is a sequence of (n, alpha, theta_r, Ksat, nu, S_s), `class_map` an
         integer array [ncols, nlev] or [nlev] (the same horizons in every column) of indices into it;
-        classes = None removes both, class_map = None leaves (or, after new classes, keeps) the map."""
+        classes = None removes both, class_map = None leaves (or, after new classes, keeps) the map.
+        `thermal`: one (rho_c_ds, kappa_solid, rho_p, kappa_sat_unfrozen, kappa_sat_frozen, nu_ss_gravel,
+        nu_ss_om, nu_ss_quartz) per class, the supplement a coupled or heat-only context needs for a map."""
         F, L, ctx = self.F, self.L, self.ctx
         if classes is None:
             F.check(L.lh_set_soil_classes(ctx, 0, None), ctx)
             return
         arr = (F.lh_soil_class * len(classes))(*[F.lh_soil_class(*[float(x) for x in k]) for k in classes])
         F.check(L.lh_set_soil_classes(ctx, len(classes), arr), ctx)
+        if thermal is not None:
+            self.set_soil_class_thermal(thermal)
         if class_map is not None:
             self.set_soil_class_map(class_map)
+
+    def set_soil_class_thermal(self, thermal):
+        F, L, ctx = self.F, self.L, self.ctx
+        if thermal is None:
+            F.check(L.lh_set_soil_class_thermal(ctx, 0, None), ctx)
+            return
+        arr = (F.lh_soil_class_thermal * len(thermal))(*[F.lh_soil_class_thermal(*[float(x) for x in k]) for k in thermal])
+        F.check(L.lh_set_soil_class_thermal(ctx, len(thermal), arr), ctx)
 
     def set_soil_class_map(self, class_map):
         F, L, ctx = self.F, self.L, self.ctx
