@@ -958,6 +958,47 @@ void carve_planes(void* block, size_t pl, std::initializer_list<FT**> names) {
     }
 }
 
+// ---- how the implicit entry points fill what their launch arguments share
+
+// the water planes of Y, which every Newton launch iterates on
+template <typename FT, typename ARGS>
+void point_at_water(const lh_state* Y, ARGS& A) {
+    A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
+    A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+}
+// the three Newton counters of ImplicitArgs / CoupledImplicitArgs, pointed into the context's ImplicitStats block
+template <typename ARGS>
+void point_at_newton_stats(const lh_ctx* c, ARGS& A) {
+    ImplicitStats* const st = static_cast<ImplicitStats*>(c->d_imp_stats); // (device memory: addresses only)
+    A.max_iters = &st->max_iters;
+    A.unconverged = &st->unconverged;
+    A.total_iters = &st->total_iters;
+}
+
+// lh_integrate_trbdf2's defaults (DESIGN section 4.13; LH_TUNE trk= / trn= override the Newton pair)
+#define LH_TRBDF2_ABSTOL_DEFAULT 1e-6
+#define LH_TRBDF2_RELTOL_DEFAULT 1e-3
+#define LH_TRBDF2_NEWTON_KAPPA 0.01 // stage Newton test: max |delta| / (atol + rtol |Y|) <= this ...
+#define LH_TRBDF2_NEWTON_MAX 10     // ... within this many iterations, else the step is rejected
+
+// what Trbdf2Args and CoupledTrbdf2Args share besides the planes: the interval, the water's tolerances, the boundary
+// table, the stage Newton test and the statistics block
+template <typename FT, typename ARGS>
+void fill_trbdf2_args(const lh_ctx* c, ARGS& A, double t0, double t1, double dt, double abstol, double reltol,
+                      void* dt_cols_device_ft, const double* bcv) {
+    A.dt_cols = static_cast<FT*>(dt_cols_device_ft);
+    A.t0 = t0;
+    A.t1 = t1;
+    A.dt = dt;
+    A.abstol = abstol;
+    A.reltol = reltol;
+    A.has_bcv = bcv != nullptr;
+    for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
+    A.kappa = FT(c->tune.trk > 0 ? 1e-4 * c->tune.trk : LH_TRBDF2_NEWTON_KAPPA);
+    A.newton_max = c->tune.trn > 0 ? c->tune.trn : LH_TRBDF2_NEWTON_MAX;
+    A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
+}
+
 int upload_percol(lh_ctx* c, void** slot, const double* host) {
     if (*slot) {
         LH_HIP(c, hipStreamSynchronize(c->stream));
@@ -2118,15 +2159,27 @@ int lh_step_ssprk33_adaptive_hold(lh_ctx* c, lh_state* Y, const lh_state* Ya, do
     return LH_OK;
 }
 
-// ---- what lh_step_implicit_euler and lh_integrate_trbdf2 share on the host
+// ---- what the implicit entry points share on the host
 
-// They and lh_step_coupled_implicit refuse the same configurations and states, in this order (`who`: the entry
-// point, for lh_last_error; `model`, `models`: the one model it steps and the words for it)
-static int implicit_refusals(lh_ctx* c, const char* who, const lh_state* Y, const lh_state* Ya,
-                             int model = LH_MODEL_RICHARDS,
-                             const char* models = "Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)") {
-    if (c->cfg.model != model) return fail(c, LH_EMODEL, "%s: %s", who, models);
-    if (int rc = layered_unsupported(c, who)) return rc;
+static const char* const RICHARDS_MODELS = "Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)";
+static const char* const COUPLED_MODELS = "coupled models only (SoilEnergyModel + SoilHydrologyModel)";
+
+// The Newton calls (all but lh_step_heat_implicit) refuse the same configurations and states, in this order.  `who`:
+// the entry point, for lh_last_error; `model`, `models`: the one model it steps and the words for it; `scalar`: NULL
+// for a call that steps contexts without a class map, else (a layered call, which needs the map) the call that does
+static int implicit_refusals(lh_ctx* c, const char* who, const lh_state* Y, const lh_state* Ya, int model, const char* models,
+                             const char* scalar = nullptr) {
+    if (c->cfg.model != model)
+        return scalar && layered(c)
+                   ? fail(c, LH_EMODEL, "%s is not available with soil classes (a class map is set) on this model: it steps %s", who, models)
+                   : fail(c, LH_EMODEL, "%s: %s", who, models);
+    if (scalar) {
+        if (!layered(c))
+            return fail(c, LH_EMODEL, "%s: the context has no class map (lh_set_soil_class_map); %s steps a model without soil classes",
+                        who, scalar);
+        if (int rc = layered_check(c, who)) return rc;
+    } else if (int rc = layered_unsupported(c, who))
+        return rc;
     if (c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE)
         return fail(c, LH_EMODEL, "%s: conductivity factors other than NoEffect are not supported", who);
     // (validate_model refuses a prescribed atmosphere on any model but the coupled one already; kept so
@@ -2170,17 +2223,47 @@ static bool implicit_noice(const lh_ctx* c, const lh_state* Y) {
     return c->tune.zero != 0 && (Y->zero_mask & LH_MASK(LH_VAR_THETA_I));
 }
 
-int lh_step_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
-                           const double* bcv, double tol, int32_t max_iter) {
-    (void)t; // boundary values of t_{n+1} come through bcv or lh_set_bc, as for lh_step_ssprk33
+// lh_step_implicit_euler's Newton test where the caller passes none (tol <= 0, max_iter <= 0): also
+// lh_step_coupled_implicit's, and the fixed mode of the TR-BDF2 calls
+static void newton_defaults(const lh_ctx* c, double& tol, int32_t& max_iter) {
+    if (!(tol > 0)) tol = c->cfg.dtype == LH_F64 ? 1e-10 : 1e-5;
+    if (max_iter <= 0) max_iter = 50;
+}
+// the argument checks of lh_step_heat_implicit and lh_step_coupled_implicit (`allowed`: the call's TR-BDF2 flag)
+static int fixed_step_argument_refusals(lh_ctx* c, const char* who, int64_t nsteps, double dt, uint32_t flags, uint32_t allowed) {
+    if (nsteps < 0 || !std::isfinite(dt) || !(dt > 0)) return fail(c, LH_EINVAL, "%s: need nsteps >= 0 and a finite dt > 0", who);
+    if (flags & ~allowed) return fail(c, LH_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    return LH_OK;
+}
+// ... and the coefficient of their stage solves: dt (backward Euler) or (2 - sqrt 2)/2 dt (both TR-BDF2 stages)
+static double stage_coefficient(bool trbdf2, double dt) { return trbdf2 ? 0.5 * (2.0 - 1.4142135623730951) * dt : dt; }
+// The last line of every implicit call: the fixed-step ones hand it launch_error(c, d_bcv), the adaptive ones (which
+// upload no table) hipGetLastError(); `launch` names the launch in lh_last_error
+static int launch_status(lh_ctx* c, hipError_t e, const char* launch) {
+    return e == hipSuccess ? LH_OK : fail(c, LH_ENODEVICE, "%s launch failed: %s", launch, hipGetErrorString(e));
+}
+
+// The two Richards calls exist twice, for contexts without and with a class map (lh_implicit.hpp,
+// lh_layered_implicit.hpp), on the same scratch and statistics blocks.  One body each; what a
+// layered entry point words or does differently is its flavour: besides the names below, implicit_refusals' list for
+// a context that must hold a map, layered_params, and the launcher that takes layered_args.
+struct RichardsFlavour {
+    const char* who;    // the entry point, for lh_last_error
+    const char* scalar; // a layered call: the call for a context without a class map; NULL for that call itself
+    const char* range;  // the roctx range
+    const char* launch; // the launch, in the words of its failure message
+    bool layered() const { return scalar != nullptr; }
+};
+
+static int richards_implicit_euler(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, const lh_state* Ya, double dt,
+                                   int64_t nsteps, const double* bcv, double tol, int32_t max_iter) {
     if (!c) return LH_EINVAL;
     int rc = zero_stats(c, c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24");
     if (rc) return rc;
-    if (nsteps < 0 || !(dt > 0)) return fail(c, LH_EINVAL, "lh_step_implicit_euler: need nsteps >= 0 and dt > 0");
-    Range r_("lh:step_implicit_euler");
-    if ((rc = implicit_refusals(c, "lh_step_implicit_euler", Y, Ya))) return rc;
-    if (!(tol > 0)) tol = c->cfg.dtype == LH_F64 ? 1e-10 : 1e-5;
-    if (max_iter <= 0) max_iter = 50;
+    if (nsteps < 0 || !(dt > 0)) return fail(c, LH_EINVAL, "%s: need nsteps >= 0 and dt > 0", fl.who);
+    Range r_(fl.range);
+    if ((rc = implicit_refusals(c, fl.who, Y, Ya, LH_MODEL_RICHARDS, RICHARDS_MODELS, fl.scalar))) return rc;
+    newton_defaults(c, tol, max_iter);
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
     if ((rc = ensure_scratch(c, &c->d_imp, 3 * pl * c->esize, "c->d_imp", "3 * plane"))) return rc;
     if ((rc = ensure_scratch(c, &c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24", true))) return rc;
@@ -2191,25 +2274,36 @@ int lh_step_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t,
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
-        ImplicitStats* const st = static_cast<ImplicitStats*>(c->d_imp_stats); // (device memory: addresses only)
+        if (fl.layered()) layered_params<FT>(c, P);
         ImplicitArgs<FT> A;
-        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
-        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+        point_at_water<FT>(Y, A);
         carve_planes<FT>(c->d_imp, pl, {&A.yn, &A.cp, &A.dp});
         A.bcv = static_cast<const FT*>(d_bcv.p);
         A.dt = FT(dt);
         A.tol = FT(tol);
         A.max_iter = max_iter;
         A.nsteps = nsteps;
-        A.max_iters = &st->max_iters;
-        A.unconverged = &st->unconverged;
-        A.total_iters = &st->total_iters;
-        launch_implicit_euler<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+        point_at_newton_stats(c, A);
+        if (fl.layered()) launch_layered_implicit_euler<FT>(P, layered_args<FT>(c), A, implicit_noice(c, Y), c->stream);
+        else launch_implicit_euler<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
-    const hipError_t e = launch_error(c, d_bcv);
-    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "implicit Euler launch failed: %s", hipGetErrorString(e));
-    return LH_OK;
+    return launch_status(c, launch_error(c, d_bcv), fl.launch);
+}
+
+int lh_step_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                           const double* bcv, double tol, int32_t max_iter) {
+    (void)t; // boundary values of t_{n+1} come through bcv or lh_set_bc, as for lh_step_ssprk33
+    static const RichardsFlavour fl = {"lh_step_implicit_euler", nullptr, "lh:step_implicit_euler", "implicit Euler"};
+    return richards_implicit_euler(c, fl, Y, Ya, dt, nsteps, bcv, tol, max_iter);
+}
+
+int lh_step_layered_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                                   const double* bcv, double tol, int32_t max_iter) {
+    (void)t; // as for lh_step_implicit_euler
+    static const RichardsFlavour fl = {"lh_step_layered_implicit_euler", "lh_step_implicit_euler",
+                                       "lh:step_layered_implicit_euler", "layered implicit Euler"};
+    return richards_implicit_euler(c, fl, Y, Ya, dt, nsteps, bcv, tol, max_iter);
 }
 
 int lh_implicit_iterations(lh_ctx* c, int64_t* iterations) {
@@ -2229,65 +2323,74 @@ int lh_implicit_stats(lh_ctx* c, int32_t* max_iters, int64_t* unconverged) {
     return rc;
 }
 
-// lh_integrate_trbdf2's defaults (DESIGN section 4.13; LH_TUNE trk= / trn= override the Newton pair)
-#define LH_TRBDF2_ABSTOL_DEFAULT 1e-6
-#define LH_TRBDF2_RELTOL_DEFAULT 1e-3
-#define LH_TRBDF2_NEWTON_KAPPA 0.01 // stage Newton test: max |delta| / (atol + rtol |Y|) <= this ...
-#define LH_TRBDF2_NEWTON_MAX 10     // ... within this many iterations, else the step is rejected
+static const size_t TRBDF2_STATS_BYTES = LH_TRBDF2_NSTATS * sizeof(uint64_t);
 
-int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
-                        double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
-    if (!c) return LH_EINVAL;
-    const size_t nstat = LH_TRBDF2_NSTATS * sizeof(uint64_t);
-    int rc = zero_stats(c, c->d_tr_stats, nstat, "c->d_tr_stats", "nstat");
-    if (rc) return rc;
-    if (!std::isfinite(t0) || !std::isfinite(t1) || !(t1 >= t0))
-        return fail(c, LH_EINVAL, "lh_integrate_trbdf2: need finite t0 <= t1");
-    if (!std::isfinite(dt) || !(dt > 0)) return fail(c, LH_EINVAL, "lh_integrate_trbdf2: need a finite dt > 0");
-    if (!std::isfinite(abstol) || !std::isfinite(reltol) || abstol < 0 || reltol < 0)
-        return fail(c, LH_EINVAL, "lh_integrate_trbdf2: tolerances must be finite and >= 0");
-    if (flags & ~LH_TRBDF2_FIXED) return fail(c, LH_EINVAL, "lh_integrate_trbdf2: unknown flags 0x%x", flags);
+// The argument checks of the three adaptive calls, in this order.  `tols`: every tolerance the call takes; `allowed`:
+// the flags it knows (lh_integrate_coupled_trbdf2: none, its fixed steps are lh_step_coupled_implicit's LH_COUPLED_TRBDF2)
+static int trbdf2_argument_refusals(lh_ctx* c, const char* who, double t0, double t1, double dt, std::initializer_list<double> tols,
+                                    uint32_t flags, uint32_t allowed, const double* bcv) {
+    if (!std::isfinite(t0) || !std::isfinite(t1) || !(t1 >= t0)) return fail(c, LH_EINVAL, "%s: need finite t0 <= t1", who);
+    if (!std::isfinite(dt) || !(dt > 0)) return fail(c, LH_EINVAL, "%s: need a finite dt > 0", who);
+    for (const double tol : tols)
+        if (!std::isfinite(tol) || tol < 0) return fail(c, LH_EINVAL, "%s: tolerances must be finite and >= 0", who);
+    if (flags & ~allowed) return fail(c, LH_EINVAL, "%s: unknown flags 0x%x", who, flags);
     if (bcv)
         for (int k = 0; k < 8; ++k)
-            if (!std::isfinite(bcv[k])) return fail(c, LH_EINVAL, "lh_integrate_trbdf2: non-finite boundary value");
-    Range r_("lh:integrate_trbdf2");
-    if ((rc = implicit_refusals(c, "lh_integrate_trbdf2", Y, Ya))) return rc;
-    const bool fixed = (flags & LH_TRBDF2_FIXED) != 0;
-    // each tolerance that is 0 takes its own default (OrdinaryDiffEq's)
+            if (!std::isfinite(bcv[k])) return fail(c, LH_EINVAL, "%s: non-finite boundary value", who);
+    return LH_OK;
+}
+// each tolerance that is 0 takes its own default (OrdinaryDiffEq's)
+static void trbdf2_tolerance_defaults(double& abstol, double& reltol) {
     if (!(abstol > 0)) abstol = LH_TRBDF2_ABSTOL_DEFAULT;
     if (!(reltol > 0)) reltol = LH_TRBDF2_RELTOL_DEFAULT;
+}
+
+static int richards_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, const lh_state* Ya, double t0, double t1,
+                           double dt, double abstol, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    if (!c) return LH_EINVAL;
+    int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
+    if (rc) return rc;
+    if ((rc = trbdf2_argument_refusals(c, fl.who, t0, t1, dt, {abstol, reltol}, flags, LH_TRBDF2_FIXED, bcv))) return rc;
+    Range r_(fl.range);
+    if ((rc = implicit_refusals(c, fl.who, Y, Ya, LH_MODEL_RICHARDS, RICHARDS_MODELS, fl.scalar))) return rc;
+    trbdf2_tolerance_defaults(abstol, reltol);
+    double tol = 0; // (fixed mode: lh_step_implicit_euler's defaults)
+    int32_t max_iter = 0;
+    newton_defaults(c, tol, max_iter);
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
     if ((rc = ensure_scratch(c, &c->d_tr, 6 * pl * c->esize, "c->d_tr", "6 * plane"))) return rc;
-    if ((rc = ensure_scratch(c, &c->d_tr_stats, nstat, "c->d_tr_stats", "nstat", true))) return rc;
+    if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
     if (t1 == t0) return LH_OK;
     if ((rc = materialize(c, Y, ~0u))) return rc;
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
+        if (fl.layered()) layered_params<FT>(c, P);
         Trbdf2Args<FT> A;
-        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
-        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+        point_at_water<FT>(Y, A);
         carve_planes<FT>(c->d_tr, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp});
-        A.dt_cols = static_cast<FT*>(dt_cols_device_ft);
-        A.t0 = t0;
-        A.t1 = t1;
-        A.dt = dt;
-        A.abstol = abstol;
-        A.reltol = reltol;
-        A.has_bcv = bcv != nullptr;
-        for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
-        A.fixed = fixed;
-        A.tol = FT(sizeof(FT) == 8 ? 1e-10 : 1e-5); // (fixed mode: lh_step_implicit_euler's defaults)
-        A.max_iter = 50;
-        A.kappa = FT(c->tune.trk > 0 ? 1e-4 * c->tune.trk : LH_TRBDF2_NEWTON_KAPPA);
-        A.newton_max = c->tune.trn > 0 ? c->tune.trn : LH_TRBDF2_NEWTON_MAX;
-        A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
-        launch_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+        fill_trbdf2_args<FT>(c, A, t0, t1, dt, abstol, reltol, dt_cols_device_ft, bcv);
+        A.fixed = (flags & LH_TRBDF2_FIXED) != 0;
+        A.tol = FT(tol);
+        A.max_iter = max_iter;
+        if (fl.layered()) launch_layered_trbdf2<FT>(P, layered_args<FT>(c), A, implicit_noice(c, Y), c->stream);
+        else launch_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "TR-BDF2 launch failed: %s", hipGetErrorString(e));
-    return LH_OK;
+    return launch_status(c, hipGetLastError(), fl.launch);
+}
+
+int lh_integrate_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
+                        double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    static const RichardsFlavour fl = {"lh_integrate_trbdf2", nullptr, "lh:integrate_trbdf2", "TR-BDF2"};
+    return richards_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol, reltol, flags, dt_cols_device_ft, bcv);
+}
+
+int lh_integrate_layered_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
+                                double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    static const RichardsFlavour fl = {"lh_integrate_layered_trbdf2", "lh_integrate_trbdf2", "lh:integrate_layered_trbdf2",
+                                       "layered TR-BDF2"};
+    return richards_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol, reltol, flags, dt_cols_device_ft, bcv);
 }
 
 int lh_trbdf2_stats(lh_ctx* c, int64_t* stats) {
@@ -2298,138 +2401,18 @@ int lh_trbdf2_stats(lh_ctx* c, int64_t* stats) {
     return rc;
 }
 
-// ---- the implicit integrators of layered soils (lh_layered_implicit.hpp): the two calls above
-// with the layered kernels, on the same scratch and statistics blocks
-
-// implicit_refusals' order for a context that must hold a class map (`scalar`: the call for one that does not)
-static int layered_implicit_refusals(lh_ctx* c, const char* who, const char* scalar, const lh_state* Y, const lh_state* Ya) {
-    if (c->cfg.model != LH_MODEL_RICHARDS && layered(c))
-        return fail(c, LH_EMODEL, "%s is not available with soil classes (a class map is set) on this model: it steps Richards models "
-                                  "only (SoilHydrologyModel + PrescribedTemperatureModel)", who);
-    if (c->cfg.model != LH_MODEL_RICHARDS)
-        return fail(c, LH_EMODEL, "%s: Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)", who);
-    if (!layered(c))
-        return fail(c, LH_EMODEL, "%s: the context has no class map (lh_set_soil_class_map); %s steps a model without soil classes",
-                    who, scalar);
-    if (int rc = layered_check(c, who)) return rc;
-    if (c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE)
-        return fail(c, LH_EMODEL, "%s: conductivity factors other than NoEffect are not supported", who);
-    if (c->hp.atmos_on) return fail(c, LH_EMODEL, "%s: a prescribed-atmosphere top is not supported", who);
-    return stepping_preamble(c, Y, Ya);
-}
-
-int lh_step_layered_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
-                                   const double* bcv, double tol, int32_t max_iter) {
-    (void)t; // boundary values of t_{n+1} come through bcv or lh_set_bc, as for lh_step_implicit_euler
-    if (!c) return LH_EINVAL;
-    int rc = zero_stats(c, c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24");
-    if (rc) return rc;
-    if (nsteps < 0 || !(dt > 0)) return fail(c, LH_EINVAL, "lh_step_layered_implicit_euler: need nsteps >= 0 and dt > 0");
-    Range r_("lh:step_layered_implicit_euler");
-    if ((rc = layered_implicit_refusals(c, "lh_step_layered_implicit_euler", "lh_step_implicit_euler", Y, Ya))) return rc;
-    if (!(tol > 0)) tol = c->cfg.dtype == LH_F64 ? 1e-10 : 1e-5;
-    if (max_iter <= 0) max_iter = 50;
-    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
-    if ((rc = ensure_scratch(c, &c->d_imp, 3 * pl * c->esize, "c->d_imp", "3 * plane"))) return rc;
-    if ((rc = ensure_scratch(c, &c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24", true))) return rc;
-    if (nsteps == 0) return LH_OK;
-    if ((rc = materialize(c, Y, ~0u))) return rc;
-    DeviceBuffer d_bcv; // [nsteps][2][2] doubles -> FT on the device
-    if (bcv && (rc = upload_boundary_values(c, bcv, size_t(nsteps) * 4, d_bcv))) return rc;
-    with_ft(c, [&](auto ft) {
-        using FT = decltype(ft);
-        DevParams<FT> P = make_params<FT>(c);
-        layered_params<FT>(c, P);
-        ImplicitStats* const st = static_cast<ImplicitStats*>(c->d_imp_stats); // (device memory: addresses only)
-        ImplicitArgs<FT> A;
-        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
-        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
-        carve_planes<FT>(c->d_imp, pl, {&A.yn, &A.cp, &A.dp});
-        A.bcv = static_cast<const FT*>(d_bcv.p);
-        A.dt = FT(dt);
-        A.tol = FT(tol);
-        A.max_iter = max_iter;
-        A.nsteps = nsteps;
-        A.max_iters = &st->max_iters;
-        A.unconverged = &st->unconverged;
-        A.total_iters = &st->total_iters;
-        launch_layered_implicit_euler<FT>(P, layered_args<FT>(c), A, implicit_noice(c, Y), c->stream);
-    });
-    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
-    const hipError_t e = launch_error(c, d_bcv);
-    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "layered implicit Euler launch failed: %s", hipGetErrorString(e));
-    return LH_OK;
-}
-
-int lh_integrate_layered_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
-                                double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
-    if (!c) return LH_EINVAL;
-    const size_t nstat = LH_TRBDF2_NSTATS * sizeof(uint64_t);
-    int rc = zero_stats(c, c->d_tr_stats, nstat, "c->d_tr_stats", "nstat");
-    if (rc) return rc;
-    if (!std::isfinite(t0) || !std::isfinite(t1) || !(t1 >= t0))
-        return fail(c, LH_EINVAL, "lh_integrate_layered_trbdf2: need finite t0 <= t1");
-    if (!std::isfinite(dt) || !(dt > 0)) return fail(c, LH_EINVAL, "lh_integrate_layered_trbdf2: need a finite dt > 0");
-    if (!std::isfinite(abstol) || !std::isfinite(reltol) || abstol < 0 || reltol < 0)
-        return fail(c, LH_EINVAL, "lh_integrate_layered_trbdf2: tolerances must be finite and >= 0");
-    if (flags & ~LH_TRBDF2_FIXED) return fail(c, LH_EINVAL, "lh_integrate_layered_trbdf2: unknown flags 0x%x", flags);
-    if (bcv)
-        for (int k = 0; k < 8; ++k)
-            if (!std::isfinite(bcv[k])) return fail(c, LH_EINVAL, "lh_integrate_layered_trbdf2: non-finite boundary value");
-    Range r_("lh:integrate_layered_trbdf2");
-    if ((rc = layered_implicit_refusals(c, "lh_integrate_layered_trbdf2", "lh_integrate_trbdf2", Y, Ya))) return rc;
-    const bool fixed = (flags & LH_TRBDF2_FIXED) != 0;
-    // each tolerance that is 0 takes its own default, as lh_integrate_trbdf2's
-    if (!(abstol > 0)) abstol = LH_TRBDF2_ABSTOL_DEFAULT;
-    if (!(reltol > 0)) reltol = LH_TRBDF2_RELTOL_DEFAULT;
-    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
-    if ((rc = ensure_scratch(c, &c->d_tr, 6 * pl * c->esize, "c->d_tr", "6 * plane"))) return rc;
-    if ((rc = ensure_scratch(c, &c->d_tr_stats, nstat, "c->d_tr_stats", "nstat", true))) return rc;
-    if (t1 == t0) return LH_OK;
-    if ((rc = materialize(c, Y, ~0u))) return rc;
-    with_ft(c, [&](auto ft) {
-        using FT = decltype(ft);
-        DevParams<FT> P = make_params<FT>(c);
-        layered_params<FT>(c, P);
-        Trbdf2Args<FT> A;
-        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
-        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
-        carve_planes<FT>(c->d_tr, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp});
-        A.dt_cols = static_cast<FT*>(dt_cols_device_ft);
-        A.t0 = t0;
-        A.t1 = t1;
-        A.dt = dt;
-        A.abstol = abstol;
-        A.reltol = reltol;
-        A.has_bcv = bcv != nullptr;
-        for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
-        A.fixed = fixed;
-        A.tol = FT(sizeof(FT) == 8 ? 1e-10 : 1e-5); // (fixed mode: lh_step_implicit_euler's defaults)
-        A.max_iter = 50;
-        A.kappa = FT(c->tune.trk > 0 ? 1e-4 * c->tune.trk : LH_TRBDF2_NEWTON_KAPPA);
-        A.newton_max = c->tune.trn > 0 ? c->tune.trn : LH_TRBDF2_NEWTON_MAX;
-        A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
-        launch_layered_trbdf2<FT>(P, layered_args<FT>(c), A, implicit_noice(c, Y), c->stream);
-    });
-    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "layered TR-BDF2 launch failed: %s", hipGetErrorString(e));
-    return LH_OK;
-}
-
 int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
                           uint32_t flags, const double* bcv) {
     (void)t; // boundary values come through bcv or lh_set_bc, as for lh_step_implicit_euler
     if (!c) return LH_EINVAL;
-    if (nsteps < 0 || !std::isfinite(dt) || !(dt > 0))
-        return fail(c, LH_EINVAL, "lh_step_heat_implicit: need nsteps >= 0 and a finite dt > 0");
-    if (flags & ~LH_HEAT_TRBDF2) return fail(c, LH_EINVAL, "lh_step_heat_implicit: unknown flags 0x%x", flags);
-    Range r_("lh:step_heat_implicit");
-    if (c->cfg.model != LH_MODEL_HEAT)
-        return fail(c, LH_EMODEL, "lh_step_heat_implicit: heat-only models (SoilEnergyModel + PrescribedHydrologyModel)");
-    int rc = stepping_preamble(c, Y, Ya);
+    static const char* const who = "lh_step_heat_implicit";
+    int rc = fixed_step_argument_refusals(c, who, nsteps, dt, flags, LH_HEAT_TRBDF2);
     if (rc) return rc;
-    if ((rc = layered_unsupported(c, "lh_step_heat_implicit"))) return rc;
+    Range r_("lh:step_heat_implicit");
+    // (its own order, not implicit_refusals': the model, the states, then the class map)
+    if (c->cfg.model != LH_MODEL_HEAT) return fail(c, LH_EMODEL, "%s: heat-only models (SoilEnergyModel + PrescribedHydrologyModel)", who);
+    if ((rc = stepping_preamble(c, Y, Ya))) return rc;
+    if ((rc = layered_unsupported(c, who))) return rc;
     if (nsteps == 0) return LH_OK;
     const bool trbdf2 = (flags & LH_HEAT_TRBDF2) != 0;
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
@@ -2447,32 +2430,26 @@ int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, 
         A.ti = static_cast<const FT*>(Ya->plane[LH_VAR_THETA_I]);
         carve_planes<FT>(c->d_heat, pl, {&A.a, &A.iden, &A.cp, &A.kc, &A.z, &A.ks, &A.al, &A.be});
         A.bcv = static_cast<const FT*>(d_bcv.p);
-        A.coef = FT(trbdf2 ? 0.5 * (2.0 - 1.4142135623730951) * dt : dt);
+        A.coef = FT(stage_coefficient(trbdf2, dt));
         A.nsteps = nsteps;
         launch_heat_implicit<FT>(P, A, any_percol(c), trbdf2, c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_RHOE_INT));
-    const hipError_t e = launch_error(c, d_bcv);
-    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "heat implicit launch failed: %s", hipGetErrorString(e));
-    return LH_OK;
+    return launch_status(c, launch_error(c, d_bcv), "heat implicit");
 }
 
 int lh_step_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
                              uint32_t flags, const double* bcv, double tol, int32_t max_iter) {
     (void)t; // boundary values come through bcv or lh_set_bc, as for lh_step_heat_implicit
     if (!c) return LH_EINVAL;
+    static const char* const who = "lh_step_coupled_implicit";
     int rc = zero_stats(c, c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24");
     if (rc) return rc;
-    if (nsteps < 0 || !std::isfinite(dt) || !(dt > 0))
-        return fail(c, LH_EINVAL, "lh_step_coupled_implicit: need nsteps >= 0 and a finite dt > 0");
-    if (flags & ~LH_COUPLED_TRBDF2) return fail(c, LH_EINVAL, "lh_step_coupled_implicit: unknown flags 0x%x", flags);
+    if ((rc = fixed_step_argument_refusals(c, who, nsteps, dt, flags, LH_COUPLED_TRBDF2))) return rc;
     Range r_("lh:step_coupled_implicit");
     // (with a viscosity factor the water reads T: the Jacobian is no longer block triangular)
-    if ((rc = implicit_refusals(c, "lh_step_coupled_implicit", Y, Ya, LH_MODEL_COUPLED,
-                                "coupled models only (SoilEnergyModel + SoilHydrologyModel)")))
-        return rc;
-    if (!(tol > 0)) tol = c->cfg.dtype == LH_F64 ? 1e-10 : 1e-5; // lh_step_implicit_euler's defaults
-    if (max_iter <= 0) max_iter = 50;
+    if ((rc = implicit_refusals(c, who, Y, Ya, LH_MODEL_COUPLED, COUPLED_MODELS))) return rc;
+    newton_defaults(c, tol, max_iter);
     const bool trbdf2 = (flags & LH_COUPLED_TRBDF2) != 0;
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
     if ((rc = ensure_scratch(c, &c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24", true))) return rc;
@@ -2485,85 +2462,54 @@ int lh_step_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
-        ImplicitStats* const st = static_cast<ImplicitStats*>(c->d_imp_stats); // (device memory: addresses only)
         CoupledImplicitArgs<FT> A;
-        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
-        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+        point_at_water<FT>(Y, A);
         A.e = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
         carve_planes<FT>(c->d_cpl, pl, {&A.w, &A.cp, &A.dp});
         A.yn = A.fn = A.fe = A.we = nullptr;
         if (trbdf2) carve_planes<FT>(c->d_cpl_tr, pl, {&A.yn, &A.fn, &A.fe, &A.we});
         A.bcv = static_cast<const FT*>(d_bcv.p);
-        A.coef = FT(trbdf2 ? 0.5 * (2.0 - 1.4142135623730951) * dt : dt);
+        A.coef = FT(stage_coefficient(trbdf2, dt));
         A.tol = FT(tol);
         A.max_iter = max_iter;
         A.nsteps = nsteps;
-        A.max_iters = &st->max_iters;
-        A.unconverged = &st->unconverged;
-        A.total_iters = &st->total_iters;
+        point_at_newton_stats(c, A);
         launch_coupled_implicit<FT>(P, A, any_percol(c), implicit_noice(c, Y), trbdf2, c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
-    const hipError_t e = launch_error(c, d_bcv);
-    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "coupled implicit launch failed: %s", hipGetErrorString(e));
-    return LH_OK;
+    return launch_status(c, launch_error(c, d_bcv), "coupled implicit");
 }
 
 int lh_integrate_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
                                 double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
     if (!c) return LH_EINVAL;
-    const size_t nstat = LH_TRBDF2_NSTATS * sizeof(uint64_t);
-    int rc = zero_stats(c, c->d_tr_stats, nstat, "c->d_tr_stats", "nstat");
+    static const char* const who = "lh_integrate_coupled_trbdf2";
+    int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
     if (rc) return rc;
-    if (!std::isfinite(t0) || !std::isfinite(t1) || !(t1 >= t0))
-        return fail(c, LH_EINVAL, "lh_integrate_coupled_trbdf2: need finite t0 <= t1");
-    if (!std::isfinite(dt) || !(dt > 0)) return fail(c, LH_EINVAL, "lh_integrate_coupled_trbdf2: need a finite dt > 0");
-    if (!std::isfinite(abstol) || !std::isfinite(abstol_e) || !std::isfinite(reltol) || abstol < 0 || abstol_e < 0 || reltol < 0)
-        return fail(c, LH_EINVAL, "lh_integrate_coupled_trbdf2: tolerances must be finite and >= 0");
-    // (fixed steps are lh_step_coupled_implicit's LH_COUPLED_TRBDF2)
-    if (flags) return fail(c, LH_EINVAL, "lh_integrate_coupled_trbdf2: unknown flags 0x%x", flags);
-    if (bcv)
-        for (int k = 0; k < 8; ++k)
-            if (!std::isfinite(bcv[k])) return fail(c, LH_EINVAL, "lh_integrate_coupled_trbdf2: non-finite boundary value");
+    if ((rc = trbdf2_argument_refusals(c, who, t0, t1, dt, {abstol, abstol_e, reltol}, flags, 0, bcv))) return rc;
     Range r_("lh:integrate_coupled_trbdf2");
-    if ((rc = implicit_refusals(c, "lh_integrate_coupled_trbdf2", Y, Ya, LH_MODEL_COUPLED,
-                                "coupled models only (SoilEnergyModel + SoilHydrologyModel)")))
-        return rc;
-    // each tolerance that is 0 takes its own default; the energy's is that of 1e-6 K in water
-    if (!(abstol > 0)) abstol = LH_TRBDF2_ABSTOL_DEFAULT;
+    if ((rc = implicit_refusals(c, who, Y, Ya, LH_MODEL_COUPLED, COUPLED_MODELS))) return rc;
+    trbdf2_tolerance_defaults(abstol, reltol);
+    // (the energy's own default is that of 1e-6 K in water)
     if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
-    if (!(reltol > 0)) reltol = LH_TRBDF2_RELTOL_DEFAULT;
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
     if ((rc = ensure_scratch(c, &c->d_cpl_ad, 10 * pl * c->esize, "c->d_cpl_ad", "10 * plane"))) return rc;
-    if ((rc = ensure_scratch(c, &c->d_tr_stats, nstat, "c->d_tr_stats", "nstat", true))) return rc;
+    if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
     if (t1 == t0) return LH_OK;
     if ((rc = materialize(c, Y, ~0u))) return rc;
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
         CoupledTrbdf2Args<FT> A;
-        A.y = static_cast<FT*>(Y->plane[LH_VAR_VARTHETA_L]);
-        A.ti = static_cast<const FT*>(Y->plane[LH_VAR_THETA_I]); // (read only by the kernels that do not know it zero)
+        point_at_water<FT>(Y, A);
         A.e = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
         carve_planes<FT>(c->d_cpl_ad, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp, &A.en, &A.fe, &A.eg, &A.we});
-        A.dt_cols = static_cast<FT*>(dt_cols_device_ft);
-        A.t0 = t0;
-        A.t1 = t1;
-        A.dt = dt;
-        A.abstol = abstol;
+        fill_trbdf2_args<FT>(c, A, t0, t1, dt, abstol, reltol, dt_cols_device_ft, bcv);
         A.abstol_e = abstol_e;
-        A.reltol = reltol;
-        A.has_bcv = bcv != nullptr;
-        for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
-        A.kappa = FT(c->tune.trk > 0 ? 1e-4 * c->tune.trk : LH_TRBDF2_NEWTON_KAPPA);
-        A.newton_max = c->tune.trn > 0 ? c->tune.trn : LH_TRBDF2_NEWTON_MAX;
-        A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
         launch_coupled_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "coupled TR-BDF2 launch failed: %s", hipGetErrorString(e));
-    return LH_OK;
+    return launch_status(c, hipGetLastError(), "coupled TR-BDF2");
 }
 
 int lh_stable_dt_device(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double courant, void* d_out) {

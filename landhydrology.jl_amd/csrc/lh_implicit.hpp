@@ -344,6 +344,25 @@ void launch_implicit_euler(const DevParams<FT>& P, const ImplicitArgs<FT>& A, bo
 // A.newton_max iterations rejects the step with h <- h/4.  Each lane carries its own t and h
 // (double) and its own accept/reject history: no collective.
 
+// The step controller's scalar arithmetic, for trbdf2_column and layered_trbdf2_column (lh_coupled_trbdf2.hpp keeps
+// its own lines: its kernels move through these calls).  The step taken from t with the proposal
+// h: the rest of the interval where h reaches t1 to round-off (the column then lands on t1 exactly) ...
+__device__ __forceinline__ bool trbdf2_clip(double t, double t1, double h, double& hh) {
+    const bool clip = t + h * (1.0 + 1e-10) >= t1;
+    hh = clip ? t1 - t : h;
+    return clip;
+}
+// ... whether a step with error norm E is accepted, and the factor 0.9 E^(-1/3) in [0.2, 5] its size changes by ...
+__device__ __forceinline__ bool trbdf2_control(double E, double& fac) {
+    fac = 0.9 * pow(E, -1.0 / 3.0);
+    fac = fac != fac ? 0.2 : fmin(fmax(fac, 0.2), 5.0);
+    return E <= 1.0;
+}
+// ... and the proposal after an accepted step of hh: a clipped step that could have grown does not shrink h
+__device__ __forceinline__ double trbdf2_next_step(double h, double hh, double fac, bool clip) {
+    return (clip && fac >= 1.0) ? fmax(hh * fac, h) : hh * fac;
+}
+
 template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF>
 __device__ __forceinline__ void trbdf2_column(const M& mm, DevParams<FT> P, const Trbdf2Args<FT>& A, int64_t col,
                                               Trbdf2ColStats& st) {
@@ -403,9 +422,8 @@ __device__ __forceinline__ void trbdf2_column(const M& mm, DevParams<FT> P, cons
     while (t < A.t1) {
         if (steps >= LH_TRBDF2_MAX_STEPS) { failed = true; break; }
         ++steps;
-        double hh = h;
-        bool clip = false;
-        if (t + hh * (1.0 + 1e-10) >= A.t1) { hh = A.t1 - t; clip = true; } // land on t1 exactly
+        double hh;
+        const bool clip = trbdf2_clip(t, A.t1, h, hh);
         const FT dh = FT(dg * hh);
         // stage 1: Y_n and w1 = Y_n + d h f_n; the guess is Y_n
         for (int i = 0; i < n; ++i) {
@@ -464,14 +482,12 @@ __device__ __forceinline__ void trbdf2_column(const M& mm, DevParams<FT> P, cons
                 sum += q * q;
             }
             const double E = sqrt(sum / n);
-            fac = 0.9 * pow(E, -1.0 / 3.0);
-            fac = fac != fac ? 0.2 : fmin(fmax(fac, 0.2), 5.0);
-            accept = E <= 1.0;
+            accept = trbdf2_control(E, fac);
         }
         if (accept) {
             ++st.accepted;
             t = clip ? A.t1 : t + hh; // (assigned: the column lands on t1 exactly)
-            if (!A.fixed) h = (clip && fac >= 1.0) ? fmax(hh * fac, h) : hh * fac;
+            if (!A.fixed) h = trbdf2_next_step(h, hh, fac, clip);
             if (t < A.t1) { // f_{n+1} = z_1 / h for the next step
                 const FT inv_dh = FT(1.0 / (dg * hh));
                 for (int i = 0; i < n; ++i) {

@@ -294,9 +294,8 @@ __device__ __forceinline__ void layered_trbdf2_column(const M& mm, DevParams<FT>
     while (t < A.t1) {
         if (steps >= LH_TRBDF2_MAX_STEPS) { failed = true; break; }
         ++steps;
-        double hh = h;
-        bool clip = false;
-        if (t + hh * (1.0 + 1e-10) >= A.t1) { hh = A.t1 - t; clip = true; } // land on t1 exactly
+        double hh;
+        const bool clip = trbdf2_clip(t, A.t1, h, hh);
         const FT dh = FT(dg * hh);
         // stage 1: Y_n and w1 = Y_n + d h f_n; the guess is Y_n
         for (int i = 0; i < n; ++i) {
@@ -352,14 +351,12 @@ __device__ __forceinline__ void layered_trbdf2_column(const M& mm, DevParams<FT>
                 sum += q * q;
             }
             const double E = sqrt(sum / n);
-            fac = 0.9 * pow(E, -1.0 / 3.0);
-            fac = fac != fac ? 0.2 : fmin(fmax(fac, 0.2), 5.0);
-            accept = E <= 1.0;
+            accept = trbdf2_control(E, fac);
         }
         if (accept) {
             ++st.accepted;
             t = clip ? A.t1 : t + hh; // (assigned: the column lands on t1 exactly)
-            if (!A.fixed) h = (clip && fac >= 1.0) ? fmax(hh * fac, h) : hh * fac;
+            if (!A.fixed) h = trbdf2_next_step(h, hh, fac, clip);
             if (t < A.t1) { // f_{n+1} = z_1 / h for the next step
                 const FT inv_dh = FT(1.0 / (dg * hh));
                 for (int i = 0; i < n; ++i) {
