@@ -499,7 +499,8 @@ int lh_implicit_iterations(lh_ctx*, int64_t* iterations);
 int lh_integrate_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
                         double abstol, double reltol, uint32_t flags, void* dt_cols_device_ft,
                         const double* bcv);
-/* Of the last lh_integrate_trbdf2, lh_integrate_layered_trbdf2 or lh_integrate_coupled_trbdf2 call,
+/* Of the last lh_integrate_trbdf2, lh_integrate_layered_trbdf2, lh_integrate_coupled_trbdf2 or
+ * lh_integrate_series call (the last one's counters over its whole interval, see there),
  * LH_TRBDF2_NSTATS counters (zeros once a later call of any of them was refused): accepted steps,
  * rejected steps, Newton iterations (summed over stages and columns), the largest number of
  * attempted steps of any column,
@@ -598,6 +599,50 @@ int lh_step_coupled_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, double t,
 int lh_integrate_coupled_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
                                 double abstol, double abstol_e, double reltol, uint32_t flags,
                                 void* dt_cols_device_ft, const double* bcv);
+
+/* Per-column boundary-value time series for the TR-BDF2 integrators.
+ * A series holds nknots >= 2 knot times, finite and strictly increasing (LH_EINVAL otherwise, the
+ * message names the first offending knot), and for any (face, component) the values at the knots,
+ * piecewise linear in between: at t in [T_k, T_k+1] the value is
+ * v_k + (v_k+1 - v_k) ((t - T_k) / (T_k+1 - T_k)) in double, and exactly v_k on a knot.
+ * lh_bc_series_set: the value of (knot k, column c) is values[k*knot_stride + c*col_stride];
+ * col_stride == 0 gives every column the same value per knot (stored as nknots doubles).  A
+ * per-column table is kept on the device in double, column-fastest with the context's plane
+ * stride, whatever the working type.  values == NULL removes that component's series.  Values are
+ * not judged.  The call copies the values and synchronises.
+ * lh_bc_series_destroy releases the tables (lh_destroy releases the series still alive).
+ *
+ * lh_integrate_series stands for lh_integrate_trbdf2 (Richards without a class map),
+ * lh_integrate_layered_trbdf2 (Richards with one) or lh_integrate_coupled_trbdf2 (coupled without
+ * one); anything else is LH_EMODEL.  abstol_e is read by the coupled model only.  With the
+ * breakpoints t0, every knot strictly inside (t0, t1) and t1, every column that does not fail gets,
+ * BITWISE, the Y, the dt_cols entry and status bit 0 of calling that entry point once per
+ * sub-interval [a, b] in order, dt_cols carried from call to call and bcv holding the column's own
+ * series values at a and b -- in ONE launch, each column walking its own sub-intervals.  With
+ * dt_cols_device_ft == NULL the proposals are carried in a zeroed scratch buffer of the library
+ * (the first sub-interval starts every column at dt).  A (face, component) without a series keeps
+ * lh_set_bc's value, its per-column array included; one with a series ignores both.  The step
+ * floor (1e-10 x the sub-interval) and the cap on attempted steps apply per sub-interval, and the
+ * tendency at the start of every sub-interval is evaluated anew.  A column that fails in a
+ * sub-interval stops there with its last accepted state, sets status bit 4 and gets dt_cols = 0.
+ * lh_trbdf2_stats: accepted, rejected, Newton iterations, failed and unconverged are sums over the
+ * sub-intervals; max_steps is the largest total of attempted steps of any column over the whole
+ * call and wave_steps the sum over waves of 64 x the wave's largest such total.
+ * flags: LH_TRBDF2_FIXED where the entry stood for takes it (steps are clipped at every breakpoint
+ * as at t1); 0 for the coupled model.
+ * LH_EINVAL: what the entry stood for refuses, t0 < T_0 or t1 > T_last (no extrapolation), a NULL
+ * series, a series of another context; t0 == t1 does nothing.  LH_EMODEL: what the entry stood for
+ * refuses, in its order; then a series on a component the model does not have (energy on a Richards
+ * context) or on a (face, component) whose lh_set_bc kind reads no value (LH_BC_NONE,
+ * LH_BC_FREE_DRAINAGE).  After a refused call lh_trbdf2_stats gives zeros.  Asynchronous. */
+typedef struct lh_bc_series lh_bc_series;
+int lh_bc_series_create(lh_ctx*, int32_t nknots, const double* times, lh_bc_series** out);
+int lh_bc_series_set(lh_ctx*, lh_bc_series*, int32_t face, int32_t component, const double* values,
+                     int64_t knot_stride, int64_t col_stride);
+int lh_bc_series_destroy(lh_ctx*, lh_bc_series*);
+int lh_integrate_series(lh_ctx*, lh_state* Y, const lh_state* Ya, const lh_bc_series*, double t0, double t1,
+                        double dt, double abstol, double abstol_e, double reltol, uint32_t flags,
+                        void* dt_cols_device_ft);
 
 /* Build-defined stable step (the reference uses a fixed user dt):
  * courant*dz^2 / max over owned faces of the face diffusivities

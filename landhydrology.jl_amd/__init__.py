@@ -9,7 +9,7 @@ this package is the host-side mirror of the reference's Julia interface.
 from . import _ffi, case_model, parameterizations, partition, workloads
 from ._ffi import LandHydroError, ModelError
 from .parameterizations import *  # noqa: F401,F403
-from .soil import (Column, CoupledAdaptiveTRBDF2, CoupledImplicitEuler, CoupledTRBDF2, Dirichlet,
+from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplicitEuler, CoupledTRBDF2, Dirichlet,
                    EarthParameterSet, FieldVector, Float32, Float64, FreeDrainage, HeatImplicitEuler,
                    HeatTRBDF2, IceImpedance, ImplicitEuler, LayeredImplicitEuler, LayeredTRBDF2, NoBC, NoEffect,
                    PrescribedAtmosForcing,
@@ -18,7 +18,7 @@ from .soil import (Column, CoupledAdaptiveTRBDF2, CoupledImplicitEuler, CoupledT
                    SoilThermal, SSPRK33,
                    TemperatureDependentViscosity, TRBDF2, VerticalFlux, boundary_fluxes,
                    compute_turbulent_surface_fluxes, coordinates, default_initial_conditions,
-                   initialize_states, integrate_coupled_trbdf2, integrate_layered_trbdf2, integrate_trbdf2,
+                   initialize_states, integrate_coupled_trbdf2, integrate_layered_trbdf2, integrate_series, integrate_trbdf2,
                    make_function_space, make_rhs, make_update_aux, run, stable_dt, step, step_adaptive, step_implicit,
                    step_implicit_coupled, step_implicit_heat, step_implicit_layered, tune_placement, vanGenuchten)
 

@@ -6,6 +6,7 @@
 #include "lh_layered.hpp"
 #include "lh_layered_implicit.hpp"
 #include "lh_layered_heat.hpp"
+#include "lh_series.hpp"
 #include "lh_fastmath.hpp"
 #include "lh_closures.hpp"
 
@@ -79,6 +80,16 @@ struct PlaneArena {
     std::vector<char> used;
 };
 
+// A boundary-value time series (lh_bc_series_create): the knot times on both sides, and per (face, component)
+// a table of doubles on the device -- [nknots][stride] (per-column, column-fastest) or [nknots] (uniform)
+struct lh_bc_series {
+    lh_ctx* ctx = nullptr;
+    std::vector<double> times;
+    double* d_times = nullptr;
+    double* d_val[2][2] = {};
+    bool percol[2][2] = {};
+};
+
 struct lh_ctx {
     lh_config cfg{};
     int device = 0;
@@ -118,6 +129,8 @@ struct lh_ctx {
     std::vector<lh_soil_class_thermal> soil_thermal;
     void* d_cls_therm = nullptr;
     bool cls_any_om = false;           // some class has 1 - nu_om != 1 in the working type
+    void* d_series_dt = nullptr;       // lh_integrate_series: FT[ncols] step proposals carried across sub-intervals where the caller passes none
+    std::vector<lh_bc_series*> series; // the series alive (lh_bc_series_create .. lh_bc_series_destroy)
     void* d_cpl_ad = nullptr;          // lh_integrate_coupled_trbdf2: ten FT planes [nlev][stride] (d_tr's six for the water; the energy's Y_n, f_n, Y_gamma, w2)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
@@ -1425,6 +1438,8 @@ int lh_destroy(lh_ctx* c) {
         c->comm = nullptr;
     }
     while (!c->states.empty()) state_free(c, c->states.back());
+    while (!c->series.empty()) (void)lh_bc_series_destroy(c, c->series.back());
+    if (c->d_series_dt) (void)hipFree(c->d_series_dt);
     for (auto& a : c->arenas) (void)hipFree(a.base); // none should be left
     c->arenas.clear();
     for (int i = 0; i < LH_PC_COUNT; ++i)
@@ -2510,6 +2525,193 @@ int lh_integrate_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, doub
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
     return launch_status(c, hipGetLastError(), "coupled TR-BDF2");
+}
+
+// ---- boundary-value time series (lh_series.hpp)
+
+static bool series_of(const lh_ctx* c, const lh_bc_series* s) {
+    for (const lh_bc_series* k : c->series)
+        if (k == s) return true;
+    return false;
+}
+
+int lh_bc_series_create(lh_ctx* c, int32_t nknots, const double* times, lh_bc_series** out) {
+    if (!c) return LH_EINVAL;
+    if (!times || !out) return fail(c, LH_EINVAL, "lh_bc_series_create: NULL argument");
+    *out = nullptr;
+    if (nknots < 2) return fail(c, LH_EINVAL, "lh_bc_series_create: need nknots >= 2");
+    for (int32_t k = 0; k < nknots; ++k) {
+        if (!std::isfinite(times[k])) return fail(c, LH_EINVAL, "lh_bc_series_create: knot %d is not finite", k);
+        if (k > 0 && !(times[k] > times[k - 1]))
+            return fail(c, LH_EINVAL, "lh_bc_series_create: knot %d is not after knot %d (the times must increase strictly)", k, k - 1);
+    }
+    (void)hipSetDevice(c->device);
+    lh_bc_series* s = new (std::nothrow) lh_bc_series();
+    if (!s) return fail(c, LH_ENOMEM, "out of host memory");
+    s->ctx = c;
+    s->times.assign(times, times + nknots);
+    hipError_t e = hipMalloc(&s->d_times, size_t(nknots) * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(s->d_times, times, size_t(nknots) * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (s->d_times) (void)hipFree(s->d_times);
+        delete s;
+        return hip_status(c, e, "lh_bc_series_create: the upload of the knot times");
+    }
+    c->series.push_back(s);
+    *out = s;
+    return LH_OK;
+}
+
+int lh_bc_series_set(lh_ctx* c, lh_bc_series* s, int32_t face, int32_t comp, const double* values, int64_t knot_stride,
+                     int64_t col_stride) {
+    if (!c) return LH_EINVAL;
+    if (!s || !series_of(c, s)) return fail(c, LH_EINVAL, "lh_bc_series_set: not a series of this context");
+    if (face != LH_FACE_BOTTOM && face != LH_FACE_TOP) return fail(c, LH_EINVAL, "lh_bc_series_set: unknown face %d", face);
+    if (comp != LH_COMP_ENERGY && comp != LH_COMP_HYDROLOGY) return fail(c, LH_EINVAL, "lh_bc_series_set: unknown component %d", comp);
+    (void)hipSetDevice(c->device);
+    if (s->d_val[face][comp]) { // (a launch in flight may still read the table)
+        LH_HIP(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(s->d_val[face][comp]);
+        s->d_val[face][comp] = nullptr;
+    }
+    if (!values) return LH_OK;
+    const int64_t nk = int64_t(s->times.size());
+    const bool percol = col_stride != 0;
+    const int64_t row = percol ? c->stride : 1, n = percol ? c->cfg.ncols : 1;
+    std::vector<double> tab(size_t(nk) * size_t(row), 0.0);
+    for (int64_t k = 0; k < nk; ++k)
+        for (int64_t j = 0; j < n; ++j) tab[size_t(k * row + j)] = values[k * knot_stride + j * col_stride];
+    double* d = nullptr;
+    LH_HIP(c, hipMalloc(&d, tab.size() * sizeof(double)));
+    const hipError_t e = hipMemcpy(d, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return hip_status(c, e, "lh_bc_series_set: the upload of the table");
+    }
+    s->d_val[face][comp] = d;
+    s->percol[face][comp] = percol;
+    return LH_OK;
+}
+
+int lh_bc_series_destroy(lh_ctx* c, lh_bc_series* s) {
+    if (!c) return LH_EINVAL;
+    if (!s) return LH_OK;
+    if (!series_of(c, s)) return fail(c, LH_EINVAL, "lh_bc_series_destroy: not a series of this context");
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream); // (a launch in flight may still read the tables)
+    for (size_t k = 0; k < c->series.size(); ++k)
+        if (c->series[k] == s) {
+            c->series.erase(c->series.begin() + long(k));
+            break;
+        }
+    for (int f = 0; f < 2; ++f)
+        for (int k = 0; k < 2; ++k)
+            if (s->d_val[f][k]) (void)hipFree(s->d_val[f][k]);
+    if (s->d_times) (void)hipFree(s->d_times);
+    delete s;
+    return LH_OK;
+}
+
+// One launch for the chain of lh_integrate_trbdf2 / lh_integrate_layered_trbdf2 / lh_integrate_coupled_trbdf2 calls
+// over the sub-intervals of [t0, t1] between the knots: the refusals, the defaults, the scratch and the launch
+// arguments are those calls' own, in their order; the series adds its checks behind them.
+int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_series* sr, double t0, double t1, double dt,
+                        double abstol, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft) {
+    if (!c) return LH_EINVAL;
+    static const char* const who = "lh_integrate_series";
+    int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
+    if (rc) return rc;
+    if (!sr) return fail(c, LH_EINVAL, "%s: the series is NULL", who);
+    if (!series_of(c, sr)) return fail(c, LH_EINVAL, "%s: not a series of this context", who);
+    if (c->cfg.model == LH_MODEL_HEAT)
+        return fail(c, LH_EMODEL, "%s: Richards models, with or without a class map, and coupled models without one only", who);
+    const bool coupled = c->cfg.model == LH_MODEL_COUPLED;
+    const bool lay = !coupled && layered(c);
+    rc = coupled ? trbdf2_argument_refusals(c, who, t0, t1, dt, {abstol, abstol_e, reltol}, flags, 0, nullptr)
+                 : trbdf2_argument_refusals(c, who, t0, t1, dt, {abstol, reltol}, flags, LH_TRBDF2_FIXED, nullptr);
+    if (rc) return rc;
+    if (t0 < sr->times.front() || t1 > sr->times.back())
+        return fail(c, LH_EINVAL, "%s: [t0, t1] = [%g, %g] leaves the series' knots [%g, %g] (no extrapolation)", who, t0, t1,
+                    sr->times.front(), sr->times.back());
+    Range r_("lh:integrate_series");
+    if ((rc = implicit_refusals(c, who, Y, Ya, coupled ? LH_MODEL_COUPLED : LH_MODEL_RICHARDS, coupled ? COUPLED_MODELS : RICHARDS_MODELS,
+                                lay ? "lh_integrate_trbdf2" : nullptr)))
+        return rc;
+    for (int f = 0; f < 2; ++f)
+        for (int k = 0; k < 2; ++k) {
+            if (!sr->d_val[f][k]) continue;
+            const char* fn = f == LH_FACE_TOP ? "top" : "bottom";
+            if (k == LH_COMP_ENERGY && !coupled)
+                return fail(c, LH_EMODEL, "%s: the series has %s energy values, and a Richards model has no energy component", who, fn);
+            const int kind = c->hp.bc_kind[f][k];
+            if (kind != LH_BC_FLUX && kind != LH_BC_DIRICHLET)
+                return fail(c, LH_EMODEL, "%s: the series has %s %s values, and the boundary condition there (lh_set_bc) reads no value",
+                            who, fn, k == LH_COMP_ENERGY ? "energy" : "hydrology");
+        }
+    trbdf2_tolerance_defaults(abstol, reltol);
+    if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
+    double tol = 0; // (fixed mode: lh_step_implicit_euler's defaults)
+    int32_t max_iter = 0;
+    newton_defaults(c, tol, max_iter);
+    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+    if (coupled) {
+        if ((rc = ensure_scratch(c, &c->d_cpl_ad, 10 * pl * c->esize, "c->d_cpl_ad", "10 * plane"))) return rc;
+    } else if ((rc = ensure_scratch(c, &c->d_tr, 6 * pl * c->esize, "c->d_tr", "6 * plane")))
+        return rc;
+    if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
+    if (t1 == t0) return LH_OK;
+    if (!dt_cols_device_ft) { // the proposals are carried all the same: a zeroed buffer of the library's own
+        const size_t bytes = size_t(c->cfg.ncols) * c->esize;
+        if ((rc = ensure_scratch(c, &c->d_series_dt, bytes, "c->d_series_dt", "ncols"))) return rc;
+        if ((rc = zero_stats(c, c->d_series_dt, bytes, "c->d_series_dt", "ncols"))) return rc;
+        dt_cols_device_ft = c->d_series_dt;
+    }
+    if ((rc = materialize(c, Y, ~0u))) return rc;
+    SeriesArgs S;
+    S.times = sr->d_times;
+    for (int f = 0; f < 2; ++f)
+        for (int k = 0; k < 2; ++k) {
+            S.val[f][k] = sr->d_val[f][k];
+            S.knot_stride[f][k] = sr->percol[f][k] ? c->stride : 1;
+            S.col_varies[f][k] = sr->percol[f][k] ? 1 : 0;
+        }
+    {   // the first knot after t0 and the first one at or after t1: the knots in between are the interior breakpoints
+        const int nk = int(sr->times.size());
+        int k_first = 1, k_end = 1;
+        while (k_first < nk - 1 && !(sr->times[size_t(k_first)] > t0)) ++k_first;
+        while (k_end < nk - 1 && !(sr->times[size_t(k_end)] >= t1)) ++k_end;
+        S.k0 = k_first - 1;
+        S.nsub = k_end - k_first + 1;
+    }
+    // lh_set_bc's values at both ends of every sub-interval: what the chain's bcv holds where there is no series
+    double bcv[8];
+    for (int k = 0; k < 8; ++k) bcv[k] = c->hp.bc_value[(k >> 1) & 1][k & 1];
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        if (coupled) {
+            CoupledTrbdf2Args<FT> A;
+            point_at_water<FT>(Y, A);
+            A.e = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
+            carve_planes<FT>(c->d_cpl_ad, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp, &A.en, &A.fe, &A.eg, &A.we});
+            fill_trbdf2_args<FT>(c, A, t0, t1, dt, abstol, reltol, dt_cols_device_ft, bcv);
+            A.abstol_e = abstol_e;
+            launch_series_coupled_trbdf2<FT>(P, A, S, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+        } else {
+            if (lay) layered_params<FT>(c, P);
+            Trbdf2Args<FT> A;
+            point_at_water<FT>(Y, A);
+            carve_planes<FT>(c->d_tr, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp});
+            fill_trbdf2_args<FT>(c, A, t0, t1, dt, abstol, reltol, dt_cols_device_ft, bcv);
+            A.fixed = (flags & LH_TRBDF2_FIXED) != 0;
+            A.tol = FT(tol);
+            A.max_iter = max_iter;
+            if (lay) launch_series_layered_trbdf2<FT>(P, layered_args<FT>(c), A, S, implicit_noice(c, Y), c->stream);
+            else launch_series_trbdf2<FT>(P, A, S, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+        }
+    });
+    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | (coupled ? LH_MASK(LH_VAR_RHOE_INT) : 0u));
+    return launch_status(c, hipGetLastError(), "series TR-BDF2");
 }
 
 int lh_stable_dt_device(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double courant, void* d_out) {

@@ -1,0 +1,10 @@
+// gfx950 boundary-value-series kernels (lh_series.hpp: lh_integrate_series over the scalar, the layered and the
+// coupled TR-BDF2 column routines), double
+#define LH_TU_MODEL
+#define LH_LAYERED_TU // (stage_class_table; no kernel of lh_layered.hpp is instantiated here)
+#define LH_LAYERED_IMPLICIT_TU // (layered_trbdf2_column; no kernel of lh_layered_implicit.hpp is instantiated here)
+#define LH_SERIES_TU
+#include "lh_series.hpp"
+namespace lh {
+LH_INSTANTIATE_SERIES(double)
+}

@@ -653,6 +653,71 @@ function integrate_coupled_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, 
 end
 
 """
+    BoundarySeries(ens, times, values)
+
+Boundary values as piecewise-linear time series on the device (lh_bc_series_create / lh_bc_series_set).
+`times`: `nknots >= 2` finite, strictly increasing knot times.  `values`: pairs
+`(face, component) => v` with `face` in `(:bottom, :top)`, `component` in `(:energy, :hydrology)` and `v` a
+vector of `nknots` values (every column the same) or an `ncolumns × nknots` matrix (column-fastest, as the
+library stores it).  Released with the ensemble, or earlier by `release!`.
+"""
+mutable struct BoundarySeries
+    ens::ColumnEnsemble
+    handle::Ptr{Cvoid}
+end
+
+function BoundarySeries(ens::ColumnEnsemble, times, values)
+    T = convert(Vector{Float64}, times)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ens.ctx, ccall((:lh_bc_series_create, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Ptr{Cvoid}}),
+                         ens.ctx, Int32(length(T)), T, out))
+    s = BoundarySeries(ens, out[])
+    for ((face, comp), v) in values
+        f = face === :top ? Int32(1) : face === :bottom ? Int32(0) : throw(ArgumentError("Expected :top or :bottom"))
+        c = comp === :hydrology ? Int32(1) : comp === :energy ? Int32(0) : throw(ArgumentError("Expected :energy or :hydrology"))
+        a = convert(Array{Float64}, v)
+        percol = ndims(a) == 2
+        size(a, ndims(a)) == length(T) || throw(ArgumentError("the last dimension of the values must be nknots"))
+        percol && size(a, 1) != ens.ncolumns && throw(ArgumentError("per-column values must have ncolumns rows"))
+        check(ens.ctx, ccall((:lh_bc_series_set, lib), Cint,
+                             (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int64, Int64),
+                             ens.ctx, s.handle, f, c, a, Int64(percol ? size(a, 1) : 1), Int64(percol ? 1 : 0)))
+    end
+    finalizer(s) do x
+        # the context may already be gone (and with it this series): nothing left to free then
+        if x.ens.ctx != C_NULL && x.handle != C_NULL
+            ccall((:lh_bc_series_destroy, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), x.ens.ctx, x.handle)
+            x.handle = C_NULL
+        end
+    end
+    return s
+end
+
+"""
+    integrate_series!(ens, Y, Ya, series, t0, t1, dt; abstol = 0.0, abstol_e = 0.0, reltol = 0.0,
+                      adaptive = true, dt_cols = C_NULL) -> stats
+
+TR-BDF2 from `t0` to `t1` under a `BoundarySeries` in one call (lh_integrate_series): bitwise the chain of
+`integrate_trbdf2!` / `integrate_layered_trbdf2!` / `integrate_coupled_trbdf2!` calls over the sub-intervals
+between the series' knots, every column with its own boundary values and walking its own sub-intervals.
+`abstol_e`: coupled ensembles only; `adaptive = false`: Richards ensembles only.  Returns the 7 counters of
+lh_trbdf2_stats over the whole call.
+"""
+function integrate_series!(ens::ColumnEnsemble, Y::DeviceState, Ya, series::BoundarySeries, t0, t1, dt; abstol = 0.0,
+                           abstol_e = 0.0, reltol = 0.0, adaptive = true, dt_cols = C_NULL)
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    check(ens.ctx, ccall((:lh_integrate_series, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64,
+                          UInt32, Ptr{Cvoid}),
+                         ens.ctx, Y.handle, ya, series.handle, t0, t1, dt, abstol, abstol_e, reltol,
+                         adaptive ? UInt32(0) : UInt32(1), dt_cols))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
     tune_placement!(ens, Y, Ya, dY = nothing; max_candidates = 0, move_input = true)
 
 Let the library place the state written by `rhs!` (`dY` given) or the SSPRK33 stage state

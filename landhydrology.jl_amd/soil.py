@@ -1127,12 +1127,15 @@ class TRBDF2:
     own: TRBDF2(reltol=1e-5) keeps abstol 1e-6.
     adaptive=False: steps of exactly the Simulation's dt, no error control.  The Simulation's dt is the
     initial step and the interval at which Dirichlet closures are sampled; a model without them runs a
-    whole saveat chunk per library call.  Same scope as ImplicitEuler."""
+    whole saveat chunk per library call.  Same scope as ImplicitEuler.
+    forcing: None or a BoundarySeries; with it every advance is one integrate_series call (the series' values
+    replace the model's on its (face, component)s, Dirichlet closures are not sampled)."""
 
-    def __init__(self, abstol=None, reltol=None, adaptive=True):
+    def __init__(self, abstol=None, reltol=None, adaptive=True, forcing=None):
         self.abstol = abstol
         self.reltol = reltol
         self.adaptive = adaptive
+        self.forcing = forcing
 
     def check_scope(self, model):
         _check_implicit_scope(model, "TRBDF2")
@@ -1233,12 +1236,13 @@ class CoupledAdaptiveTRBDF2:
     (lh_integrate_coupled_trbdf2): CoupledTRBDF2's stages, TRBDF2's controller.  abstol (on ϑ_l), abstol_e (on
     ρe_int) and reltol: None = the library's defaults (1e-6, 1e-6 ρ_l c_l, 1e-3), each on its own.  The Simulation's
     dt is the initial step and the interval at which Dirichlet closures are sampled, as for TRBDF2.  Scope as
-    CoupledImplicitEuler."""
+    CoupledImplicitEuler.  forcing: None or a BoundarySeries, as TRBDF2's."""
 
-    def __init__(self, abstol=None, abstol_e=None, reltol=None):
+    def __init__(self, abstol=None, abstol_e=None, reltol=None, forcing=None):
         self.abstol = abstol
         self.abstol_e = abstol_e
         self.reltol = reltol
+        self.forcing = forcing
 
     def check_scope(self, model):
         _check_coupled_implicit_scope(model, type(self).__name__)
@@ -1475,9 +1479,124 @@ def integrate_coupled_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: fl
     return _trbdf2_stats(be)
 
 
+_SERIES_FACE = {"bottom": F.LH_FACE_BOTTOM, "top": F.LH_FACE_TOP, F.LH_FACE_BOTTOM: F.LH_FACE_BOTTOM,
+                F.LH_FACE_TOP: F.LH_FACE_TOP}
+_SERIES_COMP = {"energy": F.LH_COMP_ENERGY, "hydrology": F.LH_COMP_HYDROLOGY, F.LH_COMP_ENERGY: F.LH_COMP_ENERGY,
+                F.LH_COMP_HYDROLOGY: F.LH_COMP_HYDROLOGY}
+
+
+class BoundarySeries:
+    """Build extension: boundary values as piecewise-linear time series, per column or for all columns
+    (lh_bc_series).  BoundarySeries(times, {(face, component): values}): `times` are nknots >= 2 finite, strictly
+    increasing knot times; face is "bottom" / "top" (or LH_FACE_*), component "energy" / "hydrology" (or
+    LH_COMP_*); `values` has shape [nknots] (every column the same) or [nknots, ncolumns].  Validated here with
+    the library's own rules (ValueError).  At t in [T_k, T_k+1] a series is v_k + (v_k+1 - v_k) ((t - T_k) /
+    (T_k+1 - T_k)) in Float64, and exactly v_k on a knot; there is no extrapolation.  Values are not judged."""
+
+    def __init__(self, times, values):
+        t = np.array(times, dtype=np.float64)
+        if t.ndim != 1 or t.size < 2:
+            raise ValueError("BoundarySeries: need nknots >= 2 knot times")
+        for k in range(t.size):
+            if not np.isfinite(t[k]):
+                raise ValueError(f"BoundarySeries: knot {k} is not finite")
+            if k > 0 and not t[k] > t[k - 1]:
+                raise ValueError(f"BoundarySeries: knot {k} is not after knot {k - 1} (the times must increase strictly)")
+        self.times = t
+        self.values = {}
+        for key, v in dict(values).items():
+            try:
+                f, c = key
+                fc = (_SERIES_FACE[f], _SERIES_COMP[c])
+            except (TypeError, ValueError, KeyError):
+                raise ValueError(f"BoundarySeries: {key!r} is not a (face, component)") from None
+            if fc in self.values:
+                raise ValueError(f"BoundarySeries: {key!r} is given twice")
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            if a.ndim not in (1, 2) or a.shape[0] != t.size:
+                raise ValueError(f"BoundarySeries: the values of {key!r} must have shape [nknots] or [nknots, ncolumns]")
+            self.values[fc] = a
+
+    @property
+    def nknots(self):
+        return self.times.size
+
+    def breakpoints(self, t0, t1):
+        """t0, every knot strictly inside (t0, t1), t1: the ends of the sub-intervals of one integrate_series call."""
+        self._check_span(t0, t1)
+        inner = self.times[(self.times > t0) & (self.times < t1)]
+        return [float(t0)] + [float(x) for x in inner] + [float(t1)]
+
+    def value_at(self, key, t):
+        """The series of (face, component) at time t: a Float64 scalar ([nknots] values) or [ncolumns] array."""
+        f, c = key
+        v = self.values[(_SERIES_FACE[f], _SERIES_COMP[c])]
+        T = self.times
+        t = float(t)
+        if not T[0] <= t <= T[-1]:
+            raise ValueError(f"BoundarySeries: t = {t} is outside the knots [{T[0]}, {T[-1]}] (no extrapolation)")
+        k = min(int(np.searchsorted(T, t, side="right")) - 1, T.size - 2)
+        if t == T[k]:
+            return v[k].copy() if v.ndim == 2 else float(v[k])
+        if t == T[k + 1]:
+            return v[k + 1].copy() if v.ndim == 2 else float(v[k + 1])
+        s = np.float64((t - T[k]) / (T[k + 1] - T[k]))
+        r = v[k] + (v[k + 1] - v[k]) * s
+        return r if v.ndim == 2 else float(r)
+
+    def _check_span(self, t0, t1):
+        if t0 < self.times[0] or t1 > self.times[-1]:
+            raise ValueError(f"BoundarySeries: [t0, t1] = [{t0}, {t1}] leaves the knots [{self.times[0]}, {self.times[-1]}] "
+                             "(no extrapolation)")
+
+    def _device(self, model):
+        """The lh_bc_series of this series in the model's context (created and filled on first use)."""
+        be = model._backend()
+        made = be.__dict__.setdefault("_bc_series", {})   # id(series) -> (series, lh_bc_series): lh_destroy releases them
+        if id(self) in made:
+            return made[id(self)][1]
+        L = F.lib()
+        ncols = model.domain.ncolumns
+        for fc, a in self.values.items():
+            if a.ndim == 2 and a.shape[1] != ncols:
+                raise ValueError("BoundarySeries: per-column values must have ncolumns entries per knot")
+        h = C.c_void_p()
+        F.check(L.lh_bc_series_create(be.ctx, int(self.nknots), _dptr(self.times), C.byref(h)), be.ctx)
+        for (f, c), a in self.values.items():
+            F.check(L.lh_bc_series_set(be.ctx, h, f, c, _dptr(a), a.strides[0] // 8, a.strides[1] // 8 if a.ndim == 2 else 0),
+                    be.ctx)
+        made[id(self)] = (self, h)
+        return h
+
+
+def integrate_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySeries, t0: float, t1: float, dt: float,
+                     abstol=None, abstol_e=None, reltol=None, adaptive=True, dt_cols=None):
+    """Build extension: TR-BDF2 of `Y` from t0 to t1 under a BoundarySeries in ONE library call
+    (lh_integrate_series): bitwise the chain of integrate_trbdf2 / integrate_layered_trbdf2 /
+    integrate_coupled_trbdf2 calls over the sub-intervals between the series' knots, every column with its own
+    boundary values and walking its own sub-intervals.  A (face, component) without a series keeps the model's
+    boundary value of t0.  Tolerances, `adaptive` and `dt_cols` as those calls' (abstol_e: coupled models only;
+    adaptive=False: Richards models only).  Returns lh_trbdf2_stats of the whole call as a dict."""
+    if not isinstance(series, BoundarySeries):
+        raise TypeError("integrate_series: series must be a BoundarySeries")
+    series._check_span(t0, t1)
+    be = model._backend()
+    ya = _handle(Ya)
+    be.set_bcs(model, t0)
+    h = series._device(model)
+    ptr = _dt_cols_pointer(model, dt_cols)
+    flags = 0 if adaptive else F.LH_TRBDF2_FIXED
+    abstol, reltol = _trbdf2_tolerances(abstol, reltol)
+    abstol_e = 0.0 if abstol_e is None else float(abstol_e)
+    F.check(F.lib().lh_integrate_series(be.ctx, Y.handle, ya, h, float(t0), float(t1), float(dt), abstol, abstol_e, reltol,
+                                        flags, ptr), be.ctx)
+    return _trbdf2_stats(be)
+
+
 def _advance_trbdf2(sim, t1):
     """The Simulation's TR-BDF2 (TRBDF2, CoupledAdaptiveTRBDF2) from it.t to t1: one library call per dt interval when Dirichlet closures
-    depend on time, one for the whole interval otherwise; the per-column step proposals carry over.
+    depend on time, one for the whole interval otherwise; the per-column step proposals carry over.  With the method's
+    `forcing` (a BoundarySeries): one integrate_series call for the whole interval.
     Returns the time reached (t1 itself, not a sum of steps)."""
     it, m, model = sim.integrator, sim.method, sim.model
     if t1 <= it.t:
@@ -1488,6 +1607,13 @@ def _advance_trbdf2(sim, t1):
         it._dt_cols = torch.zeros(model.domain.ncolumns, dtype=ft, device=dev)
         it.trbdf2_stats = dict(accepted=0, rejected=0, newton_iterations=0, max_steps=0, failed=0, wave_steps=0,
                                unconverged=0)
+    if getattr(m, "forcing", None) is not None:
+        st = integrate_series(model, it.u, it.p, m.forcing, it.t, t1, it.dt, m.abstol, getattr(m, "abstol_e", None), m.reltol,
+                              getattr(m, "adaptive", True), it._dt_cols)
+        for k, v in st.items():
+            it.trbdf2_stats[k] += v
+        it.t = t1
+        return it.t
     if _time_dependent(model):
         n = max(1, int(round((t1 - it.t) / it.dt)))
         ends = [it.t + (k + 1) * it.dt for k in range(n - 1)] + [t1]
