@@ -337,6 +337,10 @@ int lh_step_ssprk33(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double d
  * LH_ENGINE_FUSED_STAGES = three fused-stage launches per step (rhs_kernel MODE 1-3),
  * LH_ENGINE_COLUMN_STEPPER = ONE launch of the persistent column stepper for the whole call (state in
  * registers).  per_stage_boundary_values: the call would pass bc_stage_values != NULL.
+ * A context with a class map (layered soils) answers LH_ENGINE_COLUMN_STEPPER only for LH_MODEL_RICHARDS with
+ * up to 128 levels, no prescribed atmosphere and the tuning persist=2 (LH_TUNE / lh_set_tuning);
+ * with the default tuning, for the coupled and heat-only models and above 128 levels it answers
+ * LH_ENGINE_FUSED_STAGES.  The answer is what lh_step_ssprk33 does in every case.
  * Returns the engine (>= 0) or a negative LH_E* code. */
 enum { LH_ENGINE_FUSED_STAGES = 0, LH_ENGINE_COLUMN_STEPPER = 1 };
 int lh_step_engine(const lh_ctx*, int64_t nsteps, int32_t per_stage_boundary_values);

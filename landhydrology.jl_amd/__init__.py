@@ -19,7 +19,8 @@ from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplici
                    TemperatureDependentViscosity, TRBDF2, VerticalFlux, boundary_fluxes,
                    compute_turbulent_surface_fluxes, coordinates, default_initial_conditions,
                    initialize_states, integrate_coupled_trbdf2, integrate_layered_trbdf2, integrate_series, integrate_trbdf2,
-                   make_function_space, make_rhs, make_update_aux, run, stable_dt, step, step_adaptive, step_implicit,
+                   make_function_space, make_rhs, make_update_aux, run, set_tuning, stable_dt, step, step_adaptive,
+                   step_engine, step_implicit,
                    step_implicit_coupled, step_implicit_heat, step_implicit_layered, tune_placement, vanGenuchten)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -6,6 +6,7 @@
 #include "lh_layered.hpp"
 #include "lh_layered_implicit.hpp"
 #include "lh_layered_heat.hpp"
+#include "lh_layered_stepper.hpp"
 #include "lh_series.hpp"
 #include "lh_fastmath.hpp"
 #include "lh_closures.hpp"
@@ -866,6 +867,43 @@ int run_column_stepper(lh_ctx* c, lh_state* Y, const lh_state* Ya, double dt, co
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
     const hipError_t e = launch_error(c, d_bcv);
     if (e != hipSuccess) return fail(c, LH_ENODEVICE, "column stepper launch failed: %s", hipGetErrorString(e));
+    return LH_OK;
+}
+
+// The layered twin (layered_column_stepper_wave_kernel): a Richards context with a class map
+// takes the stepper only when the tuning says persist=2 ("always"), for columns one wave can hold.  With the
+// default tuning it keeps the fused stages; the layered coupled and heat-only kernels have no stepper.
+bool use_layered_column_stepper(const lh_ctx* c) {
+    return layered(c) && c->cfg.model == LH_MODEL_RICHARDS && c->tune.persist == 2 && c->cfg.nlev <= 128 && !c->hp.atmos_on;
+}
+
+// run_column_stepper for a layered Richards context: the class plane and table beside the state, no step in
+// device memory and no step bound
+int run_layered_column_stepper(lh_ctx* c, lh_state* Y, const lh_state* Ya, double dt, int64_t nsteps, const double* bcv) {
+    if (nsteps <= 0) return LH_OK;
+    Range r_("lh:layered_column_stepper");
+    DeviceBuffer d_bcv; // [nsteps][3][2][2] doubles -> FT on the device
+    if (bcv) {
+        const int rc = upload_boundary_values(c, bcv, size_t(nsteps) * 12, d_bcv);
+        if (rc) return rc;
+    }
+    const bool factors = c->hp.viscosity_kind != LH_FACTOR_NONE || c->hp.impedance_kind != LH_FACTOR_NONE;
+    // (as do_rhs decides it for a fused stage, whose theta_i is the base state's: the launcher drops it with factors)
+    const bool noice = c->tune.zero != 0 && (Y->zero_mask & LH_MASK(LH_VAR_THETA_I));
+    {
+        int rc;
+        if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u))) return rc;
+    }
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        layered_params<FT>(c, P);
+        launch_layered_column_stepper<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), FT(dt), nsteps,
+                                          static_cast<const FT*>(d_bcv.p), factors, noice, c->stream);
+    });
+    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
+    const hipError_t e = launch_error(c, d_bcv);
+    if (e != hipSuccess) return fail(c, LH_ENODEVICE, "layered column stepper launch failed: %s", hipGetErrorString(e));
     return LH_OK;
 }
 
@@ -1998,7 +2036,7 @@ int lh_diagnostics(lh_ctx* c, const lh_state* Y, const lh_state* Ya, lh_state* o
 
 int lh_step_engine(const lh_ctx* c, int64_t nsteps, int32_t per_stage_boundary_values) {
     if (!c || nsteps < 0) return LH_EINVAL;
-    if (layered(c)) return LH_ENGINE_FUSED_STAGES; // the layered kernels have no persistent stepper
+    if (layered(c)) return use_layered_column_stepper(c) ? LH_ENGINE_COLUMN_STEPPER : LH_ENGINE_FUSED_STAGES;
     return use_column_stepper(c, nsteps, per_stage_boundary_values != 0) ? LH_ENGINE_COLUMN_STEPPER : LH_ENGINE_FUSED_STAGES;
 }
 
@@ -2017,8 +2055,11 @@ int lh_step_ssprk33(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double
     Range r_("lh:step_ssprk33");
     int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
-    if (layered(c)) { // three unsegmented fused-stage launches per step, the stage state updated in place
+    if (layered(c)) {
         if ((rc = layered_check(c, "lh_step_ssprk33"))) return rc;
+        // persist=2: all nsteps in one launch of the layered column stepper; otherwise
+        // three unsegmented fused-stage launches per step, the stage state updated in place
+        if (use_layered_column_stepper(c)) return run_layered_column_stepper(c, Y, Ya, dt, nsteps, bcv);
         lh_state* U1;
         if ((rc = stage_states(c, &U1, nullptr))) return rc;
         for (int64_t s = 0; s < nsteps; ++s)

@@ -1037,6 +1037,24 @@ def stable_dt(model: SoilModel, Y: "FieldVector", Ya=None, courant: float = 0.5)
     return out.value
 
 
+def set_tuning(model: SoilModel, spec: str) -> None:
+    """Build extension: the run-time launch overrides of the model's context (lh_set_tuning), in the words of the
+    LH_TUNE environment variable, e.g. "persist=2".  Keys the string does not name go back to their defaults."""
+    be = model._backend()
+    F.check(F.lib().lh_set_tuning(be.ctx, str(spec).encode()), be.ctx)
+
+
+def step_engine(model: SoilModel, nsteps: int, per_stage_boundary_values: bool = False) -> int:
+    """Build extension: what an SSPRK33 call of `nsteps` steps on the model's context would run (lh_step_engine):
+    _ffi.LH_ENGINE_COLUMN_STEPPER, all steps in one launch with the state in registers, or
+    _ffi.LH_ENGINE_FUSED_STAGES, three launches per step."""
+    be = model._backend()
+    rc = F.lib().lh_step_engine(be.ctx, int(nsteps), 1 if per_stage_boundary_values else 0)
+    if rc < 0:
+        F.check(rc, be.ctx)
+    return rc
+
+
 def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, courant: float = 0.5,
                   nsteps: int = 1, dt_max: float = 0.0, profiles_constant: bool = False, hold: int = 1):
     """Build extension: `nsteps` adaptive SSPRK33 steps of `Y` with nothing leaving the device
