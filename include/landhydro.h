@@ -456,6 +456,44 @@ int lh_step_ssprk33_adaptive_hold(lh_ctx*, lh_state* Y, const lh_state* Ya, doub
  * Returns the engine (>= 0) or a negative LH_E* code. */
 int lh_adaptive_hold_engine(const lh_ctx*, int32_t hold);
 
+/* ---- Adaptive SSPRK33 for LAYERED Richards soils (a class map is set).
+ * The scalar calls above keep refusing a context with a map; these three refuse one without
+ * (LH_EMODEL, naming the scalar call), any model but Richards, columns of more than 128 levels, a
+ * prescribed atmosphere, and what every layered call refuses (per-column parameter arrays,
+ * LH_MATH_LIBM) -- all LH_EMODEL; NULL words, courant <= 0, nsteps < 0, nchunks < 0 and a hold outside
+ * 1 ... 2^20 are LH_EINVAL.  They have ONE engine, the layered column stepper with the step in
+ * device memory and the step bound as its epilogue, and do not consult LH_TUNE persist: that key
+ * chooses where there are two engines.  None of them synchronises.
+ *
+ * lh_layered_step_bound_device: the stable-step bound of Y under `courant` into one FT in device
+ * memory -- lh_stable_dt's rule (every cell's slope with its own class's n m, an interior face the sum
+ * of its two true conductivities times the larger slope, a Dirichlet face half a cell away) with the
+ * slopes and maxima in Float32, as lh_rhs_stable_dt accumulates its own: within 1e-6 (Float64) or
+ * 2e-4 (Float32) of lh_stable_dt.  A zero-step launch of the stepper: no plane of Y is written.  The
+ * RCCL min over ranks follows when a communicator is attached.  A column whose bound is NaN is left
+ * out; a call no column contributes to leaves +inf. */
+int lh_layered_step_bound_device(lh_ctx*, const lh_state* Y, const lh_state* Ya, double courant, void* dt_device_ft);
+
+/* nsteps SSPRK33 steps in ONE launch at the step read from device memory (one FT, read once per
+ * launch): bitwise lh_step_ssprk33 with the same step by value.  bcv: as in lh_step_ssprk33.  The
+ * launch is the bound flavour of the stepper; the bound it leaves is written to a word the context
+ * owns and discarded. */
+int lh_step_layered_ssprk33_device_dt(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, const void* dt_device_ft,
+                                      int64_t nsteps, const double* bcv);
+
+/* lh_step_ssprk33_adaptive_hold for a layered context: nchunks chunks of `hold` steps, nothing
+ * leaving the device, one collective per chunk.  The first bound comes from a zero-step launch; per
+ * chunk dt is formed from the rank-reduced bound exactly as the scalar call forms it (dt_max, the
+ * dt = 0 fallback with status bit 2, *elapsed advanced by `hold` successive += dt, the overrun flag
+ * bit 5 for the chunk that ended), then one launch takes `hold` steps and leaves the next bound; the
+ * last chunk's bound is checked as well.  Y, every chunk's dt and *elapsed are bitwise those of: per
+ * chunk lh_layered_step_bound_device, dt = min(bound, dt_max), lh_step_ssprk33(Y, dt, hold) under
+ * LH_TUNE persist=0.  elapsed_device_ft may be NULL.  dt_device_ft holds the last chunk's dt
+ * afterwards.  Boundary values are the constants of lh_set_bc. */
+int lh_step_layered_ssprk33_adaptive_hold(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double courant,
+                                          double dt_max, int64_t nchunks, int32_t hold,
+                                          void* dt_device_ft, void* elapsed_device_ft);
+
 /* Backward-Euler steps of a Richards model: per step, Newton on
  * Y - Yn - dt f(Y, t+dt) = 0 with f exactly lh_rhs's tendency, one tridiagonal solve per
  * column and iteration.  bcv: NULL (current boundary values) or nsteps*4 doubles at t_{n+1}.

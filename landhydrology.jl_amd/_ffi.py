@@ -124,6 +124,9 @@ SIGNATURES = {
     "lh_step_ssprk33_adaptive": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int64, _P, _P]),
     "lh_step_ssprk33_adaptive_hold": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int32, _P, _P]),
     "lh_adaptive_hold_engine": (C.c_int, [_P, C.c_int32]),
+    "lh_layered_step_bound_device": (C.c_int, [_P, _P, _P, C.c_double, _P]),
+    "lh_step_layered_ssprk33_device_dt": (C.c_int, [_P, _P, _P, C.c_double, _P, C.c_int64, _DP]),
+    "lh_step_layered_ssprk33_adaptive_hold": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int32, _P, _P]),
     "lh_step_implicit_euler": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, _DP, C.c_double,
                                          C.c_int32]),
     "lh_implicit_stats": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),

@@ -470,15 +470,17 @@ int layered_check(lh_ctx* c, const char* who) {
         return fail(c, LH_EMODEL, "%s: soil classes (a class map is set) have no LH_MATH_LIBM kernels", who);
     return LH_OK;
 }
-// ... and the entry points that have no layered kernels
-int layered_unsupported(lh_ctx* c, const char* who) {
+// ... and the entry points that have no layered kernels.  `twin`: the layered call that takes the refused one's place on
+// a Richards context (the adaptive SSPRK33 calls); without one the message is what it was
+int layered_unsupported(lh_ctx* c, const char* who, const char* twin = nullptr) {
     if (!layered(c)) return LH_OK;
     if (c->cfg.model != LH_MODEL_RICHARDS) // (the layered implicit integrators step Richards contexts only)
         return fail(c, LH_EMODEL, "%s is not available with soil classes (a class map is set): lh_rhs, lh_ssprk33_stage, "
                                   "lh_step_ssprk33, lh_stable_dt, lh_diagnostics and lh_boundary_fluxes are", who);
     return fail(c, LH_EMODEL, "%s is not available with soil classes (a class map is set): lh_rhs, lh_ssprk33_stage, lh_step_ssprk33, "
                               "lh_stable_dt, lh_diagnostics and lh_boundary_fluxes are, and lh_step_layered_implicit_euler and "
-                              "lh_integrate_layered_trbdf2 step implicitly", who);
+                              "lh_integrate_layered_trbdf2 step implicitly%s%s", who, twin ? "; a layered Richards context calls " : "",
+                twin ? twin : "");
 }
 // vg_fast_all over the classes: whether EVERY class may take the integer-exponent 2^(.) (the same interval test)
 bool classes_vg_fast(const lh_ctx* c) {
@@ -877,13 +879,16 @@ bool use_layered_column_stepper(const lh_ctx* c) {
     return layered(c) && c->cfg.model == LH_MODEL_RICHARDS && c->tune.persist == 2 && c->cfg.nlev <= 128 && !c->hp.atmos_on;
 }
 
-// run_column_stepper for a layered Richards context: the class plane and table beside the state, no step in
-// device memory and no step bound
-int run_layered_column_stepper(lh_ctx* c, lh_state* Y, const lh_state* Ya, double dt, int64_t nsteps, const double* bcv) {
-    if (nsteps <= 0) return LH_OK;
+// run_column_stepper for a layered Richards context: the class plane and table beside the state.  dt_device (with
+// bound_out): the step is read from that FT word, `dt` is the Courant factor and bound_out, an FT
+// word, receives the stable-step bound of the state the call ends on; zero steps are then legal (the bound of Y,
+// no plane written).
+int run_layered_column_stepper(lh_ctx* c, lh_state* Y, const lh_state* Ya, double dt, int64_t nsteps, const double* bcv,
+                               const void* dt_device = nullptr, void* bound_out = nullptr) {
+    if (nsteps <= 0 && !bound_out) return LH_OK;
     Range r_("lh:layered_column_stepper");
     DeviceBuffer d_bcv; // [nsteps][3][2][2] doubles -> FT on the device
-    if (bcv) {
+    if (bcv && nsteps > 0) {
         const int rc = upload_boundary_values(c, bcv, size_t(nsteps) * 12, d_bcv);
         if (rc) return rc;
     }
@@ -898,10 +903,18 @@ int run_layered_column_stepper(lh_ctx* c, lh_state* Y, const lh_state* Ya, doubl
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
         layered_params<FT>(c, P);
-        launch_layered_column_stepper<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), FT(dt), nsteps,
-                                          static_cast<const FT*>(d_bcv.p), factors, noice, c->stream);
+        if (bound_out) {
+            P.dt_out = bound_out;
+            launch_fill<FT>(static_cast<FT*>(bound_out), 1, FT(INFINITY), c->stream); // the minimum starts at +inf
+            launch_layered_column_stepper_bound<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), FT(dt),
+                                                    static_cast<const FT*>(dt_device), nsteps, static_cast<const FT*>(d_bcv.p),
+                                                    factors, noice, c->stream);
+        } else {
+            launch_layered_column_stepper<FT>(P, layered_args<FT>(c), planes_of<FT>(Y), planes_of<FT>(Ya), FT(dt), nsteps,
+                                              static_cast<const FT*>(d_bcv.p), factors, noice, c->stream);
+        }
     });
-    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
+    if (nsteps > 0) mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
     const hipError_t e = launch_error(c, d_bcv);
     if (e != hipSuccess) return fail(c, LH_ENODEVICE, "layered column stepper launch failed: %s", hipGetErrorString(e));
     return LH_OK;
@@ -1977,7 +1990,7 @@ int lh_rhs_stable_dt(lh_ctx* c, double t, const lh_state* Y, const lh_state* Ya,
     if (!(courant > 0)) return fail(c, LH_EINVAL, "lh_rhs_stable_dt: courant must be > 0");
     int rc = validate_model(c);
     if (rc) return rc;
-    if ((rc = layered_unsupported(c, "lh_rhs_stable_dt"))) return rc;
+    if ((rc = layered_unsupported(c, "lh_rhs_stable_dt", "lh_layered_step_bound_device"))) return rc;
     const uint32_t pm = prognostic_mask(c->cfg.model);
     if ((rc = check_state(c, Y, pm, "Y"))) return rc;
     if ((rc = check_state(c, dY, pm, "dY"))) return rc;
@@ -2105,7 +2118,7 @@ int lh_step_ssprk33_device_dt(lh_ctx* c, lh_state* Y, const lh_state* Ya, double
     if (!c || !dt_device_ft) return fail(c, LH_EINVAL, "lh_step_ssprk33_device_dt: NULL argument");
     int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
-    if ((rc = layered_unsupported(c, "lh_step_ssprk33_device_dt"))) return rc;
+    if ((rc = layered_unsupported(c, "lh_step_ssprk33_device_dt", "lh_step_layered_ssprk33_device_dt"))) return rc;
     if (use_column_stepper(c, 1, bcv != nullptr)) return run_column_stepper(c, Y, Ya, 0.0, dt_device_ft, 1, bcv);
     lh_state *U1, *U2;
     if ((rc = stage_states(c, &U1, &U2))) return rc;
@@ -2120,7 +2133,7 @@ int lh_step_ssprk33_adaptive(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
     Range r_("lh:step_ssprk33_adaptive");
     int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
-    if ((rc = layered_unsupported(c, "lh_step_ssprk33_adaptive"))) return rc;
+    if ((rc = layered_unsupported(c, "lh_step_ssprk33_adaptive", "lh_step_layered_ssprk33_adaptive_hold"))) return rc;
     if (!c->scratch_k1 && (rc = state_alloc(c, prognostic_mask(c->cfg.model), &c->scratch_k1))) return rc;
     lh_state* K1 = c->scratch_k1;
     // With a prescribed atmosphere the surface fluxes of a stage come from the stage state's top
@@ -2174,7 +2187,7 @@ int lh_step_ssprk33_adaptive_hold(lh_ctx* c, lh_state* Y, const lh_state* Ya, do
     Range r_("lh:step_ssprk33_adaptive_hold");
     int rc = stepping_preamble(c, Y, Ya);
     if (rc) return rc;
-    if ((rc = layered_unsupported(c, "lh_step_ssprk33_adaptive_hold"))) return rc;
+    if ((rc = layered_unsupported(c, "lh_step_ssprk33_adaptive_hold", "lh_step_layered_ssprk33_adaptive_hold"))) return rc;
     if (nchunks == 0) return LH_OK;
     if (!c->scratch_k1 && (rc = state_alloc(c, prognostic_mask(c->cfg.model), &c->scratch_k1))) return rc;
     lh_state* K1 = c->scratch_k1; // the tendency the bound's launch writes with it: not used
@@ -2242,6 +2255,83 @@ static int implicit_refusals(lh_ctx* c, const char* who, const lh_state* Y, cons
     // that this path stays closed to it should that change)
     if (c->hp.atmos_on) return fail(c, LH_EMODEL, "%s: a prescribed-atmosphere top is not supported", who);
     return stepping_preamble(c, Y, Ya);
+}
+
+// ---- adaptive SSPRK33 for layered Richards soils: the BOUND flavour of the layered column
+// stepper is their one engine, so they do not consult `persist` -- that key chooses where there are two engines
+
+// What the three calls refuse, in this order.  `scalar`: the call that serves a context without a class map
+static int layered_adaptive_refusals(lh_ctx* c, const char* who, const char* scalar, const lh_state* Y, const lh_state* Ya) {
+    if (c->cfg.model != LH_MODEL_RICHARDS)
+        return layered(c) ? fail(c, LH_EMODEL, "%s is not available with soil classes (a class map is set) on this model: it steps %s",
+                                 who, RICHARDS_MODELS)
+                          : fail(c, LH_EMODEL, "%s: %s", who, RICHARDS_MODELS);
+    if (!layered(c))
+        return fail(c, LH_EMODEL, "%s: the context has no class map (lh_set_soil_class_map); %s serves a model without soil classes",
+                    who, scalar);
+    if (int rc = layered_check(c, who)) return rc;
+    if (c->cfg.nlev > 128)
+        return fail(c, LH_EMODEL, "%s: columns of more than 128 levels are not supported (this context has %d): one wave holds a column",
+                    who, int(c->cfg.nlev));
+    if (c->hp.atmos_on) return fail(c, LH_EMODEL, "%s: a prescribed-atmosphere top is not supported", who);
+    return stepping_preamble(c, Y, Ya);
+}
+
+int lh_layered_step_bound_device(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double courant, void* dt_device_ft) {
+    static const char* const who = "lh_layered_step_bound_device";
+    if (!c || !dt_device_ft) return fail(c, LH_EINVAL, "%s: NULL argument", who);
+    if (!(courant > 0)) return fail(c, LH_EINVAL, "%s: need courant > 0", who);
+    if (int rc = layered_adaptive_refusals(c, who, "lh_rhs_stable_dt", Y, Ya)) return rc;
+    // a zero-step launch: the prologue and the bound epilogue, no plane of Y written (so the const is kept in effect);
+    // the step word it reads and does not use is the context's own
+    if (int rc = run_layered_column_stepper(c, const_cast<lh_state*>(Y), Ya, courant, 0, nullptr, c->d_dt, dt_device_ft)) return rc;
+    return allreduce_min(c, dt_device_ft); // the global minimum when a communicator is attached
+}
+
+int lh_step_layered_ssprk33_device_dt(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, const void* dt_device_ft,
+                                      int64_t nsteps, const double* bcv) {
+    (void)t;
+    static const char* const who = "lh_step_layered_ssprk33_device_dt";
+    if (!c || !dt_device_ft) return fail(c, LH_EINVAL, "%s: NULL argument", who);
+    if (nsteps < 0) return fail(c, LH_EINVAL, "%s: need nsteps >= 0", who);
+    if (int rc = layered_adaptive_refusals(c, who, "lh_step_ssprk33_device_dt", Y, Ya)) return rc;
+    if (nsteps == 0) return LH_OK;
+    // the BOUND flavour is the one kernel that reads its step from device memory: the bound it leaves (under a
+    // Courant factor of 1) goes to the context's own word and is discarded
+    return run_layered_column_stepper(c, Y, Ya, 1.0, nsteps, bcv, dt_device_ft, c->d_dt);
+}
+
+int lh_step_layered_ssprk33_adaptive_hold(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double courant, double dt_max,
+                                          int64_t nchunks, int32_t hold, void* dt_device_ft, void* elapsed_device_ft) {
+    (void)t;
+    static const char* const who = "lh_step_layered_ssprk33_adaptive_hold";
+    if (!c || !dt_device_ft) return fail(c, LH_EINVAL, "%s: NULL argument", who); // (elapsed may be NULL, as in the scalar call)
+    if (nchunks < 0 || hold < 1 || hold > ADAPTIVE_HOLD_MAX || !(courant > 0))
+        return fail(c, LH_EINVAL, "%s: need nchunks >= 0, 1 <= hold <= %d and courant > 0", who, int(ADAPTIVE_HOLD_MAX));
+    Range r_("lh:step_layered_ssprk33_adaptive_hold");
+    if (int rc = layered_adaptive_refusals(c, who, "lh_step_ssprk33_adaptive_hold", Y, Ya)) return rc;
+    if (nchunks == 0) return LH_OK;
+    int rc;
+    void* bound = c->d_dt; // the bound of the current Y; dt_device_ft keeps the step of the chunk
+    // (lh_step_ssprk33_adaptive_hold's: the global minimum, the overrun check of the chunk that ended, the next dt, elapsed)
+    auto prepare = [&](int steps, bool check) -> int {
+        if (int r = allreduce_min(c, bound)) return r;
+        with_ft(c, [&](auto ft) {
+            using FT = decltype(ft);
+            launch_dt_hold_prepare<FT>(static_cast<FT*>(dt_device_ft), static_cast<const FT*>(bound), FT(dt_max),
+                                       static_cast<FT*>(elapsed_device_ft), steps, check, c->d_status, c->stream);
+        });
+        return LH_OK;
+    };
+    // the first bound from a zero-step launch; every chunk's launch of `hold` steps leaves the next
+    if ((rc = run_layered_column_stepper(c, Y, Ya, courant, 0, nullptr, dt_device_ft, bound))) return rc;
+    for (int64_t k = 0; k < nchunks; ++k) {
+        if ((rc = prepare(hold, k > 0))) return rc;
+        if ((rc = run_layered_column_stepper(c, Y, Ya, courant, hold, nullptr, dt_device_ft, bound))) return rc;
+    }
+    if ((rc = prepare(0, true))) return rc;
+    LH_HIP(c, hipGetLastError());
+    return LH_OK;
 }
 
 // The helpers below take the buffer's name and size as the entry points write them (`name`, `size`), so that a

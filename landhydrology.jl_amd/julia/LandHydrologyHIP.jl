@@ -475,6 +475,48 @@ function adaptive_hold_engine(ens::ColumnEnsemble, hold::Integer)
 end
 
 """
+    layered_step_bound!(ens, Y, Ya, courant, dt_dev)
+
+The stable-step bound of `Y` for an ensemble with soil classes and a class map (lh_layered_step_bound_device): one FT
+at the device pointer `dt_dev`, the RCCL min over ranks when a communicator is attached.  A zero-step launch of the
+layered column stepper: no plane of `Y` is written.  Richards ensembles of up to 128 levels.
+"""
+function layered_step_bound!(ens::ColumnEnsemble, Y::DeviceState, Ya, courant, dt_dev::Ptr{Cvoid})
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    check(ens.ctx, ccall((:lh_layered_step_bound_device, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}),
+                         ens.ctx, Y.handle, ya, courant, dt_dev))
+    return dt_dev
+end
+
+"`nsteps` SSPRK33 steps of a layered ensemble in one launch, dt read from device memory (lh_step_layered_ssprk33_device_dt)"
+function step_layered_ssprk33_device_dt!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt_dev::Ptr{Cvoid}, nsteps)
+    set_bcs!(ens, t)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    check(ens.ctx, ccall((:lh_step_layered_ssprk33_device_dt, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Int64, Ptr{Float64}),
+                         ens.ctx, Y.handle, ya, t, dt_dev, Int64(nsteps), C_NULL))
+    return Y
+end
+
+"""
+    step_layered_ssprk33_adaptive_hold!(ens, Y, Ya, t, courant, nchunks, hold, dt_dev; dt_max = 0.0, elapsed_dev = C_NULL)
+
+`step_ssprk33_adaptive_hold!` for an ensemble with soil classes and a class map
+(lh_step_layered_ssprk33_adaptive_hold): one launch of the layered column stepper per chunk, which also leaves the
+bound of the state it ends on, and one collective per chunk.  Richards ensembles of up to 128 levels.
+"""
+function step_layered_ssprk33_adaptive_hold!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, courant, nchunks, hold,
+                                             dt_dev::Ptr{Cvoid}; dt_max = 0.0, elapsed_dev::Ptr{Cvoid} = C_NULL)
+    set_bcs!(ens, t)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    check(ens.ctx, ccall((:lh_step_layered_ssprk33_adaptive_hold, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                         ens.ctx, Y.handle, ya, t, courant, dt_max, Int64(nchunks), Int32(hold), dt_dev, elapsed_dev))
+    return Y
+end
+
+"""
     step_implicit_euler!(ens, Y, Ya, t, dt, nsteps; bcv = nothing, tol = 0.0, max_iter = 0) -> (max_iters, unconverged, iterations)
 
 `nsteps` backward-Euler steps of a Richards ensemble (lh_step_implicit_euler): per step Newton on

@@ -1056,7 +1056,7 @@ def step_engine(model: SoilModel, nsteps: int, per_stage_boundary_values: bool =
 
 
 def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, courant: float = 0.5,
-                  nsteps: int = 1, dt_max: float = 0.0, profiles_constant: bool = False, hold: int = 1):
+                  nsteps: int = 1, dt_max: float = 0.0, profiles_constant: bool = False, hold: int = None):
     """Build extension: `nsteps` adaptive SSPRK33 steps of `Y` with nothing leaving the device
     (lh_step_ssprk33_adaptive: per step the tendency and the stable-step bound in one launch, the
     min over ranks when a communicator is attached, stages 2 and 3 -- three evaluations of the
@@ -1069,10 +1069,17 @@ def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, c
     and held over it -- `nsteps` then counts chunks, the call takes `nsteps * hold` steps, with one
     stepper launch (and one collective) per chunk where the persistent column stepper serves it.  Bit
     5 of the status reports a held step that exceeded the stable step of the state it produced.
+    A Richards model with soil_classes (up to 128 levels) has the held form only
+    (lh_step_layered_ssprk33_adaptive_hold: one launch of the layered column stepper per chunk, which leaves the
+    next bound): it is taken for every `hold` that is given, `hold=1` included.  Without `hold` the call is
+    lh_step_ssprk33_adaptive, which has no layered form and refuses as before.
     Returns (simulated time advanced, last dt)."""
+    layered = getattr(model, "soil_classes", None) is not None
+    if layered and (hold is None or not isinstance(model.energy_model, PrescribedTemperatureModel)):
+        _refuse_soil_classes(model, "step_adaptive" if hold is not None else "step_adaptive without hold=k")
+    hold = 1 if hold is None else hold
     if int(hold) < 1:
         raise ValueError("step_adaptive: hold must be >= 1")
-    _refuse_soil_classes(model, "step_adaptive")
     if _time_dependent(model):
         raise ValueError("step_adaptive needs boundary values that do not depend on time")
     if _device_reads_aux(model, Ya):
@@ -1092,7 +1099,10 @@ def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, c
     buf = torch.zeros(2, device=dev, dtype=dtype)
     torch.cuda.synchronize(dev)
     dt_ptr, elapsed_ptr = C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + buf.element_size())
-    if int(hold) == 1:
+    if layered:
+        F.check(L.lh_step_layered_ssprk33_adaptive_hold(be.ctx, Y.handle, ya, float(t), float(courant), float(dt_max),
+                                                        int(nsteps), int(hold), dt_ptr, elapsed_ptr), be.ctx)
+    elif int(hold) == 1:
         F.check(L.lh_step_ssprk33_adaptive(be.ctx, Y.handle, ya, float(t), float(courant), float(dt_max), int(nsteps),
                                            dt_ptr, elapsed_ptr), be.ctx)
     else:
