@@ -202,8 +202,10 @@ int lh_set_soil_class_thermal(lh_ctx*, int32_t nclasses, const lh_soil_class_the
  * and lh_boundary_fluxes evaluate every cell with its class's parameters; they are LH_EMODEL together
  * with a per-column parameter array, LH_MATH_LIBM or a prescribed-atmosphere top, and every other
  * tendency, stepping and tuning entry point (lh_rhs_stable_dt, lh_step_ssprk33_device_dt, the adaptive
- * SSPRK33 calls, the implicit and TR-BDF2 integrators -- the two layered ones step Richards contexts
- * only --, lh_tune_placement) is LH_EMODEL.  Without a map nothing changes. */
+ * SSPRK33 calls, the implicit and TR-BDF2 integrators -- lh_step_layered_implicit_euler and
+ * lh_integrate_layered_trbdf2 step Richards contexts only, lh_step_layered_heat_implicit is the one
+ * implicit call of a layered heat-only context, a layered coupled context has none --,
+ * lh_tune_placement) is LH_EMODEL.  Without a map nothing changes. */
 int lh_set_soil_class_map(lh_ctx*, const uint8_t* host_map, int64_t lev_stride, int64_t col_stride);
 /* the number of classes set and whether a class map is in place (build extension); either may be NULL */
 int lh_soil_class_info(const lh_ctx*, int32_t* nclasses, int32_t* has_map);
@@ -590,6 +592,18 @@ int lh_integrate_layered_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double
 #define LH_HEAT_TRBDF2 1u
 int lh_step_heat_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
                           int64_t nsteps, uint32_t flags, const double* bcv);
+
+/* lh_step_heat_implicit for layered soils (a class map with its thermal supplement is set,
+ * lh_set_soil_class_thermal + lh_set_soil_class_map): the same arguments, flags
+ * (0 or LH_HEAT_TRBDF2), bcv layout and sampling, status bit 0 and asynchrony.  Every cell takes beta,
+ * rho_c_s and kappa from its own class; an interior face is (kappa_lo + kappa_hi) whatever the classes of
+ * its two cells, a Dirichlet energy face takes kappa from the boundary cell's class: f is lh_rhs's
+ * tendency of the same context, still affine in rhoe_int, so a stage stays one exact tridiagonal solve.
+ * LH_EINVAL as lh_step_heat_implicit.  LH_EMODEL, in this order: any model but LH_MODEL_HEAT, a context
+ * without a class map (lh_step_heat_implicit steps it), what every layered call refuses (per-column
+ * parameter arrays, LH_MATH_LIBM).  nsteps == 0 does nothing. */
+int lh_step_layered_heat_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
+                                  int64_t nsteps, uint32_t flags, const double* bcv);
 
 /* Implicit steps of the coupled model, SoilEnergyModel + SoilHydrologyModel
  * (right_hand_side.jl:269-369).  Without conductivity factors the water

@@ -6,6 +6,7 @@
 #include "lh_layered.hpp"
 #include "lh_layered_implicit.hpp"
 #include "lh_layered_heat.hpp"
+#include "lh_layered_heat_implicit.hpp"
 #include "lh_layered_stepper.hpp"
 #include "lh_series.hpp"
 #include "lh_fastmath.hpp"
@@ -117,7 +118,7 @@ struct lh_ctx {
     void* d_imp_stats = nullptr;       // ... and its statistics: int32 max iterations, uint64 unconverged, uint64 iterations
     void* d_tr = nullptr;              // lh_integrate_trbdf2: six FT planes [nlev][stride] (Y_n, f_n, Y_gamma, w, c', d')
     void* d_tr_stats = nullptr;        // ... and its LH_TRBDF2_NSTATS uint64 counters
-    void* d_heat = nullptr;            // lh_step_heat_implicit: eight FT planes [nlev][stride] (three of the factorisation, kc, z; kappa sums, alpha, beta)
+    void* d_heat = nullptr;            // lh_step_heat_implicit, lh_step_layered_heat_implicit: eight FT planes [nlev][stride] (three of the factorisation, kc, z; kappa sums, alpha, beta)
     void* d_cpl = nullptr;             // lh_step_coupled_implicit: three FT planes [nlev][stride] (the water stage's w, c', d'; the energy solve reuses c', d')
     void* d_cpl_tr = nullptr;          // ... and four more for LH_COUPLED_TRBDF2 (the water's Y_n and f_n, the energy's f_n and w2)
     // layered soils (lh_layered.hpp): the classes as given, their ColC<FT> table on the device, and the class
@@ -2547,18 +2548,31 @@ int lh_trbdf2_stats(lh_ctx* c, int64_t* stats) {
     return rc;
 }
 
-int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
-                          uint32_t flags, const double* bcv) {
-    (void)t; // boundary values come through bcv or lh_set_bc, as for lh_step_implicit_euler
+// The heat-only call exists twice, for contexts without and with a class map (lh_heat_implicit.hpp,
+// lh_layered_heat_implicit.hpp), on the same scratch planes and table of boundary values.  One
+// body; what the layered entry point words or does differently is its flavour (RichardsFlavour's fields): the refusal
+// of a context WITHOUT a map and layered_check where the scalar call refuses a map, layered_params, and the launcher
+// that takes layered_heat_args.
+using HeatFlavour = RichardsFlavour;
+
+static int heat_implicit_steps(lh_ctx* c, const HeatFlavour& fl, lh_state* Y, const lh_state* Ya, double dt, int64_t nsteps,
+                               uint32_t flags, const double* bcv) {
     if (!c) return LH_EINVAL;
-    static const char* const who = "lh_step_heat_implicit";
+    const char* const who = fl.who;
     int rc = fixed_step_argument_refusals(c, who, nsteps, dt, flags, LH_HEAT_TRBDF2);
     if (rc) return rc;
-    Range r_("lh:step_heat_implicit");
+    Range r_(fl.range);
     // (its own order, not implicit_refusals': the model, the states, then the class map)
     if (c->cfg.model != LH_MODEL_HEAT) return fail(c, LH_EMODEL, "%s: heat-only models (SoilEnergyModel + PrescribedHydrologyModel)", who);
     if ((rc = stepping_preamble(c, Y, Ya))) return rc;
-    if ((rc = layered_unsupported(c, who))) return rc;
+    if (!fl.layered()) {
+        if ((rc = layered_unsupported(c, who))) return rc;
+    } else {
+        if (!layered(c))
+            return fail(c, LH_EMODEL, "%s: the context has no class map (lh_set_soil_class_map); %s steps a model without soil classes",
+                        who, fl.scalar);
+        if ((rc = layered_check(c, who))) return rc;
+    }
     if (nsteps == 0) return LH_OK;
     const bool trbdf2 = (flags & LH_HEAT_TRBDF2) != 0;
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
@@ -2570,6 +2584,7 @@ int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, 
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
+        if (fl.layered()) layered_params<FT>(c, P);
         HeatImplicitArgs<FT> A;
         A.y = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
         A.vl = static_cast<const FT*>(Ya->plane[LH_VAR_VARTHETA_L]);
@@ -2578,10 +2593,26 @@ int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, 
         A.bcv = static_cast<const FT*>(d_bcv.p);
         A.coef = FT(stage_coefficient(trbdf2, dt));
         A.nsteps = nsteps;
-        launch_heat_implicit<FT>(P, A, any_percol(c), trbdf2, c->math, c->stream);
+        if (fl.layered()) launch_layered_heat_implicit<FT>(P, layered_heat_args<FT>(c), A, trbdf2, c->stream);
+        else launch_heat_implicit<FT>(P, A, any_percol(c), trbdf2, c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_RHOE_INT));
-    return launch_status(c, launch_error(c, d_bcv), "heat implicit");
+    return launch_status(c, launch_error(c, d_bcv), fl.launch);
+}
+
+int lh_step_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                          uint32_t flags, const double* bcv) {
+    (void)t; // boundary values come through bcv or lh_set_bc, as for lh_step_implicit_euler
+    static const HeatFlavour fl = {"lh_step_heat_implicit", nullptr, "lh:step_heat_implicit", "heat implicit"};
+    return heat_implicit_steps(c, fl, Y, Ya, dt, nsteps, flags, bcv);
+}
+
+int lh_step_layered_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                                  uint32_t flags, const double* bcv) {
+    (void)t; // as for lh_step_heat_implicit
+    static const HeatFlavour fl = {"lh_step_layered_heat_implicit", "lh_step_heat_implicit", "lh:step_layered_heat_implicit",
+                                   "layered heat implicit"};
+    return heat_implicit_steps(c, fl, Y, Ya, dt, nsteps, flags, bcv);
 }
 
 int lh_step_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,

@@ -639,6 +639,26 @@ function step_heat_implicit!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt, nst
 end
 
 """
+    step_layered_heat_implicit!(ens, Y, Ya, t, dt, nsteps; method = :euler, bcv = nothing)
+
+`step_heat_implicit!` for a heat-only ensemble with soil classes, their thermal supplement and a class map
+(lh_step_layered_heat_implicit): every cell takes `ρc_s` and `κ` from its own class, a stage stays one exact
+tridiagonal solve.  Arguments as `step_heat_implicit!`.
+"""
+function step_layered_heat_implicit!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt, nsteps; method = :euler,
+                                     bcv = nothing)
+    method in (:euler, :trbdf2) || throw(ArgumentError("method must be :euler or :trbdf2"))
+    set_bcs!(ens, t)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    flags = method === :trbdf2 ? UInt32(1) : UInt32(0)
+    check(ens.ctx, ccall((:lh_step_layered_heat_implicit, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Int64, UInt32, Ptr{Float64}),
+                         ens.ctx, Y.handle, ya, t, dt, Int64(nsteps), flags, vals))
+    return Y
+end
+
+"""
     step_coupled_implicit!(ens, Y, Ya, t, dt, nsteps; method = :euler, bcv = nothing, tol = 0.0, max_iter = 0) -> (max_iters, unconverged, iterations)
 
 `nsteps` implicit steps of a coupled ensemble, SoilEnergyModel + SoilHydrologyModel without conductivity

@@ -283,9 +283,10 @@ def _check_soil_classes(model):
 def _refuse_soil_classes(model, name):
     """The integrators and tools that have no layered kernels (LH_EMODEL in the library)."""
     if getattr(model, "soil_classes", None) is not None:
-        if isinstance(model.energy_model, SoilEnergyModel):    # (the layered implicit integrators step Richards models)
-            raise NotImplementedError(f"{name} is not available with soil classes (a layered coupled or heat-only model "
-                                      "steps with SSPRK33)")
+        if isinstance(model.energy_model, SoilEnergyModel):    # (the layered Newton integrators step Richards models)
+            raise NotImplementedError(f"{name} is not available with soil classes (a layered coupled model steps with "
+                                      "SSPRK33, a layered heat-only model with SSPRK33, LayeredHeatImplicitEuler or "
+                                      "LayeredHeatTRBDF2)")
         raise NotImplementedError(f"{name} is not available with soil classes (layered soils step with SSPRK33, "
                                   "LayeredImplicitEuler or LayeredTRBDF2)")
 
@@ -1227,6 +1228,27 @@ class HeatTRBDF2(HeatImplicitEuler):
     method = "trbdf2"
 
 
+class LayeredHeatImplicitEuler(HeatImplicitEuler):
+    """HeatImplicitEuler for a heat-only model with soil_classes (lh_step_layered_heat_implicit): every cell takes
+    ρc_s and κ from its own class, the tendency stays affine in ρe_int and a step one exact tridiagonal solve.
+    Calls and prescribed profiles as HeatImplicitEuler."""
+
+    def check_scope(self, model):
+        _check_heat_implicit_scope(model, type(self).__name__, layered=True)
+
+    def advance(self, sim, nsteps):
+        it, model = sim.integrator, sim.model
+        if isinstance(it.p, FieldVector):   # the prescribed profiles of THIS time, held through the call
+            make_update_aux(model.energy_model)(it.p, it.t)
+            make_update_aux(model.hydrology_model)(it.p, it.t)
+        step_implicit_layered_heat(model, it.u, it.p, it.t, it.dt, nsteps, self.method)
+
+
+class LayeredHeatTRBDF2(LayeredHeatImplicitEuler):
+    """HeatTRBDF2 for a heat-only model with soil_classes (lh_step_layered_heat_implicit with LH_HEAT_TRBDF2)."""
+    method = "trbdf2"
+
+
 class CoupledImplicitEuler:
     """Backward Euler of the coupled model, SoilEnergyModel + SoilHydrologyModel without conductivity factors
     (lh_step_coupled_implicit): the water stage by ImplicitEuler's safeguarded Newton, the energy stage by one
@@ -1362,13 +1384,19 @@ def _sampled_bcv(model, times, base_t):
     return vals
 
 
-def _check_heat_implicit_scope(model, name="HeatImplicitEuler"):
-    """NotImplementedError for what lh_step_heat_implicit refuses with LH_EMODEL."""
+def _check_heat_implicit_scope(model, name="HeatImplicitEuler", layered=False):
+    """NotImplementedError for what lh_step_heat_implicit refuses with LH_EMODEL; layered: for what
+    lh_step_layered_heat_implicit refuses."""
     if not (isinstance(model.energy_model, SoilEnergyModel) and
             isinstance(model.hydrology_model, PrescribedHydrologyModel)):
         raise NotImplementedError(f"{name} is provided for heat-only models only "
                                   "(SoilEnergyModel + PrescribedHydrologyModel)")
-    _refuse_soil_classes(model, name)
+    if layered:
+        if getattr(model, "soil_classes", None) is None:
+            raise NotImplementedError(f"{name} is provided for models with soil_classes (without them: HeatImplicitEuler, "
+                                      "HeatTRBDF2)")
+    else:
+        _refuse_soil_classes(model, name)
 
 
 def step_implicit_heat(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
@@ -1388,6 +1416,22 @@ def step_implicit_heat(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0
     F.check(F.lib().lh_step_heat_implicit(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
                                           F.LH_HEAT_TRBDF2 if method == "trbdf2" else 0,
                                           _dptr(bcv)), be.ctx)
+
+
+def step_implicit_layered_heat(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
+                               nsteps: int = 1, method: str = "euler"):
+    """Build extension: step_implicit_heat for a heat-only model with soil_classes
+    (lh_step_layered_heat_implicit); arguments and sampling of the boundary values as step_implicit_heat."""
+    if method not in ("euler", "trbdf2"):
+        raise ValueError('step_implicit_layered_heat: method must be "euler" or "trbdf2"')
+    _check_heat_implicit_scope(model, "step_implicit_layered_heat", layered=True)
+    be = model._backend()
+    ya = _handle(Ya)
+    bcv = _sampled_bcv(model, [t + k * dt for k in range(int(nsteps) + 1)], t)
+    be.set_bcs(model, t)
+    F.check(F.lib().lh_step_layered_heat_implicit(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
+                                                  F.LH_HEAT_TRBDF2 if method == "trbdf2" else 0,
+                                                  _dptr(bcv)), be.ctx)
 
 
 def step_implicit(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0, nsteps: int = 1,
