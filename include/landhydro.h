@@ -204,8 +204,8 @@ int lh_set_soil_class_thermal(lh_ctx*, int32_t nclasses, const lh_soil_class_the
  * tendency, stepping and tuning entry point (lh_rhs_stable_dt, lh_step_ssprk33_device_dt, the adaptive
  * SSPRK33 calls, the implicit and TR-BDF2 integrators -- lh_step_layered_implicit_euler and
  * lh_integrate_layered_trbdf2 step Richards contexts only, lh_step_layered_heat_implicit is the one
- * implicit call of a layered heat-only context, a layered coupled context has none --,
- * lh_tune_placement) is LH_EMODEL.  Without a map nothing changes. */
+ * implicit call of a layered heat-only context, lh_step_layered_coupled_implicit that of a layered
+ * coupled context --, lh_tune_placement) is LH_EMODEL.  Without a map nothing changes. */
 int lh_set_soil_class_map(lh_ctx*, const uint8_t* host_map, int64_t lev_stride, int64_t col_stride);
 /* the number of classes set and whether a class map is in place (build extension); either may be NULL */
 int lh_soil_class_info(const lh_ctx*, int32_t* nclasses, int32_t* has_map);
@@ -632,6 +632,25 @@ int lh_step_layered_heat_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, doub
 int lh_step_coupled_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
                              int64_t nsteps, uint32_t flags, const double* bcv, double tol,
                              int32_t max_iter);
+
+/* lh_step_coupled_implicit for layered soils (a class map with its thermal supplement is set,
+ * lh_set_soil_class_thermal + lh_set_soil_class_map): the same arguments, flags
+ * (0 or LH_COUPLED_TRBDF2), bcv layout and sampling, tol / max_iter defaults, status bits 0 and 3,
+ * lh_implicit_stats / lh_implicit_iterations and asynchrony.  (Build-defined like that call: the
+ * reference hands any OrdinaryDiffEq method to DiffEqBase.init, src/Simulations/simulation.jl:34-73.)
+ * The water stage is lh_step_layered_implicit_euler's Newton with every cell's own class (vartheta_l
+ * after a backward-Euler step is bitwise that call's on a Richards context with the same classes); the
+ * energy stage is one tridiagonal solve at the new water state with beta, rho_c_s and kappa of every
+ * cell from its own class, the interior face (kappa_lo + kappa_hi) with the advected energy carried by
+ * the two cells' own true conductivities, a Dirichlet energy face with kappa from the boundary cell's
+ * class: f is lh_rhs's tendency of the same context, and a stage is still solved exactly.
+ * LH_EINVAL as lh_step_coupled_implicit.  LH_EMODEL, in this order: any model but LH_MODEL_COUPLED, a
+ * context without a class map (lh_step_coupled_implicit steps it; that call keeps refusing a context
+ * WITH a map), what every layered call refuses (a prescribed-atmosphere top, per-column parameter
+ * arrays, LH_MATH_LIBM), conductivity factors other than NoEffect.  nsteps == 0 does nothing. */
+int lh_step_layered_coupled_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
+                                     int64_t nsteps, uint32_t flags, const double* bcv, double tol,
+                                     int32_t max_iter);
 
 /* TR-BDF2 of the coupled model from t0 to t1 with per-column error control:
  * lh_integrate_trbdf2's method and controller over both components, every stage solved as

@@ -11,7 +11,8 @@ from ._ffi import LandHydroError, ModelError
 from .parameterizations import *  # noqa: F401,F403
 from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplicitEuler, CoupledTRBDF2, Dirichlet,
                    EarthParameterSet, FieldVector, Float32, Float64, FreeDrainage, HeatImplicitEuler,
-                   HeatTRBDF2, IceImpedance, ImplicitEuler, LayeredHeatImplicitEuler, LayeredHeatTRBDF2,
+                   HeatTRBDF2, IceImpedance, ImplicitEuler, LayeredCoupledImplicitEuler, LayeredCoupledTRBDF2,
+                   LayeredHeatImplicitEuler, LayeredHeatTRBDF2,
                    LayeredImplicitEuler, LayeredTRBDF2, NoBC, NoEffect,
                    PrescribedAtmosForcing,
                    PrescribedHydrologyModel, PrescribedTemperatureModel, Simulation, SoilColumnBC,
@@ -22,7 +23,8 @@ from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplici
                    initialize_states, integrate_coupled_trbdf2, integrate_layered_trbdf2, integrate_series, integrate_trbdf2,
                    make_function_space, make_rhs, make_update_aux, run, set_tuning, stable_dt, step, step_adaptive,
                    step_engine, step_implicit,
-                   step_implicit_coupled, step_implicit_heat, step_implicit_layered, step_implicit_layered_heat,
+                   step_implicit_coupled, step_implicit_heat, step_implicit_layered, step_implicit_layered_coupled,
+                   step_implicit_layered_heat,
                    tune_placement, vanGenuchten)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -7,6 +7,7 @@
 #include "lh_layered_implicit.hpp"
 #include "lh_layered_heat.hpp"
 #include "lh_layered_heat_implicit.hpp"
+#include "lh_layered_coupled_implicit.hpp"
 #include "lh_layered_stepper.hpp"
 #include "lh_series.hpp"
 #include "lh_fastmath.hpp"
@@ -119,7 +120,7 @@ struct lh_ctx {
     void* d_tr = nullptr;              // lh_integrate_trbdf2: six FT planes [nlev][stride] (Y_n, f_n, Y_gamma, w, c', d')
     void* d_tr_stats = nullptr;        // ... and its LH_TRBDF2_NSTATS uint64 counters
     void* d_heat = nullptr;            // lh_step_heat_implicit, lh_step_layered_heat_implicit: eight FT planes [nlev][stride] (three of the factorisation, kc, z; kappa sums, alpha, beta)
-    void* d_cpl = nullptr;             // lh_step_coupled_implicit: three FT planes [nlev][stride] (the water stage's w, c', d'; the energy solve reuses c', d')
+    void* d_cpl = nullptr;             // lh_step_coupled_implicit, lh_step_layered_coupled_implicit: three FT planes [nlev][stride] (the water stage's w, c', d'; the energy solve reuses c', d')
     void* d_cpl_tr = nullptr;          // ... and four more for LH_COUPLED_TRBDF2 (the water's Y_n and f_n, the energy's f_n and w2)
     // layered soils (lh_layered.hpp): the classes as given, their ColC<FT> table on the device, and the class
     // plane [nlev][stride] bytes; a context is "layered" while it holds a map
@@ -2615,17 +2616,21 @@ int lh_step_layered_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, do
     return heat_implicit_steps(c, fl, Y, Ya, dt, nsteps, flags, bcv);
 }
 
-int lh_step_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
-                             uint32_t flags, const double* bcv, double tol, int32_t max_iter) {
-    (void)t; // boundary values come through bcv or lh_set_bc, as for lh_step_heat_implicit
+// The coupled call exists twice, for contexts without and with a class map (lh_coupled_implicit.hpp,
+// lh_layered_coupled_implicit.hpp), on the same scratch planes, statistics block and table of
+// boundary values.  One body; what the layered entry point words or does differently is its flavour (a RichardsFlavour:
+// the fields are the same): implicit_refusals' list for a context that must hold a map, layered_params, and the launcher
+// that takes layered_heat_args.
+static int coupled_implicit_steps(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, const lh_state* Ya, double dt,
+                                  int64_t nsteps, uint32_t flags, const double* bcv, double tol, int32_t max_iter) {
     if (!c) return LH_EINVAL;
-    static const char* const who = "lh_step_coupled_implicit";
+    const char* const who = fl.who;
     int rc = zero_stats(c, c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24");
     if (rc) return rc;
     if ((rc = fixed_step_argument_refusals(c, who, nsteps, dt, flags, LH_COUPLED_TRBDF2))) return rc;
-    Range r_("lh:step_coupled_implicit");
+    Range r_(fl.range);
     // (with a viscosity factor the water reads T: the Jacobian is no longer block triangular)
-    if ((rc = implicit_refusals(c, who, Y, Ya, LH_MODEL_COUPLED, COUPLED_MODELS))) return rc;
+    if ((rc = implicit_refusals(c, who, Y, Ya, LH_MODEL_COUPLED, COUPLED_MODELS, fl.scalar))) return rc;
     newton_defaults(c, tol, max_iter);
     const bool trbdf2 = (flags & LH_COUPLED_TRBDF2) != 0;
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
@@ -2639,6 +2644,7 @@ int lh_step_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
+        if (fl.layered()) layered_params<FT>(c, P);
         CoupledImplicitArgs<FT> A;
         point_at_water<FT>(Y, A);
         A.e = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
@@ -2651,10 +2657,28 @@ int lh_step_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double 
         A.max_iter = max_iter;
         A.nsteps = nsteps;
         point_at_newton_stats(c, A);
-        launch_coupled_implicit<FT>(P, A, any_percol(c), implicit_noice(c, Y), trbdf2, c->math, c->stream);
+        if (fl.layered())
+            launch_layered_coupled_implicit<FT>(P, layered_heat_args<FT>(c), A, implicit_noice(c, Y), trbdf2, c->stream);
+        else
+            launch_coupled_implicit<FT>(P, A, any_percol(c), implicit_noice(c, Y), trbdf2, c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
-    return launch_status(c, launch_error(c, d_bcv), "coupled implicit");
+    return launch_status(c, launch_error(c, d_bcv), fl.launch);
+}
+
+int lh_step_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                             uint32_t flags, const double* bcv, double tol, int32_t max_iter) {
+    (void)t; // boundary values come through bcv or lh_set_bc, as for lh_step_heat_implicit
+    static const RichardsFlavour fl = {"lh_step_coupled_implicit", nullptr, "lh:step_coupled_implicit", "coupled implicit"};
+    return coupled_implicit_steps(c, fl, Y, Ya, dt, nsteps, flags, bcv, tol, max_iter);
+}
+
+int lh_step_layered_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                                     uint32_t flags, const double* bcv, double tol, int32_t max_iter) {
+    (void)t; // as for lh_step_coupled_implicit
+    static const RichardsFlavour fl = {"lh_step_layered_coupled_implicit", "lh_step_coupled_implicit",
+                                      "lh:step_layered_coupled_implicit", "layered coupled implicit"};
+    return coupled_implicit_steps(c, fl, Y, Ya, dt, nsteps, flags, bcv, tol, max_iter);
 }
 
 int lh_integrate_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,

@@ -285,8 +285,8 @@ def _refuse_soil_classes(model, name):
     if getattr(model, "soil_classes", None) is not None:
         if isinstance(model.energy_model, SoilEnergyModel):    # (the layered Newton integrators step Richards models)
             raise NotImplementedError(f"{name} is not available with soil classes (a layered coupled model steps with "
-                                      "SSPRK33, a layered heat-only model with SSPRK33, LayeredHeatImplicitEuler or "
-                                      "LayeredHeatTRBDF2)")
+                                      "SSPRK33, LayeredCoupledImplicitEuler or LayeredCoupledTRBDF2, a layered heat-only "
+                                      "model with SSPRK33, LayeredHeatImplicitEuler or LayeredHeatTRBDF2)")
         raise NotImplementedError(f"{name} is not available with soil classes (layered soils step with SSPRK33, "
                                   "LayeredImplicitEuler or LayeredTRBDF2)")
 
@@ -1264,10 +1264,13 @@ class CoupledImplicitEuler:
     def check_scope(self, model):
         _check_coupled_implicit_scope(model, type(self).__name__)
 
+    def step(self, model, Y, Ya, t, dt, nsteps):
+        """The library call of one chunk (the layered markers put their own here)."""
+        return step_implicit_coupled(model, Y, Ya, t, dt, nsteps, self.method, self.tol, self.max_iter)
+
     def advance(self, sim, nsteps):
         it = sim.integrator
-        it.implicit_stats = step_implicit_coupled(sim.model, it.u, it.p, it.t, it.dt, nsteps, self.method, self.tol,
-                                                  self.max_iter)
+        it.implicit_stats = self.step(sim.model, it.u, it.p, it.t, it.dt, nsteps)
         # the end of a chunk of nsteps intervals of dt; tf itself at the last
         if it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt)):
             return it.tf
@@ -1278,6 +1281,24 @@ class CoupledTRBDF2(CoupledImplicitEuler):
     """Fixed-step TR-BDF2 of the coupled model (lh_step_coupled_implicit with LH_COUPLED_TRBDF2): second order,
     L-stable, two stages per step of the Simulation's dt, no error control.  Scope, calls and arguments as
     CoupledImplicitEuler."""
+    method = "trbdf2"
+
+
+class LayeredCoupledImplicitEuler(CoupledImplicitEuler):
+    """CoupledImplicitEuler for a coupled model with soil_classes (lh_step_layered_coupled_implicit): the water stage
+    by LayeredImplicitEuler's Newton, the energy stage by one tridiagonal solve with ρc_s, κ and the true conductivity
+    of every cell from its own class -- still exactly the monolithic implicit step.  Calls and arguments as
+    CoupledImplicitEuler."""
+
+    def check_scope(self, model):
+        _check_coupled_implicit_scope(model, type(self).__name__, layered=True)
+
+    def step(self, model, Y, Ya, t, dt, nsteps):
+        return step_implicit_layered_coupled(model, Y, Ya, t, dt, nsteps, self.method, self.tol, self.max_iter)
+
+
+class LayeredCoupledTRBDF2(LayeredCoupledImplicitEuler):
+    """CoupledTRBDF2 for a coupled model with soil_classes (lh_step_layered_coupled_implicit with LH_COUPLED_TRBDF2)."""
     method = "trbdf2"
 
 
@@ -1307,12 +1328,17 @@ class CoupledAdaptiveTRBDF2:
         return integrate_coupled_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, dt_cols)
 
 
-def _check_coupled_implicit_scope(model, name="CoupledImplicitEuler"):
+def _check_coupled_implicit_scope(model, name="CoupledImplicitEuler", layered=False):
     """NotImplementedError for what lh_step_coupled_implicit and lh_integrate_coupled_trbdf2 refuse with LH_EMODEL,
-    in their order."""
+    in their order; layered: for what lh_step_layered_coupled_implicit refuses, in the library's words."""
     if not (isinstance(model.energy_model, SoilEnergyModel) and isinstance(model.hydrology_model, SoilHydrologyModel)):
         raise NotImplementedError(f"{name}: coupled models only (SoilEnergyModel + SoilHydrologyModel)")
-    _refuse_soil_classes(model, name)
+    if layered:
+        if getattr(model, "soil_classes", None) is None:
+            raise NotImplementedError(f"{name}: the context has no class map (lh_set_soil_class_map); "
+                                      "lh_step_coupled_implicit steps a model without soil classes")
+    else:
+        _refuse_soil_classes(model, name)
     hm = model.hydrology_model
     if not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
         raise NotImplementedError(f"{name}: conductivity factors other than NoEffect are not supported")
@@ -1328,17 +1354,32 @@ def step_implicit_coupled(model: SoilModel, Y: "FieldVector", Ya=None, t: float 
     Time-dependent Dirichlet closures of both components are sampled at the nsteps + 1 step times t + k dt
     (per-column values at `t`).  Returns (largest Newton iteration count of any water stage, number of
     column-stages that did not converge)."""
+    return _coupled_implicit_call("step_implicit_coupled", False, model, Y, Ya, t, dt, nsteps, method, tol, max_iter)
+
+
+def step_implicit_layered_coupled(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
+                                  nsteps: int = 1, method: str = "euler", tol=None, max_iter=None):
+    """Build extension: step_implicit_coupled for a coupled model with soil_classes
+    (lh_step_layered_coupled_implicit); arguments, sampling of the boundary values and the result as
+    step_implicit_coupled."""
+    return _coupled_implicit_call("step_implicit_layered_coupled", True, model, Y, Ya, t, dt, nsteps, method, tol,
+                                  max_iter)
+
+
+def _coupled_implicit_call(name, layered, model, Y, Ya, t, dt, nsteps, method, tol, max_iter):
+    """step_implicit_coupled and step_implicit_layered_coupled: one library call and its Newton statistics."""
     if method not in ("euler", "trbdf2"):
-        raise ValueError('step_implicit_coupled: method must be "euler" or "trbdf2"')
-    _check_coupled_implicit_scope(model, "step_implicit_coupled")
+        raise ValueError(f'{name}: method must be "euler" or "trbdf2"')
+    _check_coupled_implicit_scope(model, name, layered=layered)
     be = model._backend()
     L = F.lib()
+    call = L.lh_step_layered_coupled_implicit if layered else L.lh_step_coupled_implicit
     ya = _handle(Ya)
     bcv = _sampled_bcv(model, [t + k * dt for k in range(int(nsteps) + 1)], t)
     be.set_bcs(model, t)
-    F.check(L.lh_step_coupled_implicit(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
-                                       F.LH_COUPLED_TRBDF2 if method == "trbdf2" else 0, _dptr(bcv),
-                                       float(tol or 0.0), int(max_iter or 0)), be.ctx)
+    F.check(call(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
+                 F.LH_COUPLED_TRBDF2 if method == "trbdf2" else 0, _dptr(bcv),
+                 float(tol or 0.0), int(max_iter or 0)), be.ctx)
     mi, un = C.c_int32(), C.c_int64()
     F.check(L.lh_implicit_stats(be.ctx, C.byref(mi), C.byref(un)), be.ctx)
     return int(mi.value), int(un.value)
