@@ -204,8 +204,9 @@ int lh_set_soil_class_thermal(lh_ctx*, int32_t nclasses, const lh_soil_class_the
  * tendency, stepping and tuning entry point (lh_rhs_stable_dt, lh_step_ssprk33_device_dt, the adaptive
  * SSPRK33 calls, the implicit and TR-BDF2 integrators -- lh_step_layered_implicit_euler and
  * lh_integrate_layered_trbdf2 step Richards contexts only, lh_step_layered_heat_implicit is the one
- * implicit call of a layered heat-only context, lh_step_layered_coupled_implicit that of a layered
- * coupled context --, lh_tune_placement) is LH_EMODEL.  Without a map nothing changes. */
+ * implicit call of a layered heat-only context, lh_step_layered_coupled_implicit and
+ * lh_integrate_layered_coupled_trbdf2 those of a layered coupled context --, lh_tune_placement) is
+ * LH_EMODEL.  Without a map nothing changes. */
 int lh_set_soil_class_map(lh_ctx*, const uint8_t* host_map, int64_t lev_stride, int64_t col_stride);
 /* the number of classes set and whether a class map is in place (build extension); either may be NULL */
 int lh_soil_class_info(const lh_ctx*, int32_t* nclasses, int32_t* has_map);
@@ -543,14 +544,14 @@ int lh_implicit_iterations(lh_ctx*, int64_t* iterations);
 int lh_integrate_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
                         double abstol, double reltol, uint32_t flags, void* dt_cols_device_ft,
                         const double* bcv);
-/* Of the last lh_integrate_trbdf2, lh_integrate_layered_trbdf2, lh_integrate_coupled_trbdf2 or
- * lh_integrate_series call (the last one's counters over its whole interval, see there),
+/* Of the last lh_integrate_trbdf2, lh_integrate_layered_trbdf2, lh_integrate_coupled_trbdf2,
+ * lh_integrate_layered_coupled_trbdf2 or lh_integrate_series call (the last one's counters over its whole interval, see there),
  * LH_TRBDF2_NSTATS counters (zeros once a later call of any of them was refused): accepted steps,
  * rejected steps, Newton iterations (summed over stages and columns), the largest number of
  * attempted steps of any column,
  * failed columns, wave_steps (the sum over waves of 64 x the wave's largest step count: what the
  * slowest lane of each wave costs) and, in fixed-step mode, unconverged stages (0 after
- * lh_integrate_coupled_trbdf2).  Synchronises. */
+ * lh_integrate_coupled_trbdf2 and lh_integrate_layered_coupled_trbdf2).  Synchronises. */
 #define LH_TRBDF2_NSTATS 7
 int lh_trbdf2_stats(lh_ctx*, int64_t* stats);
 
@@ -675,6 +676,26 @@ int lh_integrate_coupled_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double
                                 double abstol, double abstol_e, double reltol, uint32_t flags,
                                 void* dt_cols_device_ft, const double* bcv);
 
+/* lh_integrate_coupled_trbdf2 for layered soils (a class map with its thermal supplement is set,
+ * lh_set_soil_class_thermal + lh_set_soil_class_map): the same arguments,
+ * tolerance defaults (abstol_e = 0 takes 1e-6 rho_l c_l), bcv layout, dt_cols in and out, error norm E
+ * over both components, controller, step floor and attempt cap, lh_trbdf2_stats, status bits 0 and 4
+ * and asynchrony.  Every stage is solved as lh_step_layered_coupled_implicit solves it: the water by
+ * lh_integrate_layered_trbdf2's Newton with every cell's own class in the safeguard, the energy by one
+ * tridiagonal solve at the new vartheta_l with beta, rho_c_s, kappa and the true conductivity of every
+ * cell from its own class.  The error filters are the two diagonal blocks at Y_1 with per-cell
+ * constants, the energy's the stage-2 matrix against r_e alone (Dirichlet conductances in the pivots,
+ * no boundary offset).  f is lh_rhs's tendency of the same context.
+ * flags must be 0 (fixed steps: lh_step_layered_coupled_implicit with LH_COUPLED_TRBDF2).
+ * LH_EINVAL as lh_integrate_coupled_trbdf2, checked first.  LH_EMODEL, in this order: any model but
+ * LH_MODEL_COUPLED, a context without a class map (lh_integrate_coupled_trbdf2 integrates it; that
+ * call keeps refusing a context WITH a map), what every layered call refuses (a prescribed-atmosphere
+ * top, per-column parameter arrays, LH_MATH_LIBM), conductivity factors other than NoEffect.  A
+ * refused call leaves the statistics zeroed; t1 == t0 does nothing. */
+int lh_integrate_layered_coupled_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1,
+                                        double dt, double abstol, double abstol_e, double reltol,
+                                        uint32_t flags, void* dt_cols_device_ft, const double* bcv);
+
 /* Per-column boundary-value time series for the TR-BDF2 integrators.
  * A series holds nknots >= 2 knot times, finite and strictly increasing (LH_EINVAL otherwise, the
  * message names the first offending knot), and for any (face, component) the values at the knots,
@@ -769,8 +790,8 @@ int lh_allreduce_min(lh_ctx*, void* value_device_ft);
  * found no positive finite step bound (no positive diffusivity anywhere and no dt_max, or a NaN)
  * and was taken with dt = 0; bit 3: an implicit step (lh_step_implicit_euler) did not converge in
  * some column (also the fixed-step mode of lh_integrate_trbdf2); bit 4: a column of
- * lh_integrate_trbdf2 or lh_integrate_coupled_trbdf2 failed (its step fell below the floor or it
- * hit the step cap) and did not reach t1; bit 5: a chunk of lh_step_ssprk33_adaptive_hold held a
+ * lh_integrate_trbdf2, lh_integrate_coupled_trbdf2 or lh_integrate_layered_coupled_trbdf2 failed
+ * (its step fell below the floor or it hit the step cap) and did not reach t1; bit 5: a chunk of lh_step_ssprk33_adaptive_hold held a
  * step that exceeded the stable step of the state it produced; synchronises and clears. */
 int lh_get_status(lh_ctx*, uint32_t* flags);
 int lh_synchronize(lh_ctx*);

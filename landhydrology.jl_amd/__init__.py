@@ -11,7 +11,8 @@ from ._ffi import LandHydroError, ModelError
 from .parameterizations import *  # noqa: F401,F403
 from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplicitEuler, CoupledTRBDF2, Dirichlet,
                    EarthParameterSet, FieldVector, Float32, Float64, FreeDrainage, HeatImplicitEuler,
-                   HeatTRBDF2, IceImpedance, ImplicitEuler, LayeredCoupledImplicitEuler, LayeredCoupledTRBDF2,
+                   HeatTRBDF2, IceImpedance, ImplicitEuler, LayeredCoupledAdaptiveTRBDF2,
+                   LayeredCoupledImplicitEuler, LayeredCoupledTRBDF2,
                    LayeredHeatImplicitEuler, LayeredHeatTRBDF2,
                    LayeredImplicitEuler, LayeredTRBDF2, NoBC, NoEffect,
                    PrescribedAtmosForcing,
@@ -20,7 +21,8 @@ from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplici
                    SoilThermal, SSPRK33,
                    TemperatureDependentViscosity, TRBDF2, VerticalFlux, boundary_fluxes,
                    compute_turbulent_surface_fluxes, coordinates, default_initial_conditions,
-                   initialize_states, integrate_coupled_trbdf2, integrate_layered_trbdf2, integrate_series, integrate_trbdf2,
+                   initialize_states, integrate_coupled_trbdf2,
+                   integrate_layered_coupled_trbdf2, integrate_layered_trbdf2, integrate_series, integrate_trbdf2,
                    make_function_space, make_rhs, make_update_aux, run, set_tuning, stable_dt, step, step_adaptive,
                    step_engine, step_implicit,
                    step_implicit_coupled, step_implicit_heat, step_implicit_layered, step_implicit_layered_coupled,

@@ -8,6 +8,7 @@
 #include "lh_layered_heat.hpp"
 #include "lh_layered_heat_implicit.hpp"
 #include "lh_layered_coupled_implicit.hpp"
+#include "lh_layered_coupled_trbdf2.hpp"
 #include "lh_layered_stepper.hpp"
 #include "lh_series.hpp"
 #include "lh_fastmath.hpp"
@@ -134,7 +135,7 @@ struct lh_ctx {
     bool cls_any_om = false;           // some class has 1 - nu_om != 1 in the working type
     void* d_series_dt = nullptr;       // lh_integrate_series: FT[ncols] step proposals carried across sub-intervals where the caller passes none
     std::vector<lh_bc_series*> series; // the series alive (lh_bc_series_create .. lh_bc_series_destroy)
-    void* d_cpl_ad = nullptr;          // lh_integrate_coupled_trbdf2: ten FT planes [nlev][stride] (d_tr's six for the water; the energy's Y_n, f_n, Y_gamma, w2)
+    void* d_cpl_ad = nullptr;          // lh_integrate_coupled_trbdf2, lh_integrate_layered_coupled_trbdf2: ten FT planes [nlev][stride] (d_tr's six for the water; the energy's Y_n, f_n, Y_gamma, w2)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
     Tune tune;
@@ -2681,15 +2682,17 @@ int lh_step_layered_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya,
     return coupled_implicit_steps(c, fl, Y, Ya, dt, nsteps, flags, bcv, tol, max_iter);
 }
 
-int lh_integrate_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
-                                double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+// The adaptive coupled call exists twice as well (lh_coupled_trbdf2.hpp, lh_layered_coupled_trbdf2.hpp; DESIGN section
+// 4.26), on the same ten scratch planes and statistics block.  One body; the layered flavour is coupled_implicit_steps'.
+static int coupled_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
+                          double abstol, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
     if (!c) return LH_EINVAL;
-    static const char* const who = "lh_integrate_coupled_trbdf2";
+    const char* const who = fl.who;
     int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
     if (rc) return rc;
     if ((rc = trbdf2_argument_refusals(c, who, t0, t1, dt, {abstol, abstol_e, reltol}, flags, 0, bcv))) return rc;
-    Range r_("lh:integrate_coupled_trbdf2");
-    if ((rc = implicit_refusals(c, who, Y, Ya, LH_MODEL_COUPLED, COUPLED_MODELS))) return rc;
+    Range r_(fl.range);
+    if ((rc = implicit_refusals(c, who, Y, Ya, LH_MODEL_COUPLED, COUPLED_MODELS, fl.scalar))) return rc;
     trbdf2_tolerance_defaults(abstol, reltol);
     // (the energy's own default is that of 1e-6 K in water)
     if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
@@ -2701,16 +2704,32 @@ int lh_integrate_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, doub
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
+        if (fl.layered()) layered_params<FT>(c, P);
         CoupledTrbdf2Args<FT> A;
         point_at_water<FT>(Y, A);
         A.e = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
         carve_planes<FT>(c->d_cpl_ad, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp, &A.en, &A.fe, &A.eg, &A.we});
         fill_trbdf2_args<FT>(c, A, t0, t1, dt, abstol, reltol, dt_cols_device_ft, bcv);
         A.abstol_e = abstol_e;
-        launch_coupled_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+        if (fl.layered()) launch_layered_coupled_trbdf2<FT>(P, layered_heat_args<FT>(c), A, implicit_noice(c, Y), c->stream);
+        else launch_coupled_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
-    return launch_status(c, hipGetLastError(), "coupled TR-BDF2");
+    return launch_status(c, hipGetLastError(), fl.launch);
+}
+
+int lh_integrate_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
+                                double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    static const RichardsFlavour fl = {"lh_integrate_coupled_trbdf2", nullptr, "lh:integrate_coupled_trbdf2", "coupled TR-BDF2"};
+    return coupled_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, flags, dt_cols_device_ft, bcv);
+}
+
+int lh_integrate_layered_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
+                                        double abstol, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft,
+                                        const double* bcv) {
+    static const RichardsFlavour fl = {"lh_integrate_layered_coupled_trbdf2", "lh_integrate_coupled_trbdf2",
+                                       "lh:integrate_layered_coupled_trbdf2", "layered coupled TR-BDF2"};
+    return coupled_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, flags, dt_cols_device_ft, bcv);
 }
 
 // ---- boundary-value time series (lh_series.hpp)

@@ -79,8 +79,10 @@ __device__ __forceinline__ FaceState<FT> layered_energy_face(const M& mm, const 
 // energy_sweep_up (lh_coupled_implicit.hpp) with per-cell constants: one upward sweep of the energy equation over
 // a column at the water state y (a rolling window of two cells' closures).  SOLVE: row i of the stage matrix and
 // r_i = in(i, idx) + coef f_e,i(T = beta), eliminated forward; cp, dp receive the back substitution's
-// Y_i = dp_i + cp_i Y_i+1.  Otherwise in(i, idx) is rhoe_int and out(idx, f_e,i) receives the tendency.
-template <typename FT, typename M, bool NOICE, bool VGF, bool SOLVE, typename In, typename Out>
+// Y_i = dp_i + cp_i Y_i+1.  Otherwise in(i, idx) is rhoe_int and out(idx, f_e,i) receives the tendency.  SOLVE with
+// HOMOG: the same matrix against r_i = in(i, idx) alone (no tendency at T = beta, no boundary offset; the Dirichlet
+// conductances stay in the pivots): the error filter of lh_layered_coupled_trbdf2.hpp, as energy_sweep_up's.
+template <typename FT, typename M, bool NOICE, bool VGF, bool SOLVE, bool HOMOG = false, typename In, typename Out>
 __device__ __forceinline__ void layered_energy_sweep_up(const M& mm, const DevParams<FT>& P, const ClassView<FT>& C,
                                                         const ThermTable<FT>& H, const FaceState<FT>& fsb,
                                                         const FaceState<FT>& fst, int64_t col, const FT* y, const FT* ti,
@@ -118,7 +120,8 @@ __device__ __forceinline__ void layered_energy_sweep_up(const M& mm, const DevPa
     cell(idx, K, np, al, be, kap, rcs);
     FT u = FT(0); // T - beta of the cell (tendency sweep)
     if constexpr (!SOLVE) u = al * in(0, idx);
-    FT Flo = boundary(fsb, FACE_BOTTOM, be) - Gb * u; // (a Dirichlet face is affine in T_c: - G_b u on top)
+    FT Flo = FT(0); // (the homogeneous solve reads no flux: the matrix alone)
+    if constexpr (!HOMOG) Flo = boundary(fsb, FACE_BOTTOM, be) - Gb * u; // (a Dirichlet face is affine in T_c: - G_b u on top)
     FT p_lo = FT(0), l_lo = FT(0);                        // p_i-1 and l_i
     FT t_prev = FT(0), ipi_prev = FT(0), rp_prev = FT(0); // t, 1 / pi and r' of the cell below
     for (int i = 0; i < n; ++i) {
@@ -131,8 +134,10 @@ __device__ __forceinline__ void layered_energy_sweep_up(const M& mm, const DevPa
             const FT gh = head_difference(npu, np, P.dz) * P.cg2;
             const FT ks = kap + kapu;
             if constexpr (SOLVE) {
-                const FT E = (P.rhocp_l * (be - P.T_ref)) * K, Eu = (P.rhocp_l * (beu - P.T_ref)) * Ku;
-                Fhi = -ks * ((beu - be) * P.cg2) - (E + Eu) * gh;
+                if constexpr (!HOMOG) {
+                    const FT E = (P.rhocp_l * (be - P.T_ref)) * K, Eu = (P.rhocp_l * (beu - P.T_ref)) * Ku;
+                    Fhi = -ks * ((beu - be) * P.cg2) - (E + Eu) * gh;
+                }
                 const FT g = ks * P.cg2;
                 p_hi = coef * (g + (P.rhocp_l * Ku) * gh);
                 l_up = coef * (g - (P.rhocp_l * K) * gh);
@@ -142,12 +147,13 @@ __device__ __forceinline__ void layered_energy_sweep_up(const M& mm, const DevPa
                 const FT E = (P.rhocp_l * ((be - P.T_ref) + u)) * K, Eu = (P.rhocp_l * ((beu - P.T_ref) + uu)) * Ku;
                 Fhi = -ks * (((uu - u) + (beu - be)) * P.cg2) - (E + Eu) * gh;
             }
-        } else {
+        } else if constexpr (!HOMOG) {
             Fhi = boundary(fst, FACE_TOP, be) + Gt * u;
         }
         const FT f = Flo - Fhi; // layered_heat_rhs_kernel's emit
         if constexpr (SOLVE) {
-            const FT r = in(i, idx) + coef * f;
+            FT r = in(i, idx);
+            if constexpr (!HOMOG) r = r + coef * f;
             FT tp = rcs; // the pivot without the entry below it: a column sum
             if (i == 0) tp = tp + coef * Gb;
             else tp = tp + p_lo * (t_prev * ipi_prev);

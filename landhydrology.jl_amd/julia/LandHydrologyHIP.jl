@@ -742,6 +742,28 @@ function integrate_coupled_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, 
 end
 
 """
+    integrate_layered_coupled_trbdf2!(ens, Y, Ya, t0, t1, dt; abstol = 0.0, abstol_e = 0.0, reltol = 0.0,
+                                      dt_cols = C_NULL, bcv = nothing) -> stats
+
+`integrate_coupled_trbdf2!` for a coupled ensemble with soil classes, their thermal supplement and a class map
+(lh_integrate_layered_coupled_trbdf2): `step_layered_coupled_implicit!`'s stages with every cell's own class under
+the same per-column step and error control.  Arguments and return value as `integrate_coupled_trbdf2!`.
+"""
+function integrate_layered_coupled_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, t1, dt; abstol = 0.0,
+                                           abstol_e = 0.0, reltol = 0.0, dt_cols = C_NULL, bcv = nothing)
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    check(ens.ctx, ccall((:lh_integrate_layered_coupled_trbdf2, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64, UInt32,
+                          Ptr{Cvoid}, Ptr{Float64}),
+                         ens.ctx, Y.handle, ya, t0, t1, dt, abstol, abstol_e, reltol, UInt32(0), dt_cols, vals))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
     BoundarySeries(ens, times, values)
 
 Boundary values as piecewise-linear time series on the device (lh_bc_series_create / lh_bc_series_set).

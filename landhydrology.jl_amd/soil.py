@@ -285,7 +285,8 @@ def _refuse_soil_classes(model, name):
     if getattr(model, "soil_classes", None) is not None:
         if isinstance(model.energy_model, SoilEnergyModel):    # (the layered Newton integrators step Richards models)
             raise NotImplementedError(f"{name} is not available with soil classes (a layered coupled model steps with "
-                                      "SSPRK33, LayeredCoupledImplicitEuler or LayeredCoupledTRBDF2, a layered heat-only "
+                                      "SSPRK33, LayeredCoupledImplicitEuler, LayeredCoupledTRBDF2 or "
+                                      "LayeredCoupledAdaptiveTRBDF2, a layered heat-only "
                                       "model with SSPRK33, LayeredHeatImplicitEuler or LayeredHeatTRBDF2)")
         raise NotImplementedError(f"{name} is not available with soil classes (layered soils step with SSPRK33, "
                                   "LayeredImplicitEuler or LayeredTRBDF2)")
@@ -1328,15 +1329,32 @@ class CoupledAdaptiveTRBDF2:
         return integrate_coupled_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, dt_cols)
 
 
-def _check_coupled_implicit_scope(model, name="CoupledImplicitEuler", layered=False):
+class LayeredCoupledAdaptiveTRBDF2(CoupledAdaptiveTRBDF2):
+    """CoupledAdaptiveTRBDF2 for a coupled model with soil_classes (lh_integrate_layered_coupled_trbdf2):
+    LayeredCoupledTRBDF2's stages with every cell's own class under the same per-column controller and error norm over
+    both components.  Tolerances, the Simulation's dt and the sampling of Dirichlet closures as CoupledAdaptiveTRBDF2.
+    No forcing: boundary-value series are not provided for layered coupled models."""
+
+    def __init__(self, abstol=None, abstol_e=None, reltol=None):
+        super().__init__(abstol, abstol_e, reltol)
+
+    def check_scope(self, model):
+        _check_coupled_implicit_scope(model, type(self).__name__, layered=True, scalar="lh_integrate_coupled_trbdf2")
+
+    def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        return integrate_layered_coupled_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, dt_cols)
+
+
+def _check_coupled_implicit_scope(model, name="CoupledImplicitEuler", layered=False, scalar="lh_step_coupled_implicit"):
     """NotImplementedError for what lh_step_coupled_implicit and lh_integrate_coupled_trbdf2 refuse with LH_EMODEL,
-    in their order; layered: for what lh_step_layered_coupled_implicit refuses, in the library's words."""
+    in their order; layered: for what lh_step_layered_coupled_implicit and lh_integrate_layered_coupled_trbdf2 refuse,
+    in the library's words (`scalar`: the call that serves a model without soil classes)."""
     if not (isinstance(model.energy_model, SoilEnergyModel) and isinstance(model.hydrology_model, SoilHydrologyModel)):
         raise NotImplementedError(f"{name}: coupled models only (SoilEnergyModel + SoilHydrologyModel)")
     if layered:
         if getattr(model, "soil_classes", None) is None:
             raise NotImplementedError(f"{name}: the context has no class map (lh_set_soil_class_map); "
-                                      "lh_step_coupled_implicit steps a model without soil classes")
+                                      f"{scalar} steps a model without soil classes")
     else:
         _refuse_soil_classes(model, name)
     hm = model.hydrology_model
@@ -1580,6 +1598,21 @@ def integrate_coupled_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: fl
     1e-6 ρ_l c_l / 1e-3, each on its own.  `dt_cols` as integrate_trbdf2.  Returns lh_trbdf2_stats as a dict
     (unconverged stays 0)."""
     _check_coupled_implicit_scope(model, "CoupledAdaptiveTRBDF2")
+    return _coupled_trbdf2(F.lib().lh_integrate_coupled_trbdf2, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, dt_cols)
+
+
+def integrate_layered_coupled_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
+                                     dt: float = 1.0, abstol=None, abstol_e=None, reltol=None, dt_cols=None):
+    """Build extension: integrate_coupled_trbdf2 for a coupled model with soil_classes
+    (lh_integrate_layered_coupled_trbdf2); arguments, sampling of the boundary values and the result as
+    integrate_coupled_trbdf2."""
+    _check_coupled_implicit_scope(model, "LayeredCoupledAdaptiveTRBDF2", layered=True, scalar="lh_integrate_coupled_trbdf2")
+    return _coupled_trbdf2(F.lib().lh_integrate_layered_coupled_trbdf2, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol,
+                           dt_cols)
+
+
+def _coupled_trbdf2(call, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, dt_cols):
+    """integrate_coupled_trbdf2's and integrate_layered_coupled_trbdf2's library call and its statistics"""
     be = model._backend()
     ya = _handle(Ya)
     bcv = _sampled_bcv(model, (t0, t1), t0)
@@ -1587,8 +1620,7 @@ def integrate_coupled_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: fl
     ptr = _dt_cols_pointer(model, dt_cols)
     abstol, reltol = _trbdf2_tolerances(abstol, reltol)
     abstol_e = 0.0 if abstol_e is None else float(abstol_e)   # (0: the library's 1e-6 rho_l c_l of its earth parameters)
-    F.check(F.lib().lh_integrate_coupled_trbdf2(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol, abstol_e,
-                                                reltol, 0, ptr, _dptr(bcv)), be.ctx)
+    F.check(call(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol, abstol_e, reltol, 0, ptr, _dptr(bcv)), be.ctx)
     return _trbdf2_stats(be)
 
 
@@ -1707,7 +1739,7 @@ def integrate_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySer
 
 
 def _advance_trbdf2(sim, t1):
-    """The Simulation's TR-BDF2 (TRBDF2, CoupledAdaptiveTRBDF2) from it.t to t1: one library call per dt interval when Dirichlet closures
+    """The Simulation's TR-BDF2 (TRBDF2, CoupledAdaptiveTRBDF2 and their layered forms) from it.t to t1: one library call per dt interval when Dirichlet closures
     depend on time, one for the whole interval otherwise; the per-column step proposals carry over.  With the method's
     `forcing` (a BoundarySeries): one integrate_series call for the whole interval.
     Returns the time reached (t1 itself, not a sum of steps)."""
