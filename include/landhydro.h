@@ -203,8 +203,9 @@ int lh_set_soil_class_thermal(lh_ctx*, int32_t nclasses, const lh_soil_class_the
  * with a per-column parameter array, LH_MATH_LIBM or a prescribed-atmosphere top, and every other
  * tendency, stepping and tuning entry point (lh_rhs_stable_dt, lh_step_ssprk33_device_dt, the adaptive
  * SSPRK33 calls, the implicit and TR-BDF2 integrators -- lh_step_layered_implicit_euler and
- * lh_integrate_layered_trbdf2 step Richards contexts only, lh_step_layered_heat_implicit is the one
- * implicit call of a layered heat-only context, lh_step_layered_coupled_implicit and
+ * lh_integrate_layered_trbdf2 step Richards contexts only, lh_step_layered_heat_implicit and
+ * lh_integrate_layered_heat_trbdf2 are the implicit calls of a layered heat-only context,
+ * lh_step_layered_coupled_implicit and
  * lh_integrate_layered_coupled_trbdf2 those of a layered coupled context --, lh_tune_placement) is
  * LH_EMODEL.  Without a map nothing changes. */
 int lh_set_soil_class_map(lh_ctx*, const uint8_t* host_map, int64_t lev_stride, int64_t col_stride);
@@ -545,13 +546,15 @@ int lh_integrate_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, dou
                         double abstol, double reltol, uint32_t flags, void* dt_cols_device_ft,
                         const double* bcv);
 /* Of the last lh_integrate_trbdf2, lh_integrate_layered_trbdf2, lh_integrate_coupled_trbdf2,
- * lh_integrate_layered_coupled_trbdf2 or lh_integrate_series call (the last one's counters over its whole interval, see there),
+ * lh_integrate_layered_coupled_trbdf2, lh_integrate_heat_trbdf2, lh_integrate_layered_heat_trbdf2 or
+ * lh_integrate_series call (the last one's counters over its whole interval, see there),
  * LH_TRBDF2_NSTATS counters (zeros once a later call of any of them was refused): accepted steps,
  * rejected steps, Newton iterations (summed over stages and columns), the largest number of
  * attempted steps of any column,
  * failed columns, wave_steps (the sum over waves of 64 x the wave's largest step count: what the
  * slowest lane of each wave costs) and, in fixed-step mode, unconverged stages (0 after
- * lh_integrate_coupled_trbdf2 and lh_integrate_layered_coupled_trbdf2).  Synchronises. */
+ * lh_integrate_coupled_trbdf2 and lh_integrate_layered_coupled_trbdf2; after the two heat-only calls,
+ * which solve every stage exactly, the Newton iterations are 0 as well).  Synchronises. */
 #define LH_TRBDF2_NSTATS 7
 int lh_trbdf2_stats(lh_ctx*, int64_t* stats);
 
@@ -696,6 +699,44 @@ int lh_integrate_layered_coupled_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya
                                         double dt, double abstol, double abstol_e, double reltol,
                                         uint32_t flags, void* dt_cols_device_ft, const double* bcv);
 
+/* Adaptive TR-BDF2 of the heat-only model, SoilEnergyModel + PrescribedHydrologyModel, each column with
+ * its own step (build-defined as lh_integrate_trbdf2).  The tendency is affine in
+ * rhoe_int (lh_step_heat_implicit), so both stages of a step are exact tridiagonal solves -- no Newton, no
+ * convergence question -- and the Hosea-Shampine estimate is filtered by the stage matrix itself:
+ * e = (I - d h A)^-1 (b1 h f_n + b2 z_g + b3 z_1), solved homogeneously against the factorisation of the
+ * attempt (Dirichlet conductances in the pivots, no boundary offset);
+ * E = sqrt(mean_i (e_i / (abstol_e + reltol max(|rhoe_n,i|, |rhoe_1,i|)))^2), accepted when E <= 1,
+ * h <- h clamp(0.9 E^(-1/3), 0.2, 5): lh_integrate_trbdf2's controller, step floor (LH_TRBDF2_HMIN_FRAC)
+ * and attempt cap (LH_TRBDF2_MAX_STEPS).  Every other semantic is lh_integrate_coupled_trbdf2's: flags
+ * must be 0 (fixed steps: lh_step_heat_implicit with LH_HEAT_TRBDF2); dt is the initial step; dt_cols is
+ * NULL or ncols FT values on the device, on entry each column's initial step (0: dt), on exit its next
+ * proposal (0: the column failed); bcv is NULL or 8 doubles [t0 | t1][2 faces][2 components], interpolated
+ * linearly in double at every stage time and rounded once to FT (hydrology entries are ignored; per-column
+ * arrays of lh_set_bc take precedence); reltol = 0 takes 1e-3 and abstol_e = 0 takes 1e-6 rho_l c_l, each
+ * on its own; t1 == t0 does nothing; status bit 0 flags a non-finite accepted result, bit 4 a column that
+ * hit the step floor or the attempt cap and keeps its last accepted state; lh_trbdf2_stats reports the
+ * call (Newton iterations and unconverged stages stay 0).  vartheta_l and theta_i of Ya are read once per
+ * call and held through it.  f_n is carried from step to step and a call's first f_n is a fresh
+ * tendency, so a call split in two is not bitwise the whole call (as for the other adaptive integrators).
+ * LH_EINVAL as lh_integrate_trbdf2, checked first; then LH_EMODEL in lh_step_heat_implicit's order: any
+ * model but LH_MODEL_HEAT, the states, a context with a class map.  A refused call leaves the statistics
+ * zeroed.  Asynchronous. */
+int lh_integrate_heat_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
+                             double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft,
+                             const double* bcv);
+
+/* lh_integrate_heat_trbdf2 for layered soils (a class map with its thermal supplement is set,
+ * lh_set_soil_class_thermal + lh_set_soil_class_map): the same arguments,
+ * defaults, bcv layout, dt_cols in and out, error norm, controller, lh_trbdf2_stats, status bits 0 and 4
+ * and asynchrony, with beta, rho_c_s and kappa of every cell from its own class as
+ * lh_step_layered_heat_implicit takes them.  LH_EINVAL as lh_integrate_heat_trbdf2, checked first.
+ * LH_EMODEL, in this order: any model but LH_MODEL_HEAT, the states, a context without a class map
+ * (lh_integrate_heat_trbdf2 integrates it; that call keeps refusing a context WITH a map), what every
+ * layered call refuses (per-column parameter arrays, LH_MATH_LIBM). */
+int lh_integrate_layered_heat_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1,
+                                     double dt, double abstol_e, double reltol, uint32_t flags,
+                                     void* dt_cols_device_ft, const double* bcv);
+
 /* Per-column boundary-value time series for the TR-BDF2 integrators.
  * A series holds nknots >= 2 knot times, finite and strictly increasing (LH_EINVAL otherwise, the
  * message names the first offending knot), and for any (face, component) the values at the knots,
@@ -790,7 +831,8 @@ int lh_allreduce_min(lh_ctx*, void* value_device_ft);
  * found no positive finite step bound (no positive diffusivity anywhere and no dt_max, or a NaN)
  * and was taken with dt = 0; bit 3: an implicit step (lh_step_implicit_euler) did not converge in
  * some column (also the fixed-step mode of lh_integrate_trbdf2); bit 4: a column of
- * lh_integrate_trbdf2, lh_integrate_coupled_trbdf2 or lh_integrate_layered_coupled_trbdf2 failed
+ * lh_integrate_trbdf2, lh_integrate_coupled_trbdf2, lh_integrate_layered_coupled_trbdf2,
+ * lh_integrate_heat_trbdf2 or lh_integrate_layered_heat_trbdf2 failed
  * (its step fell below the floor or it hit the step cap) and did not reach t1; bit 5: a chunk of lh_step_ssprk33_adaptive_hold held a
  * step that exceeded the stable step of the state it produced; synchronises and clears. */
 int lh_get_status(lh_ctx*, uint32_t* flags);

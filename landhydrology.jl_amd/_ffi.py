@@ -142,6 +142,10 @@ SIGNATURES = {
                                               C.c_double, C.c_double, C.c_uint32, _P, _DP]),
     "lh_integrate_layered_coupled_trbdf2": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
                                                       C.c_double, C.c_double, C.c_uint32, _P, _DP]),
+    "lh_integrate_heat_trbdf2": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
+                                           C.c_double, C.c_uint32, _P, _DP]),
+    "lh_integrate_layered_heat_trbdf2": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                   C.c_double, C.c_uint32, _P, _DP]),
     "lh_bc_series_create": (C.c_int, [_P, C.c_int32, _DP, C.POINTER(_P)]),
     "lh_bc_series_set": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _DP, C.c_int64, C.c_int64]),
     "lh_bc_series_destroy": (C.c_int, [_P, _P]),

@@ -7,6 +7,7 @@
 #include "lh_layered_implicit.hpp"
 #include "lh_layered_heat.hpp"
 #include "lh_layered_heat_implicit.hpp"
+#include "lh_layered_heat_trbdf2.hpp"
 #include "lh_layered_coupled_implicit.hpp"
 #include "lh_layered_coupled_trbdf2.hpp"
 #include "lh_layered_stepper.hpp"
@@ -136,6 +137,7 @@ struct lh_ctx {
     void* d_series_dt = nullptr;       // lh_integrate_series: FT[ncols] step proposals carried across sub-intervals where the caller passes none
     std::vector<lh_bc_series*> series; // the series alive (lh_bc_series_create .. lh_bc_series_destroy)
     void* d_cpl_ad = nullptr;          // lh_integrate_coupled_trbdf2, lh_integrate_layered_coupled_trbdf2: ten FT planes [nlev][stride] (d_tr's six for the water; the energy's Y_n, f_n, Y_gamma, w2)
+    void* d_heat_ad = nullptr;         // lh_integrate_heat_trbdf2, lh_integrate_layered_heat_trbdf2: twelve FT planes [nlev][stride] (rho_c_s, alpha, kappa sums, k; the attempt's factorisation; Y_n, f_n, Y_gamma, w2, r')
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int math = MATH_FAST;
     Tune tune;
@@ -1512,6 +1514,7 @@ int lh_destroy(lh_ctx* c) {
     if (c->d_cpl) (void)hipFree(c->d_cpl);
     if (c->d_cpl_tr) (void)hipFree(c->d_cpl_tr);
     if (c->d_cpl_ad) (void)hipFree(c->d_cpl_ad);
+    if (c->d_heat_ad) (void)hipFree(c->d_heat_ad);
     if (c->d_cls_table) (void)hipFree(c->d_cls_table);
     if (c->d_cls_map) (void)hipFree(c->d_cls_map);
     if (c->d_cls_therm) (void)hipFree(c->d_cls_therm);
@@ -2730,6 +2733,74 @@ int lh_integrate_layered_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* 
     static const RichardsFlavour fl = {"lh_integrate_layered_coupled_trbdf2", "lh_integrate_coupled_trbdf2",
                                        "lh:integrate_layered_coupled_trbdf2", "layered coupled TR-BDF2"};
     return coupled_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, flags, dt_cols_device_ft, bcv);
+}
+
+// The adaptive heat-only call exists twice as well (lh_heat_trbdf2.hpp, lh_layered_heat_trbdf2.hpp; DESIGN section
+// 4.27), on the same twelve scratch planes and lh_integrate_trbdf2's statistics block.  One body: lh_integrate_trbdf2's
+// argument checks, then heat_implicit_steps' refusals in its order; the layered flavour is heat_implicit_steps'.
+static int heat_trbdf2(lh_ctx* c, const HeatFlavour& fl, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
+                       double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    if (!c) return LH_EINVAL;
+    const char* const who = fl.who;
+    int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
+    if (rc) return rc;
+    if ((rc = trbdf2_argument_refusals(c, who, t0, t1, dt, {abstol_e, reltol}, flags, 0, bcv))) return rc;
+    Range r_(fl.range);
+    if (c->cfg.model != LH_MODEL_HEAT) return fail(c, LH_EMODEL, "%s: heat-only models (SoilEnergyModel + PrescribedHydrologyModel)", who);
+    if ((rc = stepping_preamble(c, Y, Ya))) return rc;
+    if (!fl.layered()) {
+        if ((rc = layered_unsupported(c, who))) return rc;
+    } else {
+        if (!layered(c))
+            return fail(c, LH_EMODEL, "%s: the context has no class map (lh_set_soil_class_map); %s steps a model without soil classes",
+                        who, fl.scalar);
+        if ((rc = layered_check(c, who))) return rc;
+    }
+    if (!(reltol > 0)) reltol = LH_TRBDF2_RELTOL_DEFAULT;
+    // (lh_integrate_coupled_trbdf2's default for the energy: that of 1e-6 K in water)
+    if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
+    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+    if ((rc = ensure_scratch(c, &c->d_heat_ad, 12 * pl * c->esize, "c->d_heat_ad", "12 * plane"))) return rc;
+    if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
+    if (t1 == t0) return LH_OK;
+    // (level-uniform variables of Ya become planes: the prologue reads each cell once)
+    if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u))) return rc;
+    with_ft(c, [&](auto ft) {
+        using FT = decltype(ft);
+        DevParams<FT> P = make_params<FT>(c);
+        if (fl.layered()) layered_params<FT>(c, P);
+        HeatTrbdf2Args<FT> A;
+        A.y = static_cast<FT*>(Y->plane[LH_VAR_RHOE_INT]);
+        A.vl = static_cast<const FT*>(Ya->plane[LH_VAR_VARTHETA_L]);
+        A.ti = static_cast<const FT*>(Ya->plane[LH_VAR_THETA_I]);
+        carve_planes<FT>(c->d_heat_ad, pl, {&A.rc, &A.al, &A.ks, &A.k, &A.a, &A.iden, &A.cp, &A.yn, &A.fn, &A.yg, &A.w, &A.z});
+        A.dt_cols = static_cast<FT*>(dt_cols_device_ft);
+        A.t0 = t0;
+        A.t1 = t1;
+        A.dt = dt;
+        A.abstol_e = abstol_e;
+        A.reltol = reltol;
+        A.has_bcv = bcv != nullptr;
+        for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
+        A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
+        if (fl.layered()) launch_layered_heat_trbdf2<FT>(P, layered_heat_args<FT>(c), A, c->stream);
+        else launch_heat_trbdf2<FT>(P, A, any_percol(c), c->math, c->stream);
+    });
+    mark_written(Y, LH_MASK(LH_VAR_RHOE_INT));
+    return launch_status(c, hipGetLastError(), fl.launch);
+}
+
+int lh_integrate_heat_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol_e,
+                             double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    static const HeatFlavour fl = {"lh_integrate_heat_trbdf2", nullptr, "lh:integrate_heat_trbdf2", "heat TR-BDF2"};
+    return heat_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol_e, reltol, flags, dt_cols_device_ft, bcv);
+}
+
+int lh_integrate_layered_heat_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
+                                     double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    static const HeatFlavour fl = {"lh_integrate_layered_heat_trbdf2", "lh_integrate_heat_trbdf2", "lh:integrate_layered_heat_trbdf2",
+                                   "layered heat TR-BDF2"};
+    return heat_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol_e, reltol, flags, dt_cols_device_ft, bcv);
 }
 
 // ---- boundary-value time series (lh_series.hpp)

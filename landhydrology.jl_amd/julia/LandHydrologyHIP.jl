@@ -764,6 +764,52 @@ function integrate_layered_coupled_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, 
 end
 
 """
+    integrate_heat_trbdf2!(ens, Y, Ya, t0, t1, dt; abstol_e = 0.0, reltol = 0.0, dt_cols = C_NULL, bcv = nothing) -> stats
+
+TR-BDF2 of a heat-only ensemble from `t0` to `t1` in one call (lh_integrate_heat_trbdf2), every column with its own
+error-controlled step over `ρe_int`: `step_heat_implicit!`'s exact stage solves, the error estimate filtered by the stage
+matrix itself.  `dt` is the initial step; `abstol_e = 0` takes `1e-6 ρ_l c_l` and `reltol = 0` takes 1e-3, each on its
+own.  `dt_cols`: a device buffer of `ncols` values of the ensemble's FT (initial steps in, 0 = `dt`; next proposals out,
+0 = failed column).  `bcv`: 8 values `[t0 | t1][face][component]`, interpolated linearly in between.  Returns
+lh_trbdf2_stats (Newton iterations and unconverged stages stay 0).
+"""
+function integrate_heat_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, t1, dt; abstol_e = 0.0, reltol = 0.0,
+                                dt_cols = C_NULL, bcv = nothing)
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    check(ens.ctx, ccall((:lh_integrate_heat_trbdf2, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, UInt32,
+                          Ptr{Cvoid}, Ptr{Float64}),
+                         ens.ctx, Y.handle, ya, t0, t1, dt, abstol_e, reltol, UInt32(0), dt_cols, vals))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
+    integrate_layered_heat_trbdf2!(ens, Y, Ya, t0, t1, dt; abstol_e = 0.0, reltol = 0.0, dt_cols = C_NULL,
+                                   bcv = nothing) -> stats
+
+`integrate_heat_trbdf2!` for a heat-only ensemble with soil classes, their thermal supplement and a class map
+(lh_integrate_layered_heat_trbdf2): every cell takes `ρc_s` and `κ` from its own class.  Arguments and return value as
+`integrate_heat_trbdf2!`.
+"""
+function integrate_layered_heat_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, t1, dt; abstol_e = 0.0,
+                                        reltol = 0.0, dt_cols = C_NULL, bcv = nothing)
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    check(ens.ctx, ccall((:lh_integrate_layered_heat_trbdf2, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, UInt32,
+                          Ptr{Cvoid}, Ptr{Float64}),
+                         ens.ctx, Y.handle, ya, t0, t1, dt, abstol_e, reltol, UInt32(0), dt_cols, vals))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
     BoundarySeries(ens, times, values)
 
 Boundary values as piecewise-linear time series on the device (lh_bc_series_create / lh_bc_series_set).

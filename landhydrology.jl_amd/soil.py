@@ -1250,6 +1250,60 @@ class LayeredHeatTRBDF2(LayeredHeatImplicitEuler):
     method = "trbdf2"
 
 
+class HeatAdaptiveTRBDF2:
+    """TR-BDF2 of a heat-only model with per-column error control (lh_integrate_heat_trbdf2): HeatTRBDF2's exact
+    stage solves under TRBDF2's controller, the error estimate filtered by the stage matrix itself.  abstol_e (on
+    ρe_int) and reltol: 0.0 = the library's defaults (1e-6 ρ_l c_l, 1e-3), each on its own.  The Simulation's dt is the
+    initial step and the interval at which Dirichlet closures are sampled, as for TRBDF2; the per-column proposals carry
+    over from call to call.  The prescribed ϑ_l and θ_i are refreshed once per saveat chunk and held through it, as for
+    HeatImplicitEuler.  No forcing: boundary-value series are not provided for heat-only models."""
+
+    def __init__(self, abstol_e=0.0, reltol=0.0):
+        self.abstol_e = abstol_e
+        self.reltol = reltol
+
+    def check_scope(self, model):
+        _check_heat_trbdf2_scope(model, type(self).__name__)
+
+    def advance(self, sim, nsteps):
+        it, model = sim.integrator, sim.model
+        if isinstance(it.p, FieldVector):   # the prescribed profiles of THIS time, held through the chunk
+            make_update_aux(model.energy_model)(it.p, it.t)
+            make_update_aux(model.hydrology_model)(it.p, it.t)
+        # the end of a chunk of nsteps intervals of dt, as the fixed-step methods reach it; tf itself at the last
+        last = it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
+        return _advance_trbdf2(sim, it.tf if last else it.t0 + (it._nsteps_done + nsteps) * it.dt)
+
+    def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        return integrate_heat_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol_e, self.reltol, dt_cols)
+
+
+class LayeredHeatAdaptiveTRBDF2(HeatAdaptiveTRBDF2):
+    """HeatAdaptiveTRBDF2 for a heat-only model with soil_classes (lh_integrate_layered_heat_trbdf2): every cell takes
+    ρc_s and κ from its own class.  Tolerances, the Simulation's dt and the sampling of Dirichlet closures as
+    HeatAdaptiveTRBDF2.  No forcing."""
+
+    def check_scope(self, model):
+        _check_heat_trbdf2_scope(model, type(self).__name__, layered=True)
+
+    def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        return integrate_layered_heat_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol_e, self.reltol, dt_cols)
+
+
+def _check_heat_trbdf2_scope(model, name, layered=False):
+    """NotImplementedError for what lh_integrate_heat_trbdf2 refuses with LH_EMODEL, in its order and the library's
+    words; layered: for what lh_integrate_layered_heat_trbdf2 refuses."""
+    if not (isinstance(model.energy_model, SoilEnergyModel) and
+            isinstance(model.hydrology_model, PrescribedHydrologyModel)):
+        raise NotImplementedError(f"{name}: heat-only models (SoilEnergyModel + PrescribedHydrologyModel)")
+    if layered:
+        if getattr(model, "soil_classes", None) is None:
+            raise NotImplementedError(f"{name}: the context has no class map (lh_set_soil_class_map); "
+                                      "lh_integrate_heat_trbdf2 steps a model without soil classes")
+    else:
+        _refuse_soil_classes(model, name)
+
+
 class CoupledImplicitEuler:
     """Backward Euler of the coupled model, SoilEnergyModel + SoilHydrologyModel without conductivity factors
     (lh_step_coupled_implicit): the water stage by ImplicitEuler's safeguarded Newton, the energy stage by one
@@ -1624,6 +1678,40 @@ def _coupled_trbdf2(call, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, dt
     return _trbdf2_stats(be)
 
 
+def integrate_heat_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
+                          dt: float = 1.0, abstol_e=0.0, reltol=0.0, dt_cols=None):
+    """Build extension: TR-BDF2 of the heat-only model's `Y` from t0 to t1 in one library call
+    (lh_integrate_heat_trbdf2), every column with its own error-controlled step over ρe_int.  `dt`: the initial step.
+    Time-dependent Dirichlet closures are evaluated at t0 and t1 and interpolated linearly in between (per-column
+    values at t0).  abstol_e / reltol: 0.0 (or None) = 1e-6 ρ_l c_l / 1e-3, each on its own.  `dt_cols` as
+    integrate_trbdf2.  The prescribed ϑ_l and θ_i are those `Ya` holds.  Returns lh_trbdf2_stats as a dict
+    (newton_iterations and unconverged stay 0)."""
+    _check_heat_trbdf2_scope(model, "HeatAdaptiveTRBDF2")
+    return _heat_trbdf2(F.lib().lh_integrate_heat_trbdf2, model, Y, Ya, t0, t1, dt, abstol_e, reltol, dt_cols)
+
+
+def integrate_layered_heat_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
+                                  dt: float = 1.0, abstol_e=0.0, reltol=0.0, dt_cols=None):
+    """Build extension: integrate_heat_trbdf2 for a heat-only model with soil_classes
+    (lh_integrate_layered_heat_trbdf2); arguments, sampling of the boundary values and the result as
+    integrate_heat_trbdf2."""
+    _check_heat_trbdf2_scope(model, "LayeredHeatAdaptiveTRBDF2", layered=True)
+    return _heat_trbdf2(F.lib().lh_integrate_layered_heat_trbdf2, model, Y, Ya, t0, t1, dt, abstol_e, reltol, dt_cols)
+
+
+def _heat_trbdf2(call, model, Y, Ya, t0, t1, dt, abstol_e, reltol, dt_cols):
+    """integrate_heat_trbdf2's and integrate_layered_heat_trbdf2's library call and its statistics"""
+    be = model._backend()
+    ya = _handle(Ya)
+    bcv = _sampled_bcv(model, (t0, t1), t0)
+    be.set_bcs(model, t0)
+    ptr = _dt_cols_pointer(model, dt_cols)
+    abstol_e = 0.0 if abstol_e is None else float(abstol_e)   # (0: the library's own default, each on its own)
+    reltol = 0.0 if reltol is None else float(reltol)
+    F.check(call(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol_e, reltol, 0, ptr, _dptr(bcv)), be.ctx)
+    return _trbdf2_stats(be)
+
+
 _SERIES_FACE = {"bottom": F.LH_FACE_BOTTOM, "top": F.LH_FACE_TOP, F.LH_FACE_BOTTOM: F.LH_FACE_BOTTOM,
                 F.LH_FACE_TOP: F.LH_FACE_TOP}
 _SERIES_COMP = {"energy": F.LH_COMP_ENERGY, "hydrology": F.LH_COMP_HYDROLOGY, F.LH_COMP_ENERGY: F.LH_COMP_ENERGY,
@@ -1739,7 +1827,7 @@ def integrate_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySer
 
 
 def _advance_trbdf2(sim, t1):
-    """The Simulation's TR-BDF2 (TRBDF2, CoupledAdaptiveTRBDF2 and their layered forms) from it.t to t1: one library call per dt interval when Dirichlet closures
+    """The Simulation's TR-BDF2 (TRBDF2, CoupledAdaptiveTRBDF2, HeatAdaptiveTRBDF2 and their layered forms) from it.t to t1: one library call per dt interval when Dirichlet closures
     depend on time, one for the whole interval otherwise; the per-column step proposals carry over.  With the method's
     `forcing` (a BoundarySeries): one integrate_series call for the whole interval.
     Returns the time reached (t1 itself, not a sum of steps)."""
@@ -1801,10 +1889,10 @@ class Simulation:
 
     def __init__(self, model, method, *, Y_init, dt, tspan, Ya_init, callbacks=None, saveat=None,
                  **kwargs):
-        # (CoupledImplicitEuler, CoupledTRBDF2 and CoupledAdaptiveTRBDF2 are accepted too; the text below is pinned
-        # word for word by tests/test_bcv_sampling.py and so does not name them)
+        # (CoupledImplicitEuler, CoupledTRBDF2, CoupledAdaptiveTRBDF2 and HeatAdaptiveTRBDF2 are accepted too; the text
+        # below is pinned word for word by tests/test_bcv_sampling.py and so does not name them)
         if not isinstance(method, (SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler, CoupledImplicitEuler,
-                                   CoupledAdaptiveTRBDF2)):
+                                   CoupledAdaptiveTRBDF2, HeatAdaptiveTRBDF2)):
             raise NotImplementedError("only SSPRK33, ImplicitEuler, TRBDF2, HeatImplicitEuler and HeatTRBDF2 are "
                                       "provided on the device")
         method.check_scope(model)
