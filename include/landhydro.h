@@ -547,7 +547,8 @@ int lh_integrate_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, dou
                         const double* bcv);
 /* Of the last lh_integrate_trbdf2, lh_integrate_layered_trbdf2, lh_integrate_coupled_trbdf2,
  * lh_integrate_layered_coupled_trbdf2, lh_integrate_heat_trbdf2, lh_integrate_layered_heat_trbdf2 or
- * lh_integrate_series call (the last one's counters over its whole interval, see there),
+ * lh_integrate_series, lh_integrate_heat_series or lh_integrate_layered_coupled_series call (the series
+ * calls' counters over their whole interval, see there),
  * LH_TRBDF2_NSTATS counters (zeros once a later call of any of them was refused): accepted steps,
  * rejected steps, Newton iterations (summed over stages and columns), the largest number of
  * attempted steps of any column,
@@ -781,6 +782,35 @@ int lh_integrate_series(lh_ctx*, lh_state* Y, const lh_state* Ya, const lh_bc_se
                         double dt, double abstol, double abstol_e, double reltol, uint32_t flags,
                         void* dt_cols_device_ft);
 
+/* lh_integrate_series' semantics for the heat-only model (no counterpart in the
+ * reference, as lh_integrate_series): stands for lh_integrate_heat_trbdf2 (a heat-only context without
+ * a class map) or lh_integrate_layered_heat_trbdf2 (with one).  Breakpoints, the bitwise chain (Y, the
+ * dt_cols entry, status bit 0 of calling that entry point once per sub-interval in order, dt_cols
+ * carried and bcv holding the column's own series values at both ends), dt_cols_device_ft == NULL, the
+ * components without a series, the step floor and attempt cap per sub-interval, a failing column and
+ * lh_trbdf2_stats are lh_integrate_series' (Newton iterations and unconverged stages stay 0).  flags
+ * must be 0.  Every sub-interval starts with that entry point's prologue: the closure sweep of the
+ * column and a fresh tendency.  Refusals, in this order: what the entry stood for refuses, in its
+ * order and words (arguments first; any model but LH_MODEL_HEAT is LH_EMODEL); a NULL series or one
+ * of another context, [t0, t1] beyond the knots (LH_EINVAL); an energy series on a face whose
+ * lh_set_bc kind reads no value, then a hydrology series -- a heat-only model has no hydrology
+ * component (LH_EMODEL).  A refused call leaves the statistics zeroed; t0 == t1 does nothing.
+ * Asynchronous. */
+int lh_integrate_heat_series(lh_ctx*, lh_state* Y, const lh_state* Ya, const lh_bc_series*, double t0, double t1,
+                             double dt, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft);
+
+/* lh_integrate_series' semantics for a coupled context with a class map and its thermal supplement
+ * (no counterpart in the reference): stands for
+ * lh_integrate_layered_coupled_trbdf2, with lh_integrate_series' arguments, breakpoints, bitwise chain,
+ * dt_cols handling and statistics (unconverged stages stay 0).  flags must be 0.  Refusals, in this
+ * order: what lh_integrate_layered_coupled_trbdf2 refuses, in its order and words (a coupled context
+ * without a class map is pointed to lh_integrate_series); then the series' own checks as
+ * lh_integrate_series makes them.  A refused call leaves the statistics zeroed; t0 == t1 does nothing.
+ * Asynchronous. */
+int lh_integrate_layered_coupled_series(lh_ctx*, lh_state* Y, const lh_state* Ya, const lh_bc_series*, double t0,
+                                        double t1, double dt, double abstol, double abstol_e, double reltol,
+                                        uint32_t flags, void* dt_cols_device_ft);
+
 /* Build-defined stable step (the reference uses a fixed user dt):
  * courant*dz^2 / max over owned faces of the face diffusivities
  * ((K_lo+K_hi)/2 * max dpsi/dvl, (kappa_lo+kappa_hi)/2 / min rho_c_s; boundary
@@ -832,7 +862,8 @@ int lh_allreduce_min(lh_ctx*, void* value_device_ft);
  * and was taken with dt = 0; bit 3: an implicit step (lh_step_implicit_euler) did not converge in
  * some column (also the fixed-step mode of lh_integrate_trbdf2); bit 4: a column of
  * lh_integrate_trbdf2, lh_integrate_coupled_trbdf2, lh_integrate_layered_coupled_trbdf2,
- * lh_integrate_heat_trbdf2 or lh_integrate_layered_heat_trbdf2 failed
+ * lh_integrate_heat_trbdf2 or lh_integrate_layered_heat_trbdf2 (or of a series call that stands for
+ * one of them) failed
  * (its step fell below the floor or it hit the step cap) and did not reach t1; bit 5: a chunk of lh_step_ssprk33_adaptive_hold held a
  * step that exceeded the stable step of the state it produced; synchronises and clears. */
 int lh_get_status(lh_ctx*, uint32_t* flags);

@@ -11,9 +11,9 @@ from ._ffi import LandHydroError, ModelError
 from .parameterizations import *  # noqa: F401,F403
 from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplicitEuler, CoupledTRBDF2, Dirichlet,
                    EarthParameterSet, FieldVector, Float32, Float64, FreeDrainage, HeatAdaptiveTRBDF2, HeatImplicitEuler,
-                   HeatTRBDF2, IceImpedance, ImplicitEuler, LayeredCoupledAdaptiveTRBDF2,
-                   LayeredCoupledImplicitEuler, LayeredCoupledTRBDF2,
-                   LayeredHeatAdaptiveTRBDF2, LayeredHeatImplicitEuler, LayeredHeatTRBDF2,
+                   HeatSeriesTRBDF2, HeatTRBDF2, IceImpedance, ImplicitEuler, LayeredCoupledAdaptiveTRBDF2,
+                   LayeredCoupledImplicitEuler, LayeredCoupledSeriesTRBDF2, LayeredCoupledTRBDF2,
+                   LayeredHeatAdaptiveTRBDF2, LayeredHeatImplicitEuler, LayeredHeatSeriesTRBDF2, LayeredHeatTRBDF2,
                    LayeredImplicitEuler, LayeredTRBDF2, NoBC, NoEffect,
                    PrescribedAtmosForcing,
                    PrescribedHydrologyModel, PrescribedTemperatureModel, Simulation, SoilColumnBC,
@@ -21,7 +21,8 @@ from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplici
                    SoilThermal, SSPRK33,
                    TemperatureDependentViscosity, TRBDF2, VerticalFlux, boundary_fluxes,
                    compute_turbulent_surface_fluxes, coordinates, default_initial_conditions,
-                   initialize_states, integrate_coupled_trbdf2, integrate_heat_trbdf2,
+                   initialize_states, integrate_coupled_trbdf2, integrate_heat_series, integrate_heat_trbdf2,
+                   integrate_layered_coupled_series,
                    integrate_layered_coupled_trbdf2, integrate_layered_heat_trbdf2, integrate_layered_trbdf2, integrate_series, integrate_trbdf2,
                    make_function_space, make_rhs, make_update_aux, run, set_tuning, stable_dt, step, step_adaptive,
                    step_engine, step_implicit,

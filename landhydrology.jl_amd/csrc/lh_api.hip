@@ -12,6 +12,8 @@
 #include "lh_layered_coupled_trbdf2.hpp"
 #include "lh_layered_stepper.hpp"
 #include "lh_series.hpp"
+#include "lh_series_heat.hpp"
+#include "lh_series_layered_coupled.hpp"
 #include "lh_fastmath.hpp"
 #include "lh_closures.hpp"
 
@@ -2685,10 +2687,103 @@ int lh_step_layered_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya,
     return coupled_implicit_steps(c, fl, Y, Ya, dt, nsteps, flags, bcv, tol, max_iter);
 }
 
+// ---- what the boundary-value-series entry points share (lh_series.hpp; DESIGN sections 4.21 and 4.28)
+
+static bool series_of(const lh_ctx* c, const lh_bc_series* s) {
+    for (const lh_bc_series* k : c->series)
+        if (k == s) return true;
+    return false;
+}
+
+static int series_handle_refusals(lh_ctx* c, const char* who, const lh_bc_series* sr) {
+    if (!sr) return fail(c, LH_EINVAL, "%s: the series is NULL", who);
+    if (!series_of(c, sr)) return fail(c, LH_EINVAL, "%s: not a series of this context", who);
+    return LH_OK;
+}
+
+static int series_span_refusal(lh_ctx* c, const char* who, const lh_bc_series* sr, double t0, double t1) {
+    if (t0 < sr->times.front() || t1 > sr->times.back())
+        return fail(c, LH_EINVAL, "%s: [t0, t1] = [%g, %g] leaves the series' knots [%g, %g] (no extrapolation)", who, t0, t1,
+                    sr->times.front(), sr->times.back());
+    return LH_OK;
+}
+
+// A series on a component the model does not have, or on a (face, component) whose kind reads no value.  A heat-only
+// model has no hydrology boundary condition whose kind could be asked: its hydrology series are refused last, as such
+static int series_kind_refusals(lh_ctx* c, const char* who, const lh_bc_series* sr) {
+    const int model = c->cfg.model;
+    for (int f = 0; f < 2; ++f)
+        for (int k = 0; k < 2; ++k) {
+            if (!sr->d_val[f][k]) continue;
+            const char* fn = f == LH_FACE_TOP ? "top" : "bottom";
+            if (k == LH_COMP_ENERGY && model == LH_MODEL_RICHARDS)
+                return fail(c, LH_EMODEL, "%s: the series has %s energy values, and a Richards model has no energy component", who, fn);
+            if (k == LH_COMP_HYDROLOGY && model == LH_MODEL_HEAT) continue;
+            const int kind = c->hp.bc_kind[f][k];
+            if (kind != LH_BC_FLUX && kind != LH_BC_DIRICHLET)
+                return fail(c, LH_EMODEL, "%s: the series has %s %s values, and the boundary condition there (lh_set_bc) reads no value",
+                            who, fn, k == LH_COMP_ENERGY ? "energy" : "hydrology");
+        }
+    if (model == LH_MODEL_HEAT)
+        for (int f = 0; f < 2; ++f)
+            if (sr->d_val[f][LH_COMP_HYDROLOGY])
+                return fail(c, LH_EMODEL, "%s: the series has %s hydrology values, and a heat-only model has no hydrology component", who,
+                            f == LH_FACE_TOP ? "top" : "bottom");
+    return LH_OK;
+}
+
+// Where the caller passes no step proposals they are carried all the same: in a zeroed buffer of the library's own
+static int series_proposals(lh_ctx* c, void** dt_cols_device_ft) {
+    if (*dt_cols_device_ft) return LH_OK;
+    const size_t bytes = size_t(c->cfg.ncols) * c->esize;
+    if (int rc = ensure_scratch(c, &c->d_series_dt, bytes, "c->d_series_dt", "ncols")) return rc;
+    if (int rc = zero_stats(c, c->d_series_dt, bytes, "c->d_series_dt", "ncols")) return rc;
+    *dt_cols_device_ft = c->d_series_dt;
+    return LH_OK;
+}
+
+// The table's launch argument for [t0, t1]
+static SeriesArgs series_args(const lh_ctx* c, const lh_bc_series* sr, double t0, double t1) {
+    SeriesArgs S;
+    S.times = sr->d_times;
+    for (int f = 0; f < 2; ++f)
+        for (int k = 0; k < 2; ++k) {
+            S.val[f][k] = sr->d_val[f][k];
+            S.knot_stride[f][k] = sr->percol[f][k] ? c->stride : 1;
+            S.col_varies[f][k] = sr->percol[f][k] ? 1 : 0;
+        }
+    // the first knot after t0 and the first one at or after t1: the knots in between are the interior breakpoints
+    const int nk = int(sr->times.size());
+    int k_first = 1, k_end = 1;
+    while (k_first < nk - 1 && !(sr->times[size_t(k_first)] > t0)) ++k_first;
+    while (k_end < nk - 1 && !(sr->times[size_t(k_end)] >= t1)) ++k_end;
+    S.k0 = k_first - 1;
+    S.nsub = k_end - k_first + 1;
+    return S;
+}
+
+// lh_set_bc's values at both ends of every sub-interval: what the chain's bcv holds where there is no series
+static void series_own_values(const lh_ctx* c, double bcv[8]) {
+    for (int k = 0; k < 8; ++k) bcv[k] = c->hp.bc_value[(k >> 1) & 1][k & 1];
+}
+
+// What lh_integrate_heat_series and lh_integrate_layered_coupled_series add to the call they wrap (heat_trbdf2,
+// coupled_trbdf2 below): the series as the caller passed it.  Its checks come behind the wrapped call's own
+struct SeriesCall {
+    const lh_bc_series* sr;
+};
+static int series_call_refusals(lh_ctx* c, const char* who, const SeriesCall& sc, double t0, double t1) {
+    if (int rc = series_handle_refusals(c, who, sc.sr)) return rc;
+    if (int rc = series_span_refusal(c, who, sc.sr, t0, t1)) return rc;
+    return series_kind_refusals(c, who, sc.sr);
+}
+
 // The adaptive coupled call exists twice as well (lh_coupled_trbdf2.hpp, lh_layered_coupled_trbdf2.hpp; DESIGN section
 // 4.26), on the same ten scratch planes and statistics block.  One body; the layered flavour is coupled_implicit_steps'.
+// `sc`: NULL, or the series of lh_integrate_layered_coupled_series (bcv is NULL then: one launch for the chain of calls).
 static int coupled_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
-                          double abstol, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+                          double abstol, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv,
+                          const SeriesCall* sc = nullptr) {
     if (!c) return LH_EINVAL;
     const char* const who = fl.who;
     int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
@@ -2696,6 +2791,7 @@ static int coupled_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, con
     if ((rc = trbdf2_argument_refusals(c, who, t0, t1, dt, {abstol, abstol_e, reltol}, flags, 0, bcv))) return rc;
     Range r_(fl.range);
     if ((rc = implicit_refusals(c, who, Y, Ya, LH_MODEL_COUPLED, COUPLED_MODELS, fl.scalar))) return rc;
+    if (sc && (rc = series_call_refusals(c, who, *sc, t0, t1))) return rc;
     trbdf2_tolerance_defaults(abstol, reltol);
     // (the energy's own default is that of 1e-6 K in water)
     if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
@@ -2703,6 +2799,12 @@ static int coupled_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, con
     if ((rc = ensure_scratch(c, &c->d_cpl_ad, 10 * pl * c->esize, "c->d_cpl_ad", "10 * plane"))) return rc;
     if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
     if (t1 == t0) return LH_OK;
+    double own[8];
+    if (sc) {
+        if ((rc = series_proposals(c, &dt_cols_device_ft))) return rc;
+        series_own_values(c, own);
+        bcv = own;
+    }
     if ((rc = materialize(c, Y, ~0u))) return rc;
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
@@ -2714,7 +2816,10 @@ static int coupled_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, con
         carve_planes<FT>(c->d_cpl_ad, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp, &A.en, &A.fe, &A.eg, &A.we});
         fill_trbdf2_args<FT>(c, A, t0, t1, dt, abstol, reltol, dt_cols_device_ft, bcv);
         A.abstol_e = abstol_e;
-        if (fl.layered()) launch_layered_coupled_trbdf2<FT>(P, layered_heat_args<FT>(c), A, implicit_noice(c, Y), c->stream);
+        if (sc) // (a layered flavour: the series of a context without a map is lh_integrate_series')
+            launch_series_layered_coupled_trbdf2<FT>(P, layered_heat_args<FT>(c), A, series_args(c, sc->sr, t0, t1), implicit_noice(c, Y),
+                                                     c->stream);
+        else if (fl.layered()) launch_layered_coupled_trbdf2<FT>(P, layered_heat_args<FT>(c), A, implicit_noice(c, Y), c->stream);
         else launch_coupled_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
@@ -2738,8 +2843,10 @@ int lh_integrate_layered_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* 
 // The adaptive heat-only call exists twice as well (lh_heat_trbdf2.hpp, lh_layered_heat_trbdf2.hpp; DESIGN section
 // 4.27), on the same twelve scratch planes and lh_integrate_trbdf2's statistics block.  One body: lh_integrate_trbdf2's
 // argument checks, then heat_implicit_steps' refusals in its order; the layered flavour is heat_implicit_steps'.
+// `sc`: NULL, or the series of lh_integrate_heat_series (bcv is NULL then: one launch for the chain of calls).
 static int heat_trbdf2(lh_ctx* c, const HeatFlavour& fl, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
-                       double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+                       double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv,
+                       const SeriesCall* sc = nullptr) {
     if (!c) return LH_EINVAL;
     const char* const who = fl.who;
     int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
@@ -2756,6 +2863,7 @@ static int heat_trbdf2(lh_ctx* c, const HeatFlavour& fl, lh_state* Y, const lh_s
                         who, fl.scalar);
         if ((rc = layered_check(c, who))) return rc;
     }
+    if (sc && (rc = series_call_refusals(c, who, *sc, t0, t1))) return rc;
     if (!(reltol > 0)) reltol = LH_TRBDF2_RELTOL_DEFAULT;
     // (lh_integrate_coupled_trbdf2's default for the energy: that of 1e-6 K in water)
     if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
@@ -2763,6 +2871,12 @@ static int heat_trbdf2(lh_ctx* c, const HeatFlavour& fl, lh_state* Y, const lh_s
     if ((rc = ensure_scratch(c, &c->d_heat_ad, 12 * pl * c->esize, "c->d_heat_ad", "12 * plane"))) return rc;
     if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
     if (t1 == t0) return LH_OK;
+    double own[8];
+    if (sc) {
+        if ((rc = series_proposals(c, &dt_cols_device_ft))) return rc;
+        series_own_values(c, own);
+        bcv = own;
+    }
     // (level-uniform variables of Ya become planes: the prologue reads each cell once)
     if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u))) return rc;
     with_ft(c, [&](auto ft) {
@@ -2783,7 +2897,11 @@ static int heat_trbdf2(lh_ctx* c, const HeatFlavour& fl, lh_state* Y, const lh_s
         A.has_bcv = bcv != nullptr;
         for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
         A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
-        if (fl.layered()) launch_layered_heat_trbdf2<FT>(P, layered_heat_args<FT>(c), A, c->stream);
+        if (sc) {
+            const SeriesArgs S = series_args(c, sc->sr, t0, t1);
+            if (fl.layered()) launch_series_layered_heat_trbdf2<FT>(P, layered_heat_args<FT>(c), A, S, c->stream);
+            else launch_series_heat_trbdf2<FT>(P, A, S, any_percol(c), c->math, c->stream);
+        } else if (fl.layered()) launch_layered_heat_trbdf2<FT>(P, layered_heat_args<FT>(c), A, c->stream);
         else launch_heat_trbdf2<FT>(P, A, any_percol(c), c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_RHOE_INT));
@@ -2804,12 +2922,6 @@ int lh_integrate_layered_heat_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya,
 }
 
 // ---- boundary-value time series (lh_series.hpp)
-
-static bool series_of(const lh_ctx* c, const lh_bc_series* s) {
-    for (const lh_bc_series* k : c->series)
-        if (k == s) return true;
-    return false;
-}
 
 int lh_bc_series_create(lh_ctx* c, int32_t nknots, const double* times, lh_bc_series** out) {
     if (!c) return LH_EINVAL;
@@ -2897,8 +3009,7 @@ int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_
     static const char* const who = "lh_integrate_series";
     int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
     if (rc) return rc;
-    if (!sr) return fail(c, LH_EINVAL, "%s: the series is NULL", who);
-    if (!series_of(c, sr)) return fail(c, LH_EINVAL, "%s: not a series of this context", who);
+    if ((rc = series_handle_refusals(c, who, sr))) return rc;
     if (c->cfg.model == LH_MODEL_HEAT)
         return fail(c, LH_EMODEL, "%s: Richards models, with or without a class map, and coupled models without one only", who);
     const bool coupled = c->cfg.model == LH_MODEL_COUPLED;
@@ -2906,24 +3017,12 @@ int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_
     rc = coupled ? trbdf2_argument_refusals(c, who, t0, t1, dt, {abstol, abstol_e, reltol}, flags, 0, nullptr)
                  : trbdf2_argument_refusals(c, who, t0, t1, dt, {abstol, reltol}, flags, LH_TRBDF2_FIXED, nullptr);
     if (rc) return rc;
-    if (t0 < sr->times.front() || t1 > sr->times.back())
-        return fail(c, LH_EINVAL, "%s: [t0, t1] = [%g, %g] leaves the series' knots [%g, %g] (no extrapolation)", who, t0, t1,
-                    sr->times.front(), sr->times.back());
+    if ((rc = series_span_refusal(c, who, sr, t0, t1))) return rc;
     Range r_("lh:integrate_series");
     if ((rc = implicit_refusals(c, who, Y, Ya, coupled ? LH_MODEL_COUPLED : LH_MODEL_RICHARDS, coupled ? COUPLED_MODELS : RICHARDS_MODELS,
                                 lay ? "lh_integrate_trbdf2" : nullptr)))
         return rc;
-    for (int f = 0; f < 2; ++f)
-        for (int k = 0; k < 2; ++k) {
-            if (!sr->d_val[f][k]) continue;
-            const char* fn = f == LH_FACE_TOP ? "top" : "bottom";
-            if (k == LH_COMP_ENERGY && !coupled)
-                return fail(c, LH_EMODEL, "%s: the series has %s energy values, and a Richards model has no energy component", who, fn);
-            const int kind = c->hp.bc_kind[f][k];
-            if (kind != LH_BC_FLUX && kind != LH_BC_DIRICHLET)
-                return fail(c, LH_EMODEL, "%s: the series has %s %s values, and the boundary condition there (lh_set_bc) reads no value",
-                            who, fn, k == LH_COMP_ENERGY ? "energy" : "hydrology");
-        }
+    if ((rc = series_kind_refusals(c, who, sr))) return rc;
     trbdf2_tolerance_defaults(abstol, reltol);
     if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
     double tol = 0; // (fixed mode: lh_step_implicit_euler's defaults)
@@ -2936,32 +3035,11 @@ int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_
         return rc;
     if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
     if (t1 == t0) return LH_OK;
-    if (!dt_cols_device_ft) { // the proposals are carried all the same: a zeroed buffer of the library's own
-        const size_t bytes = size_t(c->cfg.ncols) * c->esize;
-        if ((rc = ensure_scratch(c, &c->d_series_dt, bytes, "c->d_series_dt", "ncols"))) return rc;
-        if ((rc = zero_stats(c, c->d_series_dt, bytes, "c->d_series_dt", "ncols"))) return rc;
-        dt_cols_device_ft = c->d_series_dt;
-    }
+    if ((rc = series_proposals(c, &dt_cols_device_ft))) return rc;
     if ((rc = materialize(c, Y, ~0u))) return rc;
-    SeriesArgs S;
-    S.times = sr->d_times;
-    for (int f = 0; f < 2; ++f)
-        for (int k = 0; k < 2; ++k) {
-            S.val[f][k] = sr->d_val[f][k];
-            S.knot_stride[f][k] = sr->percol[f][k] ? c->stride : 1;
-            S.col_varies[f][k] = sr->percol[f][k] ? 1 : 0;
-        }
-    {   // the first knot after t0 and the first one at or after t1: the knots in between are the interior breakpoints
-        const int nk = int(sr->times.size());
-        int k_first = 1, k_end = 1;
-        while (k_first < nk - 1 && !(sr->times[size_t(k_first)] > t0)) ++k_first;
-        while (k_end < nk - 1 && !(sr->times[size_t(k_end)] >= t1)) ++k_end;
-        S.k0 = k_first - 1;
-        S.nsub = k_end - k_first + 1;
-    }
-    // lh_set_bc's values at both ends of every sub-interval: what the chain's bcv holds where there is no series
+    const SeriesArgs S = series_args(c, sr, t0, t1);
     double bcv[8];
-    for (int k = 0; k < 8; ++k) bcv[k] = c->hp.bc_value[(k >> 1) & 1][k & 1];
+    series_own_values(c, bcv);
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
@@ -2988,6 +3066,29 @@ int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | (coupled ? LH_MASK(LH_VAR_RHOE_INT) : 0u));
     return launch_status(c, hipGetLastError(), "series TR-BDF2");
+}
+
+// One launch for the chain of lh_integrate_heat_trbdf2 or, with a class map, lh_integrate_layered_heat_trbdf2 calls
+// (DESIGN section 4.28): heat_trbdf2 in the flavour of the context, under this call's name
+int lh_integrate_heat_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_series* sr, double t0, double t1, double dt,
+                             double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft) {
+    if (!c) return LH_EINVAL;
+    static const char* const who = "lh_integrate_heat_series";
+    static const HeatFlavour scalar = {who, nullptr, "lh:integrate_heat_series", "heat series TR-BDF2"};
+    static const HeatFlavour lay = {who, who, "lh:integrate_heat_series", "layered heat series TR-BDF2"};
+    const SeriesCall sc = {sr};
+    return heat_trbdf2(c, layered(c) ? lay : scalar, Y, Ya, t0, t1, dt, abstol_e, reltol, flags, dt_cols_device_ft, nullptr, &sc);
+}
+
+// ... and for the chain of lh_integrate_layered_coupled_trbdf2 calls: a coupled context without a class map is
+// lh_integrate_series'
+int lh_integrate_layered_coupled_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_series* sr, double t0, double t1,
+                                        double dt, double abstol, double abstol_e, double reltol, uint32_t flags,
+                                        void* dt_cols_device_ft) {
+    static const RichardsFlavour fl = {"lh_integrate_layered_coupled_series", "lh_integrate_series",
+                                       "lh:integrate_layered_coupled_series", "layered coupled series TR-BDF2"};
+    const SeriesCall sc = {sr};
+    return coupled_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, flags, dt_cols_device_ft, nullptr, &sc);
 }
 
 int lh_stable_dt_device(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double courant, void* d_out) {

@@ -67,7 +67,8 @@ __device__ __forceinline__ void series_params(DevParams<FT>& P, const SeriesArgs
 }
 
 // Sub-interval j of the call in B (a lane-local copy of the launch's A, whose bcv holds lh_set_bc's values at
-// both ends): its ends and the column's boundary values at them.  ARGS: Trbdf2Args or CoupledTrbdf2Args.
+// both ends): its ends and the column's boundary values at them.  ARGS: Trbdf2Args, CoupledTrbdf2Args or (lh_series_heat.hpp)
+// HeatTrbdf2Args -- any launch argument with t0, t1, bcv[8] and has_bcv, which the launch sets to 1.
 template <typename ARGS>
 __device__ __forceinline__ void series_sub_interval(const ARGS& A, const SeriesArgs& S, int j, int64_t col, ARGS& B) {
     const int k = S.k0 + j;

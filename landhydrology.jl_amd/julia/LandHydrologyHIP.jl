@@ -875,6 +875,48 @@ function integrate_series!(ens::ColumnEnsemble, Y::DeviceState, Ya, series::Boun
 end
 
 """
+    integrate_heat_series!(ens, Y, Ya, series, t0, t1, dt; abstol_e = 0.0, reltol = 0.0, dt_cols = C_NULL) -> stats
+
+TR-BDF2 of a heat-only ensemble from `t0` to `t1` under a `BoundarySeries` in one call (lh_integrate_heat_series):
+bitwise the chain of `integrate_heat_trbdf2!` or, with soil classes, `integrate_layered_heat_trbdf2!` calls over the
+sub-intervals between the series' knots, every column with its own boundary values and walking its own sub-intervals.
+The prescribed `ϑ_l` and `θ_i` are those `Ya` holds.  Returns the 7 counters of lh_trbdf2_stats over the whole call.
+"""
+function integrate_heat_series!(ens::ColumnEnsemble, Y::DeviceState, Ya, series::BoundarySeries, t0, t1, dt; abstol_e = 0.0,
+                                reltol = 0.0, dt_cols = C_NULL)
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    check(ens.ctx, ccall((:lh_integrate_heat_series, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, UInt32,
+                          Ptr{Cvoid}),
+                         ens.ctx, Y.handle, ya, series.handle, t0, t1, dt, abstol_e, reltol, UInt32(0), dt_cols))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
+    integrate_layered_coupled_series!(ens, Y, Ya, series, t0, t1, dt; abstol = 0.0, abstol_e = 0.0, reltol = 0.0,
+                                      dt_cols = C_NULL) -> stats
+
+`integrate_series!` for a coupled ensemble with soil classes, their thermal supplement and a class map
+(lh_integrate_layered_coupled_series): bitwise the chain of `integrate_layered_coupled_trbdf2!` calls over the
+sub-intervals between the series' knots.  Returns the 7 counters of lh_trbdf2_stats over the whole call.
+"""
+function integrate_layered_coupled_series!(ens::ColumnEnsemble, Y::DeviceState, Ya, series::BoundarySeries, t0, t1, dt;
+                                           abstol = 0.0, abstol_e = 0.0, reltol = 0.0, dt_cols = C_NULL)
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    check(ens.ctx, ccall((:lh_integrate_layered_coupled_series, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64,
+                          UInt32, Ptr{Cvoid}),
+                         ens.ctx, Y.handle, ya, series.handle, t0, t1, dt, abstol, abstol_e, reltol, UInt32(0), dt_cols))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
     tune_placement!(ens, Y, Ya, dY = nothing; max_candidates = 0, move_input = true)
 
 Let the library place the state written by `rhs!` (`dY` given) or the SSPRK33 stage state

@@ -1179,6 +1179,10 @@ class TRBDF2:
     def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
         return integrate_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.reltol, self.adaptive, dt_cols)
 
+    def integrate_forcing(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        """One library call from t0 to t1 under self.forcing: what _advance_trbdf2 makes of an advance."""
+        return integrate_series(model, Y, Ya, self.forcing, t0, t1, dt, self.abstol, None, self.reltol, self.adaptive, dt_cols)
+
 
 class LayeredImplicitEuler(ImplicitEuler):
     """ImplicitEuler for a Richards model with soil_classes (lh_step_layered_implicit_euler): the same Newton,
@@ -1256,7 +1260,7 @@ class HeatAdaptiveTRBDF2:
     ρe_int) and reltol: 0.0 = the library's defaults (1e-6 ρ_l c_l, 1e-3), each on its own.  The Simulation's dt is the
     initial step and the interval at which Dirichlet closures are sampled, as for TRBDF2; the per-column proposals carry
     over from call to call.  The prescribed ϑ_l and θ_i are refreshed once per saveat chunk and held through it, as for
-    HeatImplicitEuler.  No forcing: boundary-value series are not provided for heat-only models."""
+    HeatImplicitEuler.  No forcing: under a BoundarySeries use HeatSeriesTRBDF2."""
 
     def __init__(self, abstol_e=0.0, reltol=0.0):
         self.abstol_e = abstol_e
@@ -1281,13 +1285,46 @@ class HeatAdaptiveTRBDF2:
 class LayeredHeatAdaptiveTRBDF2(HeatAdaptiveTRBDF2):
     """HeatAdaptiveTRBDF2 for a heat-only model with soil_classes (lh_integrate_layered_heat_trbdf2): every cell takes
     ρc_s and κ from its own class.  Tolerances, the Simulation's dt and the sampling of Dirichlet closures as
-    HeatAdaptiveTRBDF2.  No forcing."""
+    HeatAdaptiveTRBDF2.  No forcing: under a BoundarySeries use LayeredHeatSeriesTRBDF2."""
 
     def check_scope(self, model):
         _check_heat_trbdf2_scope(model, type(self).__name__, layered=True)
 
     def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
         return integrate_layered_heat_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol_e, self.reltol, dt_cols)
+
+
+def _series_forcing(name, forcing):
+    """The required BoundarySeries of a series marker"""
+    if not isinstance(forcing, BoundarySeries):
+        raise TypeError(f"{name}: forcing must be a BoundarySeries")
+    return forcing
+
+
+class HeatSeriesTRBDF2(HeatAdaptiveTRBDF2):
+    """HeatAdaptiveTRBDF2 under a BoundarySeries (lh_integrate_heat_series): every advance is ONE library call, bitwise
+    the chain of integrate_heat_trbdf2 calls over the sub-intervals between the series' knots, every column with its
+    own boundary values.  forcing: the BoundarySeries (required); its values replace the model's on its
+    (face, component)s, and Dirichlet closures are not sampled.  Tolerances, scope and the refresh of the prescribed
+    profiles (once per saveat chunk) as HeatAdaptiveTRBDF2."""
+
+    def __init__(self, forcing, abstol_e=0.0, reltol=0.0):
+        super().__init__(abstol_e, reltol)
+        self.forcing = _series_forcing(type(self).__name__, forcing)
+
+    def integrate_forcing(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        return integrate_heat_series(model, Y, Ya, self.forcing, t0, t1, dt, self.abstol_e, self.reltol, dt_cols)
+
+
+class LayeredHeatSeriesTRBDF2(LayeredHeatAdaptiveTRBDF2):
+    """LayeredHeatAdaptiveTRBDF2 under a BoundarySeries (lh_integrate_heat_series on a model with soil_classes): as
+    HeatSeriesTRBDF2, the chain being that of integrate_layered_heat_trbdf2 calls."""
+
+    def __init__(self, forcing, abstol_e=0.0, reltol=0.0):
+        super().__init__(abstol_e, reltol)
+        self.forcing = _series_forcing(type(self).__name__, forcing)
+
+    integrate_forcing = HeatSeriesTRBDF2.integrate_forcing   # (lh_integrate_heat_series picks the kernel by the map)
 
 
 def _check_heat_trbdf2_scope(model, name, layered=False):
@@ -1382,12 +1419,15 @@ class CoupledAdaptiveTRBDF2:
     def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
         return integrate_coupled_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, dt_cols)
 
+    def integrate_forcing(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        return integrate_series(model, Y, Ya, self.forcing, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, True, dt_cols)
+
 
 class LayeredCoupledAdaptiveTRBDF2(CoupledAdaptiveTRBDF2):
     """CoupledAdaptiveTRBDF2 for a coupled model with soil_classes (lh_integrate_layered_coupled_trbdf2):
     LayeredCoupledTRBDF2's stages with every cell's own class under the same per-column controller and error norm over
     both components.  Tolerances, the Simulation's dt and the sampling of Dirichlet closures as CoupledAdaptiveTRBDF2.
-    No forcing: boundary-value series are not provided for layered coupled models."""
+    No forcing: under a BoundarySeries use LayeredCoupledSeriesTRBDF2."""
 
     def __init__(self, abstol=None, abstol_e=None, reltol=None):
         super().__init__(abstol, abstol_e, reltol)
@@ -1397,6 +1437,24 @@ class LayeredCoupledAdaptiveTRBDF2(CoupledAdaptiveTRBDF2):
 
     def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
         return integrate_layered_coupled_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, dt_cols)
+
+
+class LayeredCoupledSeriesTRBDF2(LayeredCoupledAdaptiveTRBDF2):
+    """LayeredCoupledAdaptiveTRBDF2 under a BoundarySeries (lh_integrate_layered_coupled_series): every advance is ONE
+    library call, bitwise the chain of integrate_layered_coupled_trbdf2 calls over the sub-intervals between the series'
+    knots.  forcing: the BoundarySeries (required), as HeatSeriesTRBDF2's.  Tolerances and scope as
+    LayeredCoupledAdaptiveTRBDF2.  check_scope is the parent's, so a model without soil_classes is pointed to
+    lh_integrate_coupled_trbdf2 when the Simulation is built; under a forcing the call that serves such a model is
+    integrate_series (CoupledAdaptiveTRBDF2(forcing=...)), which is what integrate_layered_coupled_series and the library
+    name."""
+
+    def __init__(self, forcing, abstol=None, abstol_e=None, reltol=None):
+        super().__init__(abstol, abstol_e, reltol)
+        self.forcing = _series_forcing(type(self).__name__, forcing)
+
+    def integrate_forcing(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        return integrate_layered_coupled_series(model, Y, Ya, self.forcing, t0, t1, dt, self.abstol, self.abstol_e,
+                                                self.reltol, dt_cols)
 
 
 def _check_coupled_implicit_scope(model, name="CoupledImplicitEuler", layered=False, scalar="lh_step_coupled_implicit"):
@@ -1826,10 +1884,56 @@ def integrate_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySer
     return _trbdf2_stats(be)
 
 
+def integrate_heat_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySeries, t0: float, t1: float, dt: float,
+                          abstol_e=None, reltol=None, dt_cols=None):
+    """Build extension: TR-BDF2 of a heat-only model's `Y` from t0 to t1 under a BoundarySeries in ONE library call
+    (lh_integrate_heat_series): bitwise the chain of integrate_heat_trbdf2 or, for a model with soil_classes,
+    integrate_layered_heat_trbdf2 calls over the sub-intervals between the series' knots, every column with its own
+    boundary values and walking its own sub-intervals.  A (face, component) without a series keeps the model's boundary
+    value of t0.  Tolerances and `dt_cols` as those calls'; the prescribed ϑ_l and θ_i are those `Ya` holds, read anew
+    in every sub-interval.  Returns lh_trbdf2_stats of the whole call as a dict."""
+    if not isinstance(series, BoundarySeries):
+        raise TypeError("integrate_heat_series: series must be a BoundarySeries")
+    series._check_span(t0, t1)
+    layered = getattr(model, "soil_classes", None) is not None
+    _check_heat_trbdf2_scope(model, "LayeredHeatSeriesTRBDF2" if layered else "HeatSeriesTRBDF2", layered=layered)
+    be = model._backend()
+    ya = _handle(Ya)
+    be.set_bcs(model, t0)
+    h = series._device(model)
+    ptr = _dt_cols_pointer(model, dt_cols)
+    abstol_e = 0.0 if abstol_e is None else float(abstol_e)   # (0: the library's own default, each on its own)
+    reltol = 0.0 if reltol is None else float(reltol)
+    F.check(F.lib().lh_integrate_heat_series(be.ctx, Y.handle, ya, h, float(t0), float(t1), float(dt), abstol_e, reltol, 0,
+                                             ptr), be.ctx)
+    return _trbdf2_stats(be)
+
+
+def integrate_layered_coupled_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySeries, t0: float, t1: float,
+                                     dt: float, abstol=None, abstol_e=None, reltol=None, dt_cols=None):
+    """Build extension: integrate_series for a coupled model with soil_classes (lh_integrate_layered_coupled_series):
+    bitwise the chain of integrate_layered_coupled_trbdf2 calls over the sub-intervals between the series' knots.
+    Arguments and the result as integrate_series' (no `adaptive`)."""
+    if not isinstance(series, BoundarySeries):
+        raise TypeError("integrate_layered_coupled_series: series must be a BoundarySeries")
+    series._check_span(t0, t1)
+    _check_coupled_implicit_scope(model, "LayeredCoupledSeriesTRBDF2", layered=True, scalar="lh_integrate_series")
+    be = model._backend()
+    ya = _handle(Ya)
+    be.set_bcs(model, t0)
+    h = series._device(model)
+    ptr = _dt_cols_pointer(model, dt_cols)
+    abstol, reltol = _trbdf2_tolerances(abstol, reltol)
+    abstol_e = 0.0 if abstol_e is None else float(abstol_e)
+    F.check(F.lib().lh_integrate_layered_coupled_series(be.ctx, Y.handle, ya, h, float(t0), float(t1), float(dt), abstol,
+                                                        abstol_e, reltol, 0, ptr), be.ctx)
+    return _trbdf2_stats(be)
+
+
 def _advance_trbdf2(sim, t1):
     """The Simulation's TR-BDF2 (TRBDF2, CoupledAdaptiveTRBDF2, HeatAdaptiveTRBDF2 and their layered forms) from it.t to t1: one library call per dt interval when Dirichlet closures
     depend on time, one for the whole interval otherwise; the per-column step proposals carry over.  With the method's
-    `forcing` (a BoundarySeries): one integrate_series call for the whole interval.
+    `forcing` (a BoundarySeries): one series call for the whole interval, the method's integrate_forcing.
     Returns the time reached (t1 itself, not a sum of steps)."""
     it, m, model = sim.integrator, sim.method, sim.model
     if t1 <= it.t:
@@ -1841,8 +1945,12 @@ def _advance_trbdf2(sim, t1):
         it.trbdf2_stats = dict(accepted=0, rejected=0, newton_iterations=0, max_steps=0, failed=0, wave_steps=0,
                                unconverged=0)
     if getattr(m, "forcing", None) is not None:
-        st = integrate_series(model, it.u, it.p, m.forcing, it.t, t1, it.dt, m.abstol, getattr(m, "abstol_e", None), m.reltol,
-                              getattr(m, "adaptive", True), it._dt_cols)
+        hook = getattr(m, "integrate_forcing", None)
+        if hook is not None:
+            st = hook(model, it.u, it.p, it.t, t1, it.dt, it._dt_cols)
+        else:   # (a method object that has `forcing` and the tolerances only: integrate_series, as before the hook)
+            st = integrate_series(model, it.u, it.p, m.forcing, it.t, t1, it.dt, m.abstol, getattr(m, "abstol_e", None), m.reltol,
+                                  getattr(m, "adaptive", True), it._dt_cols)
         for k, v in st.items():
             it.trbdf2_stats[k] += v
         it.t = t1
