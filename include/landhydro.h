@@ -811,6 +811,37 @@ int lh_integrate_layered_coupled_series(lh_ctx*, lh_state* Y, const lh_state* Ya
                                         double t1, double dt, double abstol, double abstol_e, double reltol,
                                         uint32_t flags, void* dt_cols_device_ft);
 
+/* Dense output for the adaptive TR-BDF2 integrators (OrdinaryDiffEq's saveat): the
+ * integration of lh_integrate_series -- same three families (Richards, Richards with a class map, coupled
+ * without one), same arguments, defaults and flags -- with nsave snapshots of the state at save_times,
+ * interpolated inside the launch from the steps the columns accept.  series == NULL: no forcing table;
+ * the call then stands for lh_integrate_trbdf2 / lh_integrate_layered_trbdf2 / lh_integrate_coupled_trbdf2
+ * with bcv == NULL (lh_set_bc's values, per-column arrays included; one sub-interval).
+ * The integration does not see the output: Y, dt_cols, the status word and all of lh_trbdf2_stats are
+ * BITWISE those of that twin call without output; no step is clipped or restarted at a save time.
+ * save_times (host, [nsave]): finite, strictly increasing, t0 <= s_1 and s_nsave <= t1; nsave <= 65536;
+ * nsave == 0 with both arrays NULL is the twin call.  snapshots (host, [nsave]): states of this context
+ * that hold vartheta_l and, on a coupled context, rhoe_int, each distinct from Y, Ya and one another.
+ * Only those planes are written (and marked written).  Snapshot k of a column is written when the column
+ * accepts the step t -> t_new (its own doubles) with t < s_k <= t_new: with theta = (s_k - t) / h,
+ * y0 = Y_n, y1 = Y_n+1, f0 the step's f_n and f1 = (Y_n+1 - w_2) / (d h),
+ *   u = (1 - theta) y0 + theta y1 + theta (theta - 1) ((1 - 2 theta)(y1 - y0) + (theta - 1) h f0 + theta h f1),
+ * the coefficients rounded to the working type once and the combination evaluated in it, per cell.
+ * theta == 1 gives Y_n+1 bitwise; a snapshot at s_k == t0 is Y as passed.  A rejected step writes nothing.
+ * A column that fails (status bit 4) stops as in lh_integrate_series, and every snapshot it has not yet
+ * written receives its last accepted state.  A column's snapshots do not depend on the other columns.
+ * Refusals: lh_integrate_series' own, in its order and words under this call's name (a heat-only context
+ * and a coupled context with a class map are LH_EMODEL), the series' checks only with a series; behind
+ * them, all LH_EINVAL and naming the offending index: nsave < 0 or > 65536, a NULL array with nsave > 0,
+ * a save time that is not finite, not above its predecessor or outside [t0, t1], a snapshot that is
+ * NULL, not a state of this context, Y, Ya or an earlier snapshot, or that lacks a written plane.  A
+ * refused call leaves Y, every snapshot and dt_cols untouched and the statistics zeroed.  The two host
+ * arrays are copied before the call returns; it waits for its launch. */
+int lh_integrate_dense(lh_ctx*, lh_state* Y, const lh_state* Ya, const lh_bc_series* series, double t0, double t1,
+                       double dt, double abstol, double abstol_e, double reltol, uint32_t flags,
+                       void* dt_cols_device_ft, int32_t nsave, const double* save_times,
+                       lh_state* const* snapshots);
+
 /* Build-defined stable step (the reference uses a fixed user dt):
  * courant*dz^2 / max over owned faces of the face diffusivities
  * ((K_lo+K_hi)/2 * max dpsi/dvl, (kappa_lo+kappa_hi)/2 / min rho_c_s; boundary

@@ -151,6 +151,8 @@ SIGNATURES = {
     "lh_bc_series_destroy": (C.c_int, [_P, _P]),
     "lh_integrate_series": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                       C.c_double, C.c_uint32, _P]),
+    "lh_integrate_dense": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                     C.c_double, C.c_uint32, _P, C.c_int32, _DP, C.POINTER(_P)]),
     "lh_integrate_heat_series": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                            C.c_uint32, _P]),
     "lh_integrate_layered_coupled_series": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,

@@ -14,6 +14,7 @@
 #include "lh_series.hpp"
 #include "lh_series_heat.hpp"
 #include "lh_series_layered_coupled.hpp"
+#include "lh_dense.hpp"
 #include "lh_fastmath.hpp"
 #include "lh_closures.hpp"
 
@@ -3000,16 +3001,84 @@ int lh_bc_series_destroy(lh_ctx* c, lh_bc_series* s) {
     return LH_OK;
 }
 
+// ---- lh_integrate_dense's output (lh_dense.hpp): what it adds to lh_integrate_series' call
+
+#define LH_DENSE_MAX_SAVES 65536
+struct DenseCall {
+    int32_t nsave;
+    const double* times;       // host, [nsave]
+    lh_state* const* snapshots; // host, [nsave]
+};
+
+static bool state_of(const lh_ctx* c, const lh_state* s) {
+    for (const lh_state* k : c->states)
+        if (k == s) return true;
+    return false;
+}
+
+// Its checks, behind those of the call it wraps; `vars`: the planes the call writes
+static int dense_refusals(lh_ctx* c, const char* who, const DenseCall& dc, const lh_state* Y, const lh_state* Ya, double t0,
+                          double t1, uint32_t vars) {
+    if (dc.nsave < 0 || dc.nsave > LH_DENSE_MAX_SAVES)
+        return fail(c, LH_EINVAL, "%s: nsave = %d is outside [0, %d]", who, int(dc.nsave), LH_DENSE_MAX_SAVES);
+    if (dc.nsave > 0 && (!dc.times || !dc.snapshots))
+        return fail(c, LH_EINVAL, "%s: nsave = %d with a NULL %s array", who, int(dc.nsave), dc.times ? "snapshots" : "save_times");
+    for (int k = 0; k < dc.nsave; ++k) {
+        const double s = dc.times[k];
+        if (!std::isfinite(s)) return fail(c, LH_EINVAL, "%s: save time %d is not finite", who, k);
+        if (k > 0 && !(s > dc.times[k - 1]))
+            return fail(c, LH_EINVAL, "%s: save time %d = %g is not above save time %d = %g (strictly increasing)", who, k, s, k - 1,
+                        dc.times[k - 1]);
+        if (s < t0 || s > t1) return fail(c, LH_EINVAL, "%s: save time %d = %g is outside [t0, t1] = [%g, %g]", who, k, s, t0, t1);
+    }
+    for (int k = 0; k < dc.nsave; ++k) {
+        const lh_state* const sn = dc.snapshots[k];
+        if (!sn) return fail(c, LH_EINVAL, "%s: snapshot %d is NULL", who, k);
+        if (!state_of(c, sn)) return fail(c, LH_EINVAL, "%s: snapshot %d is not a state of this context", who, k);
+        if (sn == Y || sn == Ya) return fail(c, LH_EINVAL, "%s: snapshot %d is %s", who, k, sn == Y ? "Y" : "Ya");
+        for (int j = 0; j < k; ++j)
+            if (dc.snapshots[j] == sn) return fail(c, LH_EINVAL, "%s: snapshot %d is snapshot %d again", who, k, j);
+        if ((sn->mask & vars) != vars)
+            return fail(c, LH_EINVAL, "%s: snapshot %d lacks a plane the call writes (has mask 0x%x, needs 0x%x)", who, k, sn->mask, vars);
+    }
+    return LH_OK;
+}
+
+// `bytes` of host memory into a transient device buffer
+static int upload_bytes(lh_ctx* c, const void* host, size_t bytes, DeviceBuffer& buf, const char* what) {
+    if (int rc = named_status(c, hipMalloc(&buf.p, bytes), "hipMalloc(&%s, %s)", what, "nsave")) return rc;
+    hipError_t e = hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (pageable host memory)
+    return e == hipSuccess ? LH_OK : fail(c, LH_ENODEVICE, "%s upload failed: %s", what, hipGetErrorString(e));
+}
+
+// The save times and the snapshots' plane tables ([nsave] pointers per written variable) on the device, for the
+// launch's lifetime: the caller keeps the three buffers alive until launch_error(c, d_times) has waited
+static int upload_dense_tables(lh_ctx* c, const DenseCall& dc, bool coupled, DeviceBuffer& d_times, DeviceBuffer& d_y, DeviceBuffer& d_e) {
+    if (dc.nsave == 0) return LH_OK;
+    const size_t n = size_t(dc.nsave);
+    std::vector<void*> planes(n);
+    if (int rc = upload_bytes(c, dc.times, n * sizeof(double), d_times, "d_save_times")) return rc;
+    for (size_t k = 0; k < n; ++k) planes[k] = dc.snapshots[k]->plane[LH_VAR_VARTHETA_L];
+    if (int rc = upload_bytes(c, planes.data(), n * sizeof(void*), d_y, "d_snapshot_planes")) return rc;
+    if (!coupled) return LH_OK;
+    for (size_t k = 0; k < n; ++k) planes[k] = dc.snapshots[k]->plane[LH_VAR_RHOE_INT];
+    return upload_bytes(c, planes.data(), n * sizeof(void*), d_e, "d_snapshot_planes");
+}
+
 // One launch for the chain of lh_integrate_trbdf2 / lh_integrate_layered_trbdf2 / lh_integrate_coupled_trbdf2 calls
 // over the sub-intervals of [t0, t1] between the knots: the refusals, the defaults, the scratch and the launch
-// arguments are those calls' own, in their order; the series adds its checks behind them.
-int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_series* sr, double t0, double t1, double dt,
-                        double abstol, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft) {
+// arguments are those calls' own, in their order; the series adds its checks behind them.  `dc`: NULL, or the output
+// of lh_integrate_dense, whose checks come last and whose series may be NULL (one sub-interval, no table: those calls
+// with bcv = NULL).
+static int integrate_series(lh_ctx* c, const char* who, const char* range, const char* launch, lh_state* Y, const lh_state* Ya,
+                            const lh_bc_series* sr, double t0, double t1, double dt, double abstol, double abstol_e, double reltol,
+                            uint32_t flags, void* dt_cols_device_ft, const DenseCall* dc) {
     if (!c) return LH_EINVAL;
-    static const char* const who = "lh_integrate_series";
     int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
     if (rc) return rc;
-    if ((rc = series_handle_refusals(c, who, sr))) return rc;
+    const bool tabled = sr || !dc;
+    if (tabled && (rc = series_handle_refusals(c, who, sr))) return rc;
     if (c->cfg.model == LH_MODEL_HEAT)
         return fail(c, LH_EMODEL, "%s: Richards models, with or without a class map, and coupled models without one only", who);
     const bool coupled = c->cfg.model == LH_MODEL_COUPLED;
@@ -3017,12 +3086,14 @@ int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_
     rc = coupled ? trbdf2_argument_refusals(c, who, t0, t1, dt, {abstol, abstol_e, reltol}, flags, 0, nullptr)
                  : trbdf2_argument_refusals(c, who, t0, t1, dt, {abstol, reltol}, flags, LH_TRBDF2_FIXED, nullptr);
     if (rc) return rc;
-    if ((rc = series_span_refusal(c, who, sr, t0, t1))) return rc;
-    Range r_("lh:integrate_series");
+    if (tabled && (rc = series_span_refusal(c, who, sr, t0, t1))) return rc;
+    Range r_(range);
     if ((rc = implicit_refusals(c, who, Y, Ya, coupled ? LH_MODEL_COUPLED : LH_MODEL_RICHARDS, coupled ? COUPLED_MODELS : RICHARDS_MODELS,
                                 lay ? "lh_integrate_trbdf2" : nullptr)))
         return rc;
-    if ((rc = series_kind_refusals(c, who, sr))) return rc;
+    if (tabled && (rc = series_kind_refusals(c, who, sr))) return rc;
+    const uint32_t written = LH_MASK(LH_VAR_VARTHETA_L) | (coupled ? LH_MASK(LH_VAR_RHOE_INT) : 0u);
+    if (dc && (rc = dense_refusals(c, who, *dc, Y, Ya, t0, t1, written))) return rc;
     trbdf2_tolerance_defaults(abstol, reltol);
     if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
     double tol = 0; // (fixed mode: lh_step_implicit_euler's defaults)
@@ -3034,15 +3105,34 @@ int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_
     } else if ((rc = ensure_scratch(c, &c->d_tr, 6 * pl * c->esize, "c->d_tr", "6 * plane")))
         return rc;
     if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
-    if (t1 == t0) return LH_OK;
-    if ((rc = series_proposals(c, &dt_cols_device_ft))) return rc;
+    if (t1 == t0) { // (nothing to integrate; the one save time there can be is t0: Y as passed)
+        if (!dc || dc->nsave == 0) return LH_OK;
+        if ((rc = materialize(c, Y, written))) return rc;
+        for (int i = 0; i < LH_NVARS; ++i)
+            if (written >> i & 1u) {
+                LH_HIP(c, hipMemcpyAsync(dc->snapshots[0]->plane[i], Y->plane[i], pl * c->esize, hipMemcpyDeviceToDevice, c->stream));
+                mark_written(dc->snapshots[0], 1u << i);
+            }
+        return LH_OK;
+    }
+    if (tabled && (rc = series_proposals(c, &dt_cols_device_ft))) return rc;
     if ((rc = materialize(c, Y, ~0u))) return rc;
-    const SeriesArgs S = series_args(c, sr, t0, t1);
-    double bcv[8];
-    series_own_values(c, bcv);
+    SeriesArgs S{}; // (no table: one sub-interval)
+    S.nsub = 1;
+    double own[8];
+    const double* bcv = nullptr;
+    if (tabled) {
+        S = series_args(c, sr, t0, t1);
+        series_own_values(c, own);
+        bcv = own;
+    }
+    DeviceBuffer d_times, d_snap_y, d_snap_e; // (dc: read by the launch)
+    if (dc && (rc = upload_dense_tables(c, *dc, coupled, d_times, d_snap_y, d_snap_e))) return rc;
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
+        const DenseArgs<FT> D = {static_cast<const double*>(d_times.p), static_cast<FT* const*>(d_snap_y.p),
+                                 static_cast<FT* const*>(d_snap_e.p), dc ? dc->nsave : 0};
         if (coupled) {
             CoupledTrbdf2Args<FT> A;
             point_at_water<FT>(Y, A);
@@ -3050,7 +3140,8 @@ int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_
             carve_planes<FT>(c->d_cpl_ad, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp, &A.en, &A.fe, &A.eg, &A.we});
             fill_trbdf2_args<FT>(c, A, t0, t1, dt, abstol, reltol, dt_cols_device_ft, bcv);
             A.abstol_e = abstol_e;
-            launch_series_coupled_trbdf2<FT>(P, A, S, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+            if (dc) launch_dense_coupled_trbdf2<FT>(P, A, S, D, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+            else launch_series_coupled_trbdf2<FT>(P, A, S, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
         } else {
             if (lay) layered_params<FT>(c, P);
             Trbdf2Args<FT> A;
@@ -3060,12 +3151,30 @@ int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_
             A.fixed = (flags & LH_TRBDF2_FIXED) != 0;
             A.tol = FT(tol);
             A.max_iter = max_iter;
-            if (lay) launch_series_layered_trbdf2<FT>(P, layered_args<FT>(c), A, S, implicit_noice(c, Y), c->stream);
-            else launch_series_trbdf2<FT>(P, A, S, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+            if (!dc && lay) launch_series_layered_trbdf2<FT>(P, layered_args<FT>(c), A, S, implicit_noice(c, Y), c->stream);
+            else if (!dc) launch_series_trbdf2<FT>(P, A, S, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
+            else if (lay) launch_dense_layered_trbdf2<FT>(P, layered_args<FT>(c), A, S, D, implicit_noice(c, Y), c->stream);
+            else launch_dense_trbdf2<FT>(P, A, S, D, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
         }
     });
-    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | (coupled ? LH_MASK(LH_VAR_RHOE_INT) : 0u));
-    return launch_status(c, hipGetLastError(), "series TR-BDF2");
+    mark_written(Y, written);
+    for (int k = 0; dc && k < dc->nsave; ++k) mark_written(dc->snapshots[k], written);
+    return launch_status(c, launch_error(c, d_times), launch);
+}
+
+int lh_integrate_series(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_series* sr, double t0, double t1, double dt,
+                        double abstol, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft) {
+    return integrate_series(c, "lh_integrate_series", "lh:integrate_series", "series TR-BDF2", Y, Ya, sr, t0, t1, dt, abstol, abstol_e,
+                            reltol, flags, dt_cols_device_ft, nullptr);
+}
+
+// ... with output at save times, interpolated in the launch from the accepted steps (lh_dense.hpp)
+int lh_integrate_dense(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_series* sr, double t0, double t1, double dt,
+                       double abstol, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, int32_t nsave,
+                       const double* save_times, lh_state* const* snapshots) {
+    const DenseCall dc = {nsave, save_times, snapshots};
+    return integrate_series(c, "lh_integrate_dense", "lh:integrate_dense", "dense TR-BDF2", Y, Ya, sr, t0, t1, dt, abstol, abstol_e,
+                            reltol, flags, dt_cols_device_ft, &dc);
 }
 
 // One launch for the chain of lh_integrate_heat_trbdf2 or, with a class map, lh_integrate_layered_heat_trbdf2 calls

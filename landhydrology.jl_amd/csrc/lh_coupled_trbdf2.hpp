@@ -24,9 +24,9 @@
 namespace lh {
 
 // One column (lane) from t0 to t1.  nonfinite: an accepted result was not finite.
-template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF>
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, typename OUT = NoStepOutput>
 __device__ __forceinline__ void coupled_trbdf2_column(const M& mm, const DevParams<FT>& P0, const CoupledTrbdf2Args<FT>& A,
-                                                      int64_t col, Trbdf2ColStats& st, bool& nonfinite) {
+                                                      int64_t col, Trbdf2ColStats& st, bool& nonfinite, OUT output = OUT()) {
     constexpr bool vgf = VGF && M::uses_tables;
     DevParams<FT> P = P0; // (the lane's own: its boundary values are those of its own stage times)
     const ColumnSolve<FT, M, PERCOL, NOICE> S(mm, P, col);
@@ -208,6 +208,7 @@ __device__ __forceinline__ void coupled_trbdf2_column(const M& mm, const DevPara
         }
         if (accept) {
             ++st.accepted;
+            output(t, clip ? A.t1 : t + hh, hh);
             t = clip ? A.t1 : t + hh; // (assigned: the column lands on t1 exactly)
             h = (clip && fac >= 1.0) ? fmax(hh * fac, h) : hh * fac;
             // the accepted result's finiteness and, as trbdf2_column, f_n+1 = z_1 / h where a next step follows

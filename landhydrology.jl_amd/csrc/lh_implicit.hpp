@@ -363,9 +363,16 @@ __device__ __forceinline__ double trbdf2_next_step(double h, double hh, double f
     return (clip && fac >= 1.0) ? fmax(hh * fac, h) : hh * fac;
 }
 
-template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF>
+// What the column routines (here, lh_layered_implicit.hpp, lh_coupled_trbdf2.hpp) hand an accepted step t -> t_new of
+// size hh to, before f_n is overwritten: nothing, for every launch but lh_integrate_dense's (lh_dense.hpp), whose
+// functor interpolates the output that falls into the step
+struct NoStepOutput {
+    __device__ __forceinline__ void operator()(double, double, double) const {}
+};
+
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, typename OUT = NoStepOutput>
 __device__ __forceinline__ void trbdf2_column(const M& mm, DevParams<FT> P, const Trbdf2Args<FT>& A, int64_t col,
-                                              Trbdf2ColStats& st) {
+                                              Trbdf2ColStats& st, OUT output = OUT()) {
     constexpr bool vgf = VGF && M::uses_tables;
     const ColumnSolve<FT, M, PERCOL, NOICE> S(mm, P, col);
     const int n = P.nlev;
@@ -486,6 +493,7 @@ __device__ __forceinline__ void trbdf2_column(const M& mm, DevParams<FT> P, cons
         }
         if (accept) {
             ++st.accepted;
+            output(t, clip ? A.t1 : t + hh, hh);
             t = clip ? A.t1 : t + hh; // (assigned: the column lands on t1 exactly)
             if (!A.fixed) h = trbdf2_next_step(h, hh, fac, clip);
             if (t < A.t1) { // f_{n+1} = z_1 / h for the next step

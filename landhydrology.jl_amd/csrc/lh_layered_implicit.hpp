@@ -246,9 +246,10 @@ layered_implicit_euler_kernel(const DevParams<FT> P, const LayeredArgs<FT> L, co
 }
 
 // trbdf2_column (lh_implicit.hpp): the stages, the error estimate and the controller are its own, unchanged
-template <typename FT, typename M, bool NOICE, bool VGF>
+template <typename FT, typename M, bool NOICE, bool VGF, typename OUT = NoStepOutput>
 __device__ __forceinline__ void layered_trbdf2_column(const M& mm, DevParams<FT> P, const ClassView<FT>& C,
-                                                      const Trbdf2Args<FT>& A, int64_t col, Trbdf2ColStats& st) {
+                                                      const Trbdf2Args<FT>& A, int64_t col, Trbdf2ColStats& st,
+                                                      OUT output = OUT()) {
     const int n = P.nlev;
     const int64_t stride = P.stride;
     const double gam = 2.0 - 1.4142135623730951, dg = 0.5 * gam;
@@ -355,6 +356,7 @@ __device__ __forceinline__ void layered_trbdf2_column(const M& mm, DevParams<FT>
         }
         if (accept) {
             ++st.accepted;
+            output(t, clip ? A.t1 : t + hh, hh);
             t = clip ? A.t1 : t + hh; // (assigned: the column lands on t1 exactly)
             if (!A.fixed) h = trbdf2_next_step(h, hh, fac, clip);
             if (t < A.t1) { // f_{n+1} = z_1 / h for the next step

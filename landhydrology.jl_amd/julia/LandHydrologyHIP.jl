@@ -875,6 +875,36 @@ function integrate_series!(ens::ColumnEnsemble, Y::DeviceState, Ya, series::Boun
 end
 
 """
+    integrate_dense!(ens, Y, Ya, t0, t1, dt, saveat, snapshots; series = nothing, abstol = 0.0, abstol_e = 0.0,
+                     reltol = 0.0, adaptive = true, dt_cols = C_NULL) -> stats
+
+`integrate_series!` (with `series = nothing`: `integrate_trbdf2!` / `integrate_layered_trbdf2!` /
+`integrate_coupled_trbdf2!` under the boundary values of `t0`) with the state at the times `saveat` written into
+`snapshots`, one `DeviceState` of `ens` per save time (lh_integrate_dense; OrdinaryDiffEq's `saveat`).  The
+integration is bitwise that call's, whatever `saveat` holds: no step is cut at a save time, and every snapshot is
+the cubic Hermite interpolant of the accepted step that contains its time, evaluated on the device in the same
+launch.  `saveat` must increase strictly inside `[t0, t1]`; only `ϑ_l` and, on a coupled ensemble, `ρe_int` of a
+snapshot are written.  Returns the 7 counters of lh_trbdf2_stats over the whole call.
+"""
+function integrate_dense!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, t1, dt, saveat, snapshots::Vector{DeviceState};
+                          series = nothing, abstol = 0.0, abstol_e = 0.0, reltol = 0.0, adaptive = true, dt_cols = C_NULL)
+    s = convert(Vector{Float64}, saveat)
+    length(s) == length(snapshots) || throw(ArgumentError("one snapshot state per save time"))
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    sr = series === nothing ? C_NULL : series.handle
+    handles = Ptr{Cvoid}[x.handle for x in snapshots]
+    GC.@preserve snapshots check(ens.ctx, ccall((:lh_integrate_dense, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64,
+                          UInt32, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Ptr{Cvoid}}),
+                         ens.ctx, Y.handle, ya, sr, t0, t1, dt, abstol, abstol_e, reltol,
+                         adaptive ? UInt32(0) : UInt32(1), dt_cols, Int32(length(s)), s, handles))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
     integrate_heat_series!(ens, Y, Ya, series, t0, t1, dt; abstol_e = 0.0, reltol = 0.0, dt_cols = C_NULL) -> stats
 
 TR-BDF2 of a heat-only ensemble from `t0` to `t1` under a `BoundarySeries` in one call (lh_integrate_heat_series):

@@ -1884,6 +1884,53 @@ def integrate_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySer
     return _trbdf2_stats(be)
 
 
+def _check_saveat(saveat, t0, t1):
+    """integrate_dense's save times as a Float64 array: finite, strictly increasing, inside [t0, t1] (ValueError),
+    with the library's own rules and before any library call."""
+    s = np.array(saveat, dtype=np.float64)
+    if s.ndim != 1:
+        raise ValueError("integrate_dense: saveat must be a sequence of times")
+    if s.size > 65536:
+        raise ValueError("integrate_dense: at most 65536 save times")
+    for k in range(s.size):
+        if not np.isfinite(s[k]):
+            raise ValueError(f"integrate_dense: save time {k} is not finite")
+        if k > 0 and not s[k] > s[k - 1]:
+            raise ValueError(f"integrate_dense: save time {k} is not after save time {k - 1} (saveat must increase strictly)")
+        if s[k] < t0 or s[k] > t1:
+            raise ValueError(f"integrate_dense: save time {k} = {s[k]} is outside [t0, t1] = [{t0}, {t1}]")
+    return np.ascontiguousarray(s)
+
+
+def integrate_dense(model: SoilModel, Y: "FieldVector", Ya, t0: float, t1: float, dt: float, saveat, series=None,
+                    abstol=None, abstol_e=None, reltol=None, adaptive=True, dt_cols=None):
+    """Build extension: TR-BDF2 of `Y` from t0 to t1 with the state at the times `saveat` (OrdinaryDiffEq's saveat;
+    lh_integrate_dense): the integration is that of integrate_series (or, with series=None, of integrate_trbdf2 /
+    integrate_layered_trbdf2 / integrate_coupled_trbdf2 under the model's boundary values of t0), bitwise, whatever
+    `saveat` holds -- no step is cut at a save time; each snapshot is the cubic Hermite interpolant of the accepted
+    step that contains its time, evaluated on the device in the same launch.  Returns (lh_trbdf2_stats as a dict,
+    [one FieldVector like Y per save time]); only ϑ_l and, on a coupled model, ρe_int of a snapshot are written."""
+    s = _check_saveat(saveat, t0, t1)
+    if series is not None:
+        if not isinstance(series, BoundarySeries):
+            raise TypeError("integrate_dense: series must be a BoundarySeries or None")
+        series._check_span(t0, t1)
+    be = model._backend()
+    ya = _handle(Ya)
+    be.set_bcs(model, t0)
+    h = None if series is None else series._device(model)
+    ptr = _dt_cols_pointer(model, dt_cols)
+    flags = 0 if adaptive else F.LH_TRBDF2_FIXED
+    abstol, reltol = _trbdf2_tolerances(abstol, reltol)
+    abstol_e = 0.0 if abstol_e is None else float(abstol_e)
+    snaps = [Y.similar() for _ in range(s.size)]
+    handles = (C.c_void_p * max(s.size, 1))(*[sn.handle.value for sn in snaps])
+    F.check(F.lib().lh_integrate_dense(be.ctx, Y.handle, ya, h, float(t0), float(t1), float(dt), abstol, abstol_e, reltol,
+                                       flags, ptr, int(s.size), _dptr(s) if s.size else None, handles if s.size else None),
+            be.ctx)
+    return _trbdf2_stats(be), snaps
+
+
 def integrate_heat_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySeries, t0: float, t1: float, dt: float,
                           abstol_e=None, reltol=None, dt_cols=None):
     """Build extension: TR-BDF2 of a heat-only model's `Y` from t0 to t1 under a BoundarySeries in ONE library call
