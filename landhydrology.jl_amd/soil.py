@@ -1120,7 +1120,77 @@ def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, c
 
 # Each method marker states what it refuses (check_scope: NotImplementedError, as the library's LH_EMODEL)
 # and how a Simulation advances `nsteps` intervals of dt with it (advance: returns the time reached, None
-# for it.t + nsteps dt; _advance keeps the step count and the time).
+# for it.t + nsteps dt; _advance keeps the step count and the time).  A family's first marker says both; its layered
+# and series forms carry what differs: `_layered`, the library call that serves a model without soil classes, the forcing.
+
+
+@dataclass(frozen=True)
+class _Scope:
+    """What one integrator family serves, and the words of its refusals ({name}: the marker or function that refuses).
+    The library's own words and order (LH_EMODEL) are mirrored here, and GPU tests match them."""
+    energy: type
+    hydrology: type
+    pair: str                      # another model pair
+    no_classes: str                # a layered call on a model without soil classes ({scalar}: the call that serves it)
+    factors: Optional[str] = None  # conductivity factors other than NoEffect (None: not refused)
+    atmos: Optional[str] = None    # a prescribed-atmosphere top (None: not refused)
+
+
+_RICHARDS = _Scope(      # lh_step_[layered_]implicit_euler, lh_integrate_[layered_]trbdf2
+    PrescribedTemperatureModel, SoilHydrologyModel,
+    "{name} is provided for Richards models only (SoilHydrologyModel + PrescribedTemperatureModel)",
+    "{name} is provided for models with soil_classes (without them: ImplicitEuler, TRBDF2)",
+    "{name} supports the NoEffect conductivity factors only",
+    "{name} does not support a prescribed-atmosphere top")
+_HEAT_FIXED = _Scope(    # lh_step_[layered_]heat_implicit
+    SoilEnergyModel, PrescribedHydrologyModel,
+    "{name} is provided for heat-only models only (SoilEnergyModel + PrescribedHydrologyModel)",
+    "{name} is provided for models with soil_classes (without them: HeatImplicitEuler, HeatTRBDF2)")
+_HEAT_ADAPTIVE = _Scope(  # lh_integrate_[layered_]heat_trbdf2, lh_integrate_heat_series
+    SoilEnergyModel, PrescribedHydrologyModel,
+    "{name}: heat-only models (SoilEnergyModel + PrescribedHydrologyModel)",
+    "{name}: the context has no class map (lh_set_soil_class_map); lh_integrate_heat_trbdf2 steps a model without soil "
+    "classes")
+_COUPLED = _Scope(       # lh_step_[layered_]coupled_implicit, lh_integrate_[layered_]coupled_trbdf2, ..._coupled_series
+    SoilEnergyModel, SoilHydrologyModel,
+    "{name}: coupled models only (SoilEnergyModel + SoilHydrologyModel)",
+    "{name}: the context has no class map (lh_set_soil_class_map); {scalar} steps a model without soil classes",
+    "{name}: conductivity factors other than NoEffect are not supported",
+    "{name}: a prescribed-atmosphere top is not supported")
+
+
+def _check_scope(model, name, scope, layered=False, scalar=None):
+    """NotImplementedError for what the library calls of `scope` refuse with LH_EMODEL, in their order: the model
+    pair, the class map (layered: its absence), conductivity factors, an atmosphere top."""
+    if not (isinstance(model.energy_model, scope.energy) and isinstance(model.hydrology_model, scope.hydrology)):
+        raise NotImplementedError(scope.pair.format(name=name))
+    if not layered:
+        _refuse_soil_classes(model, name)
+    elif getattr(model, "soil_classes", None) is None:
+        raise NotImplementedError(scope.no_classes.format(name=name, scalar=scalar))
+    hm, bcs = model.hydrology_model, model.boundary_conditions
+    if scope.factors and not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
+        raise NotImplementedError(scope.factors.format(name=name))
+    if scope.atmos and bcs is not None and isinstance(bcs.top, PrescribedAtmosForcing):
+        raise NotImplementedError(scope.atmos.format(name=name))
+
+
+def _marker_scope(self, model):
+    """check_scope of every marker but SSPRK33: its family's refusals under the marker's own name"""
+    _check_scope(model, type(self).__name__, self._scope, self._layered, self._scalar)
+
+
+def _chunk_end(it, nsteps):
+    """The end of a chunk of nsteps intervals of dt, as the fixed-step methods reach it; tf itself at the last."""
+    last = it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
+    return it.tf if last else it.t0 + (it._nsteps_done + nsteps) * it.dt
+
+
+def _refresh_prescribed(model, Ya, t):
+    """The prescribed profiles of THIS time in a Ya the device reads; a call holds them at these values."""
+    if isinstance(Ya, FieldVector):
+        make_update_aux(model.energy_model)(Ya, t)
+        make_update_aux(model.hydrology_model)(Ya, t)
 
 
 class SSPRK33:
@@ -1138,17 +1208,17 @@ class ImplicitEuler:
     column and iteration (lh_step_implicit_euler).  Richards models without conductivity factors
     and without a prescribed atmosphere; a heat-only model steps implicitly under HeatImplicitEuler /
     HeatTRBDF2 (lh_step_heat_implicit).  tol / max_iter: None = the library's defaults."""
+    _scope, _layered, _scalar = _RICHARDS, False, None
+    check_scope = _marker_scope
 
     def __init__(self, tol=None, max_iter=None):
         self.tol = tol
         self.max_iter = max_iter
 
-    def check_scope(self, model):
-        _check_implicit_scope(model)
-
     def advance(self, sim, nsteps):
         it = sim.integrator
-        step_implicit(sim.model, it.u, it.p, it.t, it.dt, nsteps, self.tol, self.max_iter)
+        call = step_implicit_layered if self._layered else step_implicit
+        call(sim.model, it.u, it.p, it.t, it.dt, nsteps, self.tol, self.max_iter)
 
 
 class TRBDF2:
@@ -1160,6 +1230,8 @@ class TRBDF2:
     whole saveat chunk per library call.  Same scope as ImplicitEuler.
     forcing: None or a BoundarySeries; with it every advance is one integrate_series call (the series' values
     replace the model's on its (face, component)s, Dirichlet closures are not sampled)."""
+    _scope, _layered, _scalar = _RICHARDS, False, None
+    check_scope = _marker_scope
 
     def __init__(self, abstol=None, reltol=None, adaptive=True, forcing=None):
         self.abstol = abstol
@@ -1167,17 +1239,12 @@ class TRBDF2:
         self.adaptive = adaptive
         self.forcing = forcing
 
-    def check_scope(self, model):
-        _check_implicit_scope(model, "TRBDF2")
-
     def advance(self, sim, nsteps):
-        it = sim.integrator
-        # the end of a chunk of nsteps intervals of dt, as the fixed-step methods reach it; tf itself at the last
-        last = it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
-        return _advance_trbdf2(sim, it.tf if last else it.t0 + (it._nsteps_done + nsteps) * it.dt)
+        return _advance_trbdf2(sim, _chunk_end(sim.integrator, nsteps))
 
     def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
-        return integrate_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.reltol, self.adaptive, dt_cols)
+        call = integrate_layered_trbdf2 if self._layered else integrate_trbdf2
+        return call(model, Y, Ya, t0, t1, dt, self.abstol, self.reltol, self.adaptive, dt_cols)
 
     def integrate_forcing(self, model, Y, Ya, t0, t1, dt, dt_cols):
         """One library call from t0 to t1 under self.forcing: what _advance_trbdf2 makes of an advance."""
@@ -1187,24 +1254,13 @@ class TRBDF2:
 class LayeredImplicitEuler(ImplicitEuler):
     """ImplicitEuler for a Richards model with soil_classes (lh_step_layered_implicit_euler): the same Newton,
     with the Jacobian, the safeguard and the convergence test taking every cell's own class."""
-
-    def check_scope(self, model):
-        _check_implicit_scope(model, "LayeredImplicitEuler", layered=True)
-
-    def advance(self, sim, nsteps):
-        it = sim.integrator
-        step_implicit_layered(sim.model, it.u, it.p, it.t, it.dt, nsteps, self.tol, self.max_iter)
+    _layered = True
 
 
 class LayeredTRBDF2(TRBDF2):
     """TRBDF2 for a Richards model with soil_classes (lh_integrate_layered_trbdf2): the same stages, error
     estimate and per-column controller over LayeredImplicitEuler's Newton."""
-
-    def check_scope(self, model):
-        _check_implicit_scope(model, "LayeredTRBDF2", layered=True)
-
-    def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
-        return integrate_layered_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.reltol, self.adaptive, dt_cols)
+    _layered = True
 
 
 class HeatImplicitEuler:
@@ -1214,16 +1270,14 @@ class HeatImplicitEuler:
     per saveat chunk (per run without saveat); the prescribed ϑ_l and θ_i are refreshed between calls and
     held within one."""
     method = "euler"
-
-    def check_scope(self, model):
-        _check_heat_implicit_scope(model, type(self).__name__)
+    _scope, _layered, _scalar = _HEAT_FIXED, False, None
+    check_scope = _marker_scope
 
     def advance(self, sim, nsteps):
         it, model = sim.integrator, sim.model
-        if isinstance(it.p, FieldVector):   # the prescribed profiles of THIS time, held through the call
-            make_update_aux(model.energy_model)(it.p, it.t)
-            make_update_aux(model.hydrology_model)(it.p, it.t)
-        step_implicit_heat(model, it.u, it.p, it.t, it.dt, nsteps, self.method)
+        _refresh_prescribed(model, it.p, it.t)
+        call = step_implicit_layered_heat if self._layered else step_implicit_heat
+        call(model, it.u, it.p, it.t, it.dt, nsteps, self.method)
 
 
 class HeatTRBDF2(HeatImplicitEuler):
@@ -1237,16 +1291,7 @@ class LayeredHeatImplicitEuler(HeatImplicitEuler):
     """HeatImplicitEuler for a heat-only model with soil_classes (lh_step_layered_heat_implicit): every cell takes
     ρc_s and κ from its own class, the tendency stays affine in ρe_int and a step one exact tridiagonal solve.
     Calls and prescribed profiles as HeatImplicitEuler."""
-
-    def check_scope(self, model):
-        _check_heat_implicit_scope(model, type(self).__name__, layered=True)
-
-    def advance(self, sim, nsteps):
-        it, model = sim.integrator, sim.model
-        if isinstance(it.p, FieldVector):   # the prescribed profiles of THIS time, held through the call
-            make_update_aux(model.energy_model)(it.p, it.t)
-            make_update_aux(model.hydrology_model)(it.p, it.t)
-        step_implicit_layered_heat(model, it.u, it.p, it.t, it.dt, nsteps, self.method)
+    _layered = True
 
 
 class LayeredHeatTRBDF2(LayeredHeatImplicitEuler):
@@ -1261,37 +1306,28 @@ class HeatAdaptiveTRBDF2:
     initial step and the interval at which Dirichlet closures are sampled, as for TRBDF2; the per-column proposals carry
     over from call to call.  The prescribed ϑ_l and θ_i are refreshed once per saveat chunk and held through it, as for
     HeatImplicitEuler.  No forcing: under a BoundarySeries use HeatSeriesTRBDF2."""
+    _scope, _layered, _scalar = _HEAT_ADAPTIVE, False, None
+    check_scope = _marker_scope
 
     def __init__(self, abstol_e=0.0, reltol=0.0):
         self.abstol_e = abstol_e
         self.reltol = reltol
 
-    def check_scope(self, model):
-        _check_heat_trbdf2_scope(model, type(self).__name__)
-
     def advance(self, sim, nsteps):
-        it, model = sim.integrator, sim.model
-        if isinstance(it.p, FieldVector):   # the prescribed profiles of THIS time, held through the chunk
-            make_update_aux(model.energy_model)(it.p, it.t)
-            make_update_aux(model.hydrology_model)(it.p, it.t)
-        # the end of a chunk of nsteps intervals of dt, as the fixed-step methods reach it; tf itself at the last
-        last = it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
-        return _advance_trbdf2(sim, it.tf if last else it.t0 + (it._nsteps_done + nsteps) * it.dt)
+        it = sim.integrator
+        _refresh_prescribed(sim.model, it.p, it.t)   # (held through the chunk)
+        return _advance_trbdf2(sim, _chunk_end(it, nsteps))
 
     def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
-        return integrate_heat_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol_e, self.reltol, dt_cols)
+        call = integrate_layered_heat_trbdf2 if self._layered else integrate_heat_trbdf2
+        return call(model, Y, Ya, t0, t1, dt, self.abstol_e, self.reltol, dt_cols)
 
 
 class LayeredHeatAdaptiveTRBDF2(HeatAdaptiveTRBDF2):
     """HeatAdaptiveTRBDF2 for a heat-only model with soil_classes (lh_integrate_layered_heat_trbdf2): every cell takes
     ρc_s and κ from its own class.  Tolerances, the Simulation's dt and the sampling of Dirichlet closures as
     HeatAdaptiveTRBDF2.  No forcing: under a BoundarySeries use LayeredHeatSeriesTRBDF2."""
-
-    def check_scope(self, model):
-        _check_heat_trbdf2_scope(model, type(self).__name__, layered=True)
-
-    def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
-        return integrate_layered_heat_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol_e, self.reltol, dt_cols)
+    _layered = True
 
 
 def _series_forcing(name, forcing):
@@ -1327,20 +1363,6 @@ class LayeredHeatSeriesTRBDF2(LayeredHeatAdaptiveTRBDF2):
     integrate_forcing = HeatSeriesTRBDF2.integrate_forcing   # (lh_integrate_heat_series picks the kernel by the map)
 
 
-def _check_heat_trbdf2_scope(model, name, layered=False):
-    """NotImplementedError for what lh_integrate_heat_trbdf2 refuses with LH_EMODEL, in its order and the library's
-    words; layered: for what lh_integrate_layered_heat_trbdf2 refuses."""
-    if not (isinstance(model.energy_model, SoilEnergyModel) and
-            isinstance(model.hydrology_model, PrescribedHydrologyModel)):
-        raise NotImplementedError(f"{name}: heat-only models (SoilEnergyModel + PrescribedHydrologyModel)")
-    if layered:
-        if getattr(model, "soil_classes", None) is None:
-            raise NotImplementedError(f"{name}: the context has no class map (lh_set_soil_class_map); "
-                                      "lh_integrate_heat_trbdf2 steps a model without soil classes")
-    else:
-        _refuse_soil_classes(model, name)
-
-
 class CoupledImplicitEuler:
     """Backward Euler of the coupled model, SoilEnergyModel + SoilHydrologyModel without conductivity factors
     (lh_step_coupled_implicit): the water stage by ImplicitEuler's safeguarded Newton, the energy stage by one
@@ -1348,25 +1370,22 @@ class CoupledImplicitEuler:
     monolithic implicit step.  Simulation runs one call per saveat chunk (per run without saveat), Dirichlet
     closures sampled at the step times.  tol / max_iter: None = the library's defaults (ImplicitEuler's)."""
     method = "euler"
+    _scope, _layered, _scalar = _COUPLED, False, "lh_step_coupled_implicit"
+    check_scope = _marker_scope
 
     def __init__(self, tol=None, max_iter=None):
         self.tol = tol
         self.max_iter = max_iter
 
-    def check_scope(self, model):
-        _check_coupled_implicit_scope(model, type(self).__name__)
-
     def step(self, model, Y, Ya, t, dt, nsteps):
-        """The library call of one chunk (the layered markers put their own here)."""
-        return step_implicit_coupled(model, Y, Ya, t, dt, nsteps, self.method, self.tol, self.max_iter)
+        """The library call of one chunk."""
+        call = step_implicit_layered_coupled if self._layered else step_implicit_coupled
+        return call(model, Y, Ya, t, dt, nsteps, self.method, self.tol, self.max_iter)
 
     def advance(self, sim, nsteps):
         it = sim.integrator
         it.implicit_stats = self.step(sim.model, it.u, it.p, it.t, it.dt, nsteps)
-        # the end of a chunk of nsteps intervals of dt; tf itself at the last
-        if it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt)):
-            return it.tf
-        return it.t0 + (it._nsteps_done + nsteps) * it.dt
+        return _chunk_end(it, nsteps)
 
 
 class CoupledTRBDF2(CoupledImplicitEuler):
@@ -1381,12 +1400,7 @@ class LayeredCoupledImplicitEuler(CoupledImplicitEuler):
     by LayeredImplicitEuler's Newton, the energy stage by one tridiagonal solve with ρc_s, κ and the true conductivity
     of every cell from its own class -- still exactly the monolithic implicit step.  Calls and arguments as
     CoupledImplicitEuler."""
-
-    def check_scope(self, model):
-        _check_coupled_implicit_scope(model, type(self).__name__, layered=True)
-
-    def step(self, model, Y, Ya, t, dt, nsteps):
-        return step_implicit_layered_coupled(model, Y, Ya, t, dt, nsteps, self.method, self.tol, self.max_iter)
+    _layered = True
 
 
 class LayeredCoupledTRBDF2(LayeredCoupledImplicitEuler):
@@ -1400,6 +1414,8 @@ class CoupledAdaptiveTRBDF2:
     ρe_int) and reltol: None = the library's defaults (1e-6, 1e-6 ρ_l c_l, 1e-3), each on its own.  The Simulation's
     dt is the initial step and the interval at which Dirichlet closures are sampled, as for TRBDF2.  Scope as
     CoupledImplicitEuler.  forcing: None or a BoundarySeries, as TRBDF2's."""
+    _scope, _layered, _scalar = _COUPLED, False, "lh_integrate_coupled_trbdf2"
+    check_scope = _marker_scope
 
     def __init__(self, abstol=None, abstol_e=None, reltol=None, forcing=None):
         self.abstol = abstol
@@ -1407,17 +1423,12 @@ class CoupledAdaptiveTRBDF2:
         self.reltol = reltol
         self.forcing = forcing
 
-    def check_scope(self, model):
-        _check_coupled_implicit_scope(model, type(self).__name__)
-
     def advance(self, sim, nsteps):
-        it = sim.integrator
-        # the end of a chunk of nsteps intervals of dt, as the fixed-step methods reach it; tf itself at the last
-        last = it._nsteps_done + nsteps >= int(round((it.tf - it.t0) / it.dt))
-        return _advance_trbdf2(sim, it.tf if last else it.t0 + (it._nsteps_done + nsteps) * it.dt)
+        return _advance_trbdf2(sim, _chunk_end(sim.integrator, nsteps))
 
     def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
-        return integrate_coupled_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, dt_cols)
+        call = integrate_layered_coupled_trbdf2 if self._layered else integrate_coupled_trbdf2
+        return call(model, Y, Ya, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, dt_cols)
 
     def integrate_forcing(self, model, Y, Ya, t0, t1, dt, dt_cols):
         return integrate_series(model, Y, Ya, self.forcing, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, True, dt_cols)
@@ -1428,15 +1439,10 @@ class LayeredCoupledAdaptiveTRBDF2(CoupledAdaptiveTRBDF2):
     LayeredCoupledTRBDF2's stages with every cell's own class under the same per-column controller and error norm over
     both components.  Tolerances, the Simulation's dt and the sampling of Dirichlet closures as CoupledAdaptiveTRBDF2.
     No forcing: under a BoundarySeries use LayeredCoupledSeriesTRBDF2."""
+    _layered = True
 
     def __init__(self, abstol=None, abstol_e=None, reltol=None):
         super().__init__(abstol, abstol_e, reltol)
-
-    def check_scope(self, model):
-        _check_coupled_implicit_scope(model, type(self).__name__, layered=True, scalar="lh_integrate_coupled_trbdf2")
-
-    def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
-        return integrate_layered_coupled_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.abstol_e, self.reltol, dt_cols)
 
 
 class LayeredCoupledSeriesTRBDF2(LayeredCoupledAdaptiveTRBDF2):
@@ -1457,24 +1463,49 @@ class LayeredCoupledSeriesTRBDF2(LayeredCoupledAdaptiveTRBDF2):
                                                 self.reltol, dt_cols)
 
 
-def _check_coupled_implicit_scope(model, name="CoupledImplicitEuler", layered=False, scalar="lh_step_coupled_implicit"):
-    """NotImplementedError for what lh_step_coupled_implicit and lh_integrate_coupled_trbdf2 refuse with LH_EMODEL,
-    in their order; layered: for what lh_step_layered_coupled_implicit and lh_integrate_layered_coupled_trbdf2 refuse,
-    in the library's words (`scalar`: the call that serves a model without soil classes)."""
-    if not (isinstance(model.energy_model, SoilEnergyModel) and isinstance(model.hydrology_model, SoilHydrologyModel)):
-        raise NotImplementedError(f"{name}: coupled models only (SoilEnergyModel + SoilHydrologyModel)")
-    if layered:
-        if getattr(model, "soil_classes", None) is None:
-            raise NotImplementedError(f"{name}: the context has no class map (lh_set_soil_class_map); "
-                                      f"{scalar} steps a model without soil classes")
+@dataclass(frozen=True)
+class _FixedStep:
+    """What differs between the six fixed-step entry points; _step_fixed is their one body."""
+    symbol: str            # the library call
+    scope: tuple           # _check_scope's arguments after the model: the name in the refusals, the family, layered, scalar
+    flag: Optional[int]    # the flag of method "trbdf2"; None: no `method`, backward Euler with boundary values at t_{n+1}
+    newton: bool           # tol / max_iter are passed and lh_implicit_stats is returned
+
+
+_STEP_IMPLICIT = _FixedStep("lh_step_implicit_euler", ("ImplicitEuler", _RICHARDS), None, True)
+_STEP_IMPLICIT_LAYERED = _FixedStep("lh_step_layered_implicit_euler", ("LayeredImplicitEuler", _RICHARDS, True), None, True)
+_STEP_HEAT = _FixedStep("lh_step_heat_implicit", ("step_implicit_heat", _HEAT_FIXED), F.LH_HEAT_TRBDF2, False)
+_STEP_HEAT_LAYERED = _FixedStep("lh_step_layered_heat_implicit", ("step_implicit_layered_heat", _HEAT_FIXED, True),
+                                F.LH_HEAT_TRBDF2, False)
+_STEP_COUPLED = _FixedStep("lh_step_coupled_implicit", ("step_implicit_coupled", _COUPLED), F.LH_COUPLED_TRBDF2, True)
+_STEP_COUPLED_LAYERED = _FixedStep("lh_step_layered_coupled_implicit",
+                                   ("step_implicit_layered_coupled", _COUPLED, True, "lh_step_coupled_implicit"),
+                                   F.LH_COUPLED_TRBDF2, True)
+
+
+def _step_fixed(fl, model, Y, Ya, t, dt, nsteps, method=None, tol=None, max_iter=None):
+    """One fixed-step library call: the method's name, the scope, the boundary values at the step times, set_bcs, the
+    call, and the Newton statistics where the family has a Newton."""
+    if fl.flag is not None and method not in ("euler", "trbdf2"):
+        raise ValueError(f'{fl.scope[0]}: method must be "euler" or "trbdf2"')
+    _check_scope(model, *fl.scope)
+    be = model._backend()
+    L = F.lib()
+    ya = _handle(Ya)
+    if fl.flag is None:
+        times = [t + (k + 1) * dt for k in range(int(nsteps))]   # t_{n+1} of every step
     else:
-        _refuse_soil_classes(model, name)
-    hm = model.hydrology_model
-    if not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
-        raise NotImplementedError(f"{name}: conductivity factors other than NoEffect are not supported")
-    bcs = model.boundary_conditions
-    if bcs is not None and isinstance(bcs.top, PrescribedAtmosForcing):
-        raise NotImplementedError(f"{name}: a prescribed-atmosphere top is not supported")
+        times = [t + k * dt for k in range(int(nsteps) + 1)]     # the nsteps + 1 step times
+    bcv = _sampled_bcv(model, times, t)
+    be.set_bcs(model, t)
+    flag = () if fl.flag is None else (fl.flag if method == "trbdf2" else 0,)
+    newton = (float(tol or 0.0), int(max_iter or 0)) if fl.newton else ()
+    F.check(getattr(L, fl.symbol)(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps), *flag, _dptr(bcv), *newton), be.ctx)
+    if not fl.newton:
+        return None
+    mi, un = C.c_int32(), C.c_int64()
+    F.check(L.lh_implicit_stats(be.ctx, C.byref(mi), C.byref(un)), be.ctx)
+    return int(mi.value), int(un.value)
 
 
 def step_implicit_coupled(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
@@ -1484,7 +1515,7 @@ def step_implicit_coupled(model: SoilModel, Y: "FieldVector", Ya=None, t: float 
     Time-dependent Dirichlet closures of both components are sampled at the nsteps + 1 step times t + k dt
     (per-column values at `t`).  Returns (largest Newton iteration count of any water stage, number of
     column-stages that did not converge)."""
-    return _coupled_implicit_call("step_implicit_coupled", False, model, Y, Ya, t, dt, nsteps, method, tol, max_iter)
+    return _step_fixed(_STEP_COUPLED, model, Y, Ya, t, dt, nsteps, method, tol, max_iter)
 
 
 def step_implicit_layered_coupled(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
@@ -1492,47 +1523,7 @@ def step_implicit_layered_coupled(model: SoilModel, Y: "FieldVector", Ya=None, t
     """Build extension: step_implicit_coupled for a coupled model with soil_classes
     (lh_step_layered_coupled_implicit); arguments, sampling of the boundary values and the result as
     step_implicit_coupled."""
-    return _coupled_implicit_call("step_implicit_layered_coupled", True, model, Y, Ya, t, dt, nsteps, method, tol,
-                                  max_iter)
-
-
-def _coupled_implicit_call(name, layered, model, Y, Ya, t, dt, nsteps, method, tol, max_iter):
-    """step_implicit_coupled and step_implicit_layered_coupled: one library call and its Newton statistics."""
-    if method not in ("euler", "trbdf2"):
-        raise ValueError(f'{name}: method must be "euler" or "trbdf2"')
-    _check_coupled_implicit_scope(model, name, layered=layered)
-    be = model._backend()
-    L = F.lib()
-    call = L.lh_step_layered_coupled_implicit if layered else L.lh_step_coupled_implicit
-    ya = _handle(Ya)
-    bcv = _sampled_bcv(model, [t + k * dt for k in range(int(nsteps) + 1)], t)
-    be.set_bcs(model, t)
-    F.check(call(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
-                 F.LH_COUPLED_TRBDF2 if method == "trbdf2" else 0, _dptr(bcv),
-                 float(tol or 0.0), int(max_iter or 0)), be.ctx)
-    mi, un = C.c_int32(), C.c_int64()
-    F.check(L.lh_implicit_stats(be.ctx, C.byref(mi), C.byref(un)), be.ctx)
-    return int(mi.value), int(un.value)
-
-
-def _check_implicit_scope(model, name="ImplicitEuler", layered=False):
-    """NotImplementedError for what lh_step_implicit_euler and lh_integrate_trbdf2 refuse (LH_EMODEL); layered: for
-    what lh_step_layered_implicit_euler and lh_integrate_layered_trbdf2 refuse."""
-    if not (isinstance(model.energy_model, PrescribedTemperatureModel) and
-            isinstance(model.hydrology_model, SoilHydrologyModel)):
-        raise NotImplementedError(f"{name} is provided for Richards models only "
-                                  "(SoilHydrologyModel + PrescribedTemperatureModel)")
-    if layered:
-        if getattr(model, "soil_classes", None) is None:
-            raise NotImplementedError(f"{name} is provided for models with soil_classes (without them: ImplicitEuler, TRBDF2)")
-    else:
-        _refuse_soil_classes(model, name)
-    hm = model.hydrology_model
-    if not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
-        raise NotImplementedError(f"{name} supports the NoEffect conductivity factors only")
-    bcs = model.boundary_conditions
-    if bcs is not None and isinstance(bcs.top, PrescribedAtmosForcing):
-        raise NotImplementedError(f"{name} does not support a prescribed-atmosphere top")
+    return _step_fixed(_STEP_COUPLED_LAYERED, model, Y, Ya, t, dt, nsteps, method, tol, max_iter)
 
 
 def _sampled_bcv(model, times, base_t):
@@ -1555,21 +1546,6 @@ def _sampled_bcv(model, times, base_t):
     return vals
 
 
-def _check_heat_implicit_scope(model, name="HeatImplicitEuler", layered=False):
-    """NotImplementedError for what lh_step_heat_implicit refuses with LH_EMODEL; layered: for what
-    lh_step_layered_heat_implicit refuses."""
-    if not (isinstance(model.energy_model, SoilEnergyModel) and
-            isinstance(model.hydrology_model, PrescribedHydrologyModel)):
-        raise NotImplementedError(f"{name} is provided for heat-only models only "
-                                  "(SoilEnergyModel + PrescribedHydrologyModel)")
-    if layered:
-        if getattr(model, "soil_classes", None) is None:
-            raise NotImplementedError(f"{name} is provided for models with soil_classes (without them: HeatImplicitEuler, "
-                                      "HeatTRBDF2)")
-    else:
-        _refuse_soil_classes(model, name)
-
-
 def step_implicit_heat(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
                        nsteps: int = 1, method: str = "euler"):
     """Build extension: `nsteps` implicit steps of the heat-only model in one library call
@@ -1577,32 +1553,14 @@ def step_implicit_heat(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0
     stage is one exact tridiagonal solve; the matrix is factored once per call.  Time-dependent Dirichlet
     energy closures are sampled at the nsteps + 1 step times t + k dt (per-column values at `t`).  The
     prescribed ϑ_l and θ_i are those `Ya` holds: they are held at these values through the call."""
-    if method not in ("euler", "trbdf2"):
-        raise ValueError('step_implicit_heat: method must be "euler" or "trbdf2"')
-    _check_heat_implicit_scope(model, "step_implicit_heat")
-    be = model._backend()
-    ya = _handle(Ya)
-    bcv = _sampled_bcv(model, [t + k * dt for k in range(int(nsteps) + 1)], t)
-    be.set_bcs(model, t)
-    F.check(F.lib().lh_step_heat_implicit(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
-                                          F.LH_HEAT_TRBDF2 if method == "trbdf2" else 0,
-                                          _dptr(bcv)), be.ctx)
+    return _step_fixed(_STEP_HEAT, model, Y, Ya, t, dt, nsteps, method)
 
 
 def step_implicit_layered_heat(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
                                nsteps: int = 1, method: str = "euler"):
     """Build extension: step_implicit_heat for a heat-only model with soil_classes
     (lh_step_layered_heat_implicit); arguments and sampling of the boundary values as step_implicit_heat."""
-    if method not in ("euler", "trbdf2"):
-        raise ValueError('step_implicit_layered_heat: method must be "euler" or "trbdf2"')
-    _check_heat_implicit_scope(model, "step_implicit_layered_heat", layered=True)
-    be = model._backend()
-    ya = _handle(Ya)
-    bcv = _sampled_bcv(model, [t + k * dt for k in range(int(nsteps) + 1)], t)
-    be.set_bcs(model, t)
-    F.check(F.lib().lh_step_layered_heat_implicit(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
-                                                  F.LH_HEAT_TRBDF2 if method == "trbdf2" else 0,
-                                                  _dptr(bcv)), be.ctx)
+    return _step_fixed(_STEP_HEAT_LAYERED, model, Y, Ya, t, dt, nsteps, method)
 
 
 def step_implicit(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0, nsteps: int = 1,
@@ -1611,29 +1569,14 @@ def step_implicit(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, d
     Y - Yn - dt f(Y) = 0 with f exactly make_rhs's tendency.  Time-dependent Dirichlet closures are
     evaluated at t_{n+1} of every step (per-column values at `t`).  Returns
     (largest Newton iteration count of any column-step, number of column-steps that did not converge)."""
-    _check_implicit_scope(model)
-    return _backward_euler(F.lib().lh_step_implicit_euler, model, Y, Ya, t, dt, nsteps, tol, max_iter)
+    return _step_fixed(_STEP_IMPLICIT, model, Y, Ya, t, dt, nsteps, None, tol, max_iter)
 
 
 def step_implicit_layered(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0, nsteps: int = 1,
                           tol=None, max_iter=None):
     """Build extension: step_implicit for a Richards model with soil_classes (lh_step_layered_implicit_euler);
     arguments and return value as step_implicit."""
-    _check_implicit_scope(model, "LayeredImplicitEuler", layered=True)
-    return _backward_euler(F.lib().lh_step_layered_implicit_euler, model, Y, Ya, t, dt, nsteps, tol, max_iter)
-
-
-def _backward_euler(call, model, Y, Ya, t, dt, nsteps, tol, max_iter):
-    """step_implicit's and step_implicit_layered's library call and its statistics"""
-    be = model._backend()
-    ya = _handle(Ya)
-    bcv = _sampled_bcv(model, [t + (k + 1) * dt for k in range(int(nsteps))], t)   # t_{n+1} of every step
-    be.set_bcs(model, t)
-    F.check(call(be.ctx, Y.handle, ya, float(t), float(dt), int(nsteps),
-                 _dptr(bcv), float(tol or 0.0), int(max_iter or 0)), be.ctx)
-    mi, un = C.c_int32(), C.c_int64()
-    F.check(F.lib().lh_implicit_stats(be.ctx, C.byref(mi), C.byref(un)), be.ctx)
-    return int(mi.value), int(un.value)
+    return _step_fixed(_STEP_IMPLICIT_LAYERED, model, Y, Ya, t, dt, nsteps, None, tol, max_iter)
 
 
 TRBDF2_ABSTOL, TRBDF2_RELTOL = 1e-6, 1e-3   # OrdinaryDiffEq's defaults (the library's for a 0)
@@ -1646,6 +1589,78 @@ def _trbdf2_tolerances(abstol, reltol):
             TRBDF2_RELTOL if reltol is None else float(reltol))
 
 
+def _tolerance_args(convention, abstol, abstol_e, reltol):
+    """The tolerance arguments of an adaptive library call under its convention for a None: "richards" (abstol, reltol)
+    and "coupled" (abstol, abstol_e, reltol) give abstol and reltol OrdinaryDiffEq's defaults (_trbdf2_tolerances) and
+    abstol_e 0.0, for the library its 1e-6 rho_l c_l of the earth parameters; "heat" (abstol_e, reltol) gives both 0.0,
+    the library's own defaults, each on its own."""
+    if convention != "heat":
+        abstol, reltol = _trbdf2_tolerances(abstol, reltol)
+    if convention == "richards":
+        return abstol, reltol
+    abstol_e = 0.0 if abstol_e is None else float(abstol_e)
+    if convention == "coupled":
+        return abstol, abstol_e, reltol
+    return abstol_e, 0.0 if reltol is None else float(reltol)
+
+
+@dataclass(frozen=True)
+class _Adaptive:
+    """What differs between the adaptive TR-BDF2 entry points; _integrate is their one body."""
+    symbol: str                    # the library call (without "lh_": the function, in its own messages)
+    tolerances: str                # _tolerance_args' convention
+    scope: Optional[tuple] = None  # _check_scope's arguments after the model; None: the library's own refusals only
+    series: Optional[str] = None   # a BoundarySeries is "required" or "optional"; None: closures sampled at t0 and t1
+
+
+_INTEGRATE = _Adaptive("lh_integrate_trbdf2", "richards", ("TRBDF2", _RICHARDS))
+_INTEGRATE_LAYERED = _Adaptive("lh_integrate_layered_trbdf2", "richards", ("LayeredTRBDF2", _RICHARDS, True))
+_INTEGRATE_COUPLED = _Adaptive("lh_integrate_coupled_trbdf2", "coupled", ("CoupledAdaptiveTRBDF2", _COUPLED))
+_INTEGRATE_COUPLED_LAYERED = _Adaptive("lh_integrate_layered_coupled_trbdf2", "coupled",
+                                       ("LayeredCoupledAdaptiveTRBDF2", _COUPLED, True, "lh_integrate_coupled_trbdf2"))
+_INTEGRATE_HEAT = _Adaptive("lh_integrate_heat_trbdf2", "heat", ("HeatAdaptiveTRBDF2", _HEAT_ADAPTIVE))
+_INTEGRATE_HEAT_LAYERED = _Adaptive("lh_integrate_layered_heat_trbdf2", "heat", ("LayeredHeatAdaptiveTRBDF2", _HEAT_ADAPTIVE, True))
+_INTEGRATE_SERIES = _Adaptive("lh_integrate_series", "coupled", None, "required")
+_INTEGRATE_DENSE = _Adaptive("lh_integrate_dense", "coupled", None, "optional")
+# (lh_integrate_heat_series picks the kernel by the class map, and refuses in the words of the call it chains)
+_INTEGRATE_HEAT_SERIES = _Adaptive("lh_integrate_heat_series", "heat", ("HeatSeriesTRBDF2", _HEAT_ADAPTIVE), "required")
+_INTEGRATE_HEAT_SERIES_LAYERED = _Adaptive("lh_integrate_heat_series", "heat",
+                                           ("LayeredHeatSeriesTRBDF2", _HEAT_ADAPTIVE, True), "required")
+_INTEGRATE_COUPLED_SERIES_LAYERED = _Adaptive("lh_integrate_layered_coupled_series", "coupled",
+                                              ("LayeredCoupledSeriesTRBDF2", _COUPLED, True, "lh_integrate_series"), "required")
+
+
+def _integrate(fl, model, Y, Ya, t0, t1, dt, abstol=None, abstol_e=None, reltol=None, adaptive=True, dt_cols=None,
+               series=None, saves=None):
+    """One adaptive library call, in this order: the series and its span, the scope, the backend, set_bcs at t0 (after
+    the closures are sampled at t0 and t1 where there is no series), the series' handle, the per-column step buffer,
+    the tolerances, the flags, the call, lh_trbdf2_stats.  `saves`: integrate_dense's checked save times; the result
+    is then (statistics, one state like Y per save time)."""
+    if fl.series and not (isinstance(series, BoundarySeries) or (series is None and fl.series == "optional")):
+        raise TypeError(f"{fl.symbol[3:]}: series must be a BoundarySeries" + (" or None" if fl.series == "optional" else ""))
+    if series is not None:
+        series._check_span(t0, t1)
+    if fl.scope is not None:
+        _check_scope(model, *fl.scope)
+    be = model._backend()
+    ya = _handle(Ya)
+    bcv = () if fl.series else (_dptr(_sampled_bcv(model, (t0, t1), t0)),)
+    be.set_bcs(model, t0)
+    h = () if not fl.series else (None if series is None else series._device(model),)
+    ptr = _dt_cols_pointer(model, dt_cols)
+    tolerances = _tolerance_args(fl.tolerances, abstol, abstol_e, reltol)
+    flags = 0 if adaptive else F.LH_TRBDF2_FIXED
+    dense = ()
+    if saves is not None:
+        snaps = [Y.similar() for _ in range(saves.size)]
+        handles = (C.c_void_p * max(saves.size, 1))(*[sn.handle.value for sn in snaps])
+        dense = (int(saves.size), _dptr(saves) if saves.size else None, handles if saves.size else None)
+    F.check(getattr(F.lib(), fl.symbol)(be.ctx, Y.handle, ya, *h, float(t0), float(t1), float(dt), *tolerances, flags, ptr,
+                                        *bcv, *dense), be.ctx)
+    st = _trbdf2_stats(be)
+    return st if saves is None else (st, snaps)
+
+
 def integrate_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
                      dt: float = 1.0, abstol=None, reltol=None, adaptive=True, dt_cols=None):
     """Build extension: TR-BDF2 of `Y` from t0 to t1 in one library call (lh_integrate_trbdf2), every
@@ -1655,29 +1670,14 @@ def integrate_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.
     device tensor of ncols steps in the model's FT, read as the initial steps (<= 0: dt) and overwritten by
     the next proposals (0: failed column); with adaptive=False it is not read and receives dt.
     Returns lh_trbdf2_stats as a dict."""
-    _check_implicit_scope(model, "TRBDF2")
-    return _trbdf2(F.lib().lh_integrate_trbdf2, model, Y, Ya, t0, t1, dt, abstol, reltol, adaptive, dt_cols)
+    return _integrate(_INTEGRATE, model, Y, Ya, t0, t1, dt, abstol, None, reltol, adaptive, dt_cols)
 
 
 def integrate_layered_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
                              dt: float = 1.0, abstol=None, reltol=None, adaptive=True, dt_cols=None):
     """Build extension: integrate_trbdf2 for a Richards model with soil_classes (lh_integrate_layered_trbdf2);
     arguments and return value as integrate_trbdf2."""
-    _check_implicit_scope(model, "LayeredTRBDF2", layered=True)
-    return _trbdf2(F.lib().lh_integrate_layered_trbdf2, model, Y, Ya, t0, t1, dt, abstol, reltol, adaptive, dt_cols)
-
-
-def _trbdf2(call, model, Y, Ya, t0, t1, dt, abstol, reltol, adaptive, dt_cols):
-    """integrate_trbdf2's and integrate_layered_trbdf2's library call and its statistics"""
-    be = model._backend()
-    ya = _handle(Ya)
-    bcv = _sampled_bcv(model, (t0, t1), t0)
-    be.set_bcs(model, t0)
-    ptr = _dt_cols_pointer(model, dt_cols)
-    flags = 0 if adaptive else F.LH_TRBDF2_FIXED
-    abstol, reltol = _trbdf2_tolerances(abstol, reltol)
-    F.check(call(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol, reltol, flags, ptr, _dptr(bcv)), be.ctx)
-    return _trbdf2_stats(be)
+    return _integrate(_INTEGRATE_LAYERED, model, Y, Ya, t0, t1, dt, abstol, None, reltol, adaptive, dt_cols)
 
 
 def _dt_cols_pointer(model, dt_cols):
@@ -1709,8 +1709,7 @@ def integrate_coupled_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: fl
     interpolated linearly in between (per-column values at t0).  abstol / abstol_e / reltol: None = 1e-6 /
     1e-6 ρ_l c_l / 1e-3, each on its own.  `dt_cols` as integrate_trbdf2.  Returns lh_trbdf2_stats as a dict
     (unconverged stays 0)."""
-    _check_coupled_implicit_scope(model, "CoupledAdaptiveTRBDF2")
-    return _coupled_trbdf2(F.lib().lh_integrate_coupled_trbdf2, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, dt_cols)
+    return _integrate(_INTEGRATE_COUPLED, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, True, dt_cols)
 
 
 def integrate_layered_coupled_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
@@ -1718,22 +1717,7 @@ def integrate_layered_coupled_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None
     """Build extension: integrate_coupled_trbdf2 for a coupled model with soil_classes
     (lh_integrate_layered_coupled_trbdf2); arguments, sampling of the boundary values and the result as
     integrate_coupled_trbdf2."""
-    _check_coupled_implicit_scope(model, "LayeredCoupledAdaptiveTRBDF2", layered=True, scalar="lh_integrate_coupled_trbdf2")
-    return _coupled_trbdf2(F.lib().lh_integrate_layered_coupled_trbdf2, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol,
-                           dt_cols)
-
-
-def _coupled_trbdf2(call, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, dt_cols):
-    """integrate_coupled_trbdf2's and integrate_layered_coupled_trbdf2's library call and its statistics"""
-    be = model._backend()
-    ya = _handle(Ya)
-    bcv = _sampled_bcv(model, (t0, t1), t0)
-    be.set_bcs(model, t0)
-    ptr = _dt_cols_pointer(model, dt_cols)
-    abstol, reltol = _trbdf2_tolerances(abstol, reltol)
-    abstol_e = 0.0 if abstol_e is None else float(abstol_e)   # (0: the library's 1e-6 rho_l c_l of its earth parameters)
-    F.check(call(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol, abstol_e, reltol, 0, ptr, _dptr(bcv)), be.ctx)
-    return _trbdf2_stats(be)
+    return _integrate(_INTEGRATE_COUPLED_LAYERED, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, True, dt_cols)
 
 
 def integrate_heat_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
@@ -1744,8 +1728,7 @@ def integrate_heat_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float
     values at t0).  abstol_e / reltol: 0.0 (or None) = 1e-6 ρ_l c_l / 1e-3, each on its own.  `dt_cols` as
     integrate_trbdf2.  The prescribed ϑ_l and θ_i are those `Ya` holds.  Returns lh_trbdf2_stats as a dict
     (newton_iterations and unconverged stay 0)."""
-    _check_heat_trbdf2_scope(model, "HeatAdaptiveTRBDF2")
-    return _heat_trbdf2(F.lib().lh_integrate_heat_trbdf2, model, Y, Ya, t0, t1, dt, abstol_e, reltol, dt_cols)
+    return _integrate(_INTEGRATE_HEAT, model, Y, Ya, t0, t1, dt, None, abstol_e, reltol, True, dt_cols)
 
 
 def integrate_layered_heat_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
@@ -1753,21 +1736,7 @@ def integrate_layered_heat_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t
     """Build extension: integrate_heat_trbdf2 for a heat-only model with soil_classes
     (lh_integrate_layered_heat_trbdf2); arguments, sampling of the boundary values and the result as
     integrate_heat_trbdf2."""
-    _check_heat_trbdf2_scope(model, "LayeredHeatAdaptiveTRBDF2", layered=True)
-    return _heat_trbdf2(F.lib().lh_integrate_layered_heat_trbdf2, model, Y, Ya, t0, t1, dt, abstol_e, reltol, dt_cols)
-
-
-def _heat_trbdf2(call, model, Y, Ya, t0, t1, dt, abstol_e, reltol, dt_cols):
-    """integrate_heat_trbdf2's and integrate_layered_heat_trbdf2's library call and its statistics"""
-    be = model._backend()
-    ya = _handle(Ya)
-    bcv = _sampled_bcv(model, (t0, t1), t0)
-    be.set_bcs(model, t0)
-    ptr = _dt_cols_pointer(model, dt_cols)
-    abstol_e = 0.0 if abstol_e is None else float(abstol_e)   # (0: the library's own default, each on its own)
-    reltol = 0.0 if reltol is None else float(reltol)
-    F.check(call(be.ctx, Y.handle, ya, float(t0), float(t1), float(dt), abstol_e, reltol, 0, ptr, _dptr(bcv)), be.ctx)
-    return _trbdf2_stats(be)
+    return _integrate(_INTEGRATE_HEAT_LAYERED, model, Y, Ya, t0, t1, dt, None, abstol_e, reltol, True, dt_cols)
 
 
 _SERIES_FACE = {"bottom": F.LH_FACE_BOTTOM, "top": F.LH_FACE_TOP, F.LH_FACE_BOTTOM: F.LH_FACE_BOTTOM,
@@ -1868,20 +1837,7 @@ def integrate_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySer
     boundary values and walking its own sub-intervals.  A (face, component) without a series keeps the model's
     boundary value of t0.  Tolerances, `adaptive` and `dt_cols` as those calls' (abstol_e: coupled models only;
     adaptive=False: Richards models only).  Returns lh_trbdf2_stats of the whole call as a dict."""
-    if not isinstance(series, BoundarySeries):
-        raise TypeError("integrate_series: series must be a BoundarySeries")
-    series._check_span(t0, t1)
-    be = model._backend()
-    ya = _handle(Ya)
-    be.set_bcs(model, t0)
-    h = series._device(model)
-    ptr = _dt_cols_pointer(model, dt_cols)
-    flags = 0 if adaptive else F.LH_TRBDF2_FIXED
-    abstol, reltol = _trbdf2_tolerances(abstol, reltol)
-    abstol_e = 0.0 if abstol_e is None else float(abstol_e)
-    F.check(F.lib().lh_integrate_series(be.ctx, Y.handle, ya, h, float(t0), float(t1), float(dt), abstol, abstol_e, reltol,
-                                        flags, ptr), be.ctx)
-    return _trbdf2_stats(be)
+    return _integrate(_INTEGRATE_SERIES, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, adaptive, dt_cols, series)
 
 
 def _check_saveat(saveat, t0, t1):
@@ -1911,24 +1867,7 @@ def integrate_dense(model: SoilModel, Y: "FieldVector", Ya, t0: float, t1: float
     step that contains its time, evaluated on the device in the same launch.  Returns (lh_trbdf2_stats as a dict,
     [one FieldVector like Y per save time]); only ϑ_l and, on a coupled model, ρe_int of a snapshot are written."""
     s = _check_saveat(saveat, t0, t1)
-    if series is not None:
-        if not isinstance(series, BoundarySeries):
-            raise TypeError("integrate_dense: series must be a BoundarySeries or None")
-        series._check_span(t0, t1)
-    be = model._backend()
-    ya = _handle(Ya)
-    be.set_bcs(model, t0)
-    h = None if series is None else series._device(model)
-    ptr = _dt_cols_pointer(model, dt_cols)
-    flags = 0 if adaptive else F.LH_TRBDF2_FIXED
-    abstol, reltol = _trbdf2_tolerances(abstol, reltol)
-    abstol_e = 0.0 if abstol_e is None else float(abstol_e)
-    snaps = [Y.similar() for _ in range(s.size)]
-    handles = (C.c_void_p * max(s.size, 1))(*[sn.handle.value for sn in snaps])
-    F.check(F.lib().lh_integrate_dense(be.ctx, Y.handle, ya, h, float(t0), float(t1), float(dt), abstol, abstol_e, reltol,
-                                       flags, ptr, int(s.size), _dptr(s) if s.size else None, handles if s.size else None),
-            be.ctx)
-    return _trbdf2_stats(be), snaps
+    return _integrate(_INTEGRATE_DENSE, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, adaptive, dt_cols, series, s)
 
 
 def integrate_heat_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySeries, t0: float, t1: float, dt: float,
@@ -1939,21 +1878,8 @@ def integrate_heat_series(model: SoilModel, Y: "FieldVector", Ya, series: Bounda
     boundary values and walking its own sub-intervals.  A (face, component) without a series keeps the model's boundary
     value of t0.  Tolerances and `dt_cols` as those calls'; the prescribed ϑ_l and θ_i are those `Ya` holds, read anew
     in every sub-interval.  Returns lh_trbdf2_stats of the whole call as a dict."""
-    if not isinstance(series, BoundarySeries):
-        raise TypeError("integrate_heat_series: series must be a BoundarySeries")
-    series._check_span(t0, t1)
-    layered = getattr(model, "soil_classes", None) is not None
-    _check_heat_trbdf2_scope(model, "LayeredHeatSeriesTRBDF2" if layered else "HeatSeriesTRBDF2", layered=layered)
-    be = model._backend()
-    ya = _handle(Ya)
-    be.set_bcs(model, t0)
-    h = series._device(model)
-    ptr = _dt_cols_pointer(model, dt_cols)
-    abstol_e = 0.0 if abstol_e is None else float(abstol_e)   # (0: the library's own default, each on its own)
-    reltol = 0.0 if reltol is None else float(reltol)
-    F.check(F.lib().lh_integrate_heat_series(be.ctx, Y.handle, ya, h, float(t0), float(t1), float(dt), abstol_e, reltol, 0,
-                                             ptr), be.ctx)
-    return _trbdf2_stats(be)
+    fl = _INTEGRATE_HEAT_SERIES_LAYERED if getattr(model, "soil_classes", None) is not None else _INTEGRATE_HEAT_SERIES
+    return _integrate(fl, model, Y, Ya, t0, t1, dt, None, abstol_e, reltol, True, dt_cols, series)
 
 
 def integrate_layered_coupled_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySeries, t0: float, t1: float,
@@ -1961,20 +1887,8 @@ def integrate_layered_coupled_series(model: SoilModel, Y: "FieldVector", Ya, ser
     """Build extension: integrate_series for a coupled model with soil_classes (lh_integrate_layered_coupled_series):
     bitwise the chain of integrate_layered_coupled_trbdf2 calls over the sub-intervals between the series' knots.
     Arguments and the result as integrate_series' (no `adaptive`)."""
-    if not isinstance(series, BoundarySeries):
-        raise TypeError("integrate_layered_coupled_series: series must be a BoundarySeries")
-    series._check_span(t0, t1)
-    _check_coupled_implicit_scope(model, "LayeredCoupledSeriesTRBDF2", layered=True, scalar="lh_integrate_series")
-    be = model._backend()
-    ya = _handle(Ya)
-    be.set_bcs(model, t0)
-    h = series._device(model)
-    ptr = _dt_cols_pointer(model, dt_cols)
-    abstol, reltol = _trbdf2_tolerances(abstol, reltol)
-    abstol_e = 0.0 if abstol_e is None else float(abstol_e)
-    F.check(F.lib().lh_integrate_layered_coupled_series(be.ctx, Y.handle, ya, h, float(t0), float(t1), float(dt), abstol,
-                                                        abstol_e, reltol, 0, ptr), be.ctx)
-    return _trbdf2_stats(be)
+    return _integrate(_INTEGRATE_COUPLED_SERIES_LAYERED, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, True, dt_cols,
+                      series)
 
 
 def _advance_trbdf2(sim, t1):
@@ -1989,8 +1903,7 @@ def _advance_trbdf2(sim, t1):
         import torch
         ft, dev = _torch_ft_device(model)
         it._dt_cols = torch.zeros(model.domain.ncolumns, dtype=ft, device=dev)
-        it.trbdf2_stats = dict(accepted=0, rejected=0, newton_iterations=0, max_steps=0, failed=0, wave_steps=0,
-                               unconverged=0)
+        it.trbdf2_stats = dict.fromkeys(_TRBDF2_STATS, 0)
     if getattr(m, "forcing", None) is not None:
         hook = getattr(m, "integrate_forcing", None)
         if hook is not None:
@@ -2154,10 +2067,9 @@ def _advance_ssprk33(sim: Simulation, nsteps: int):
             return it.t
         if not _aux_constant_over(model, it.p, it.t, it.dt, nsteps):
             return _advance_refreshing_aux(sim, nsteps)
-    if _aux_mask(be.kind, model) and isinstance(it.p, FieldVector):
+    if _aux_mask(be.kind, model):
         # constant-in-time profiles: still the values of THIS time (a user may have edited Ya)
-        make_update_aux(model.energy_model)(it.p, it.t)
-        make_update_aux(model.hydrology_model)(it.p, it.t)
+        _refresh_prescribed(model, it.p, it.t)
     bcv = _sampled_bcv(model, _stage_times(it.t, it.dt, nsteps), it.t)
     be.set_bcs(model, it.t)
     if not getattr(it, "_placed", False) and _placement_tuning_wanted(model):
