@@ -842,6 +842,37 @@ int lh_integrate_dense(lh_ctx*, lh_state* Y, const lh_state* Ya, const lh_bc_ser
                        void* dt_cols_device_ft, int32_t nsave, const double* save_times,
                        lh_state* const* snapshots);
 
+/* lh_integrate_dense's semantics for the heat-only model: the integration of
+ * lh_integrate_heat_series -- without or with a class map, same arguments and defaults, flags must be 0 --
+ * with nsave snapshots of rhoe_int at save_times, interpolated inside the launch from the steps the
+ * columns accept.  series == NULL: no forcing table; the call then stands for lh_integrate_heat_trbdf2 /
+ * lh_integrate_layered_heat_trbdf2 with bcv == NULL (one sub-interval).  The integration does not see
+ * the output: Y, dt_cols, the status word and all of lh_trbdf2_stats are BITWISE those of that twin call;
+ * nsave == 0 with both arrays NULL is the twin call and asynchronous as it.  save_times, the interpolant
+ * (f1 = (Y_n+1 - w_2) / (d h) also on the last step of a sub-interval), theta == 1, s_k == t0, rejected
+ * steps, a failing column and the independence of the columns are lh_integrate_dense's.  snapshots: states
+ * of this context that hold rhoe_int (vartheta_l is not required), each distinct from Y, Ya and one
+ * another; only rhoe_int of a snapshot is written (and marked written).
+ * Refusals: lh_integrate_heat_series' own, in its order and words under this call's name (any model but
+ * LH_MODEL_HEAT is LH_EMODEL), the series' checks only with a series; behind them lh_integrate_dense's
+ * checks of the output (LH_EINVAL, naming the offending index).  A refused call leaves Y, every snapshot
+ * and dt_cols untouched and the statistics zeroed.  With nsave > 0 the two host arrays are copied before
+ * the call returns and it waits for its launch. */
+int lh_integrate_heat_dense(lh_ctx*, lh_state* Y, const lh_state* Ya, const lh_bc_series* series, double t0, double t1,
+                            double dt, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft,
+                            int32_t nsave, const double* save_times, lh_state* const* snapshots);
+
+/* ... and for a coupled context with a class map and its thermal supplement: the
+ * integration of lh_integrate_layered_coupled_series (series == NULL: of lh_integrate_layered_coupled_trbdf2
+ * with bcv == NULL) with snapshots of vartheta_l and rhoe_int, both required of a snapshot, both written and
+ * marked written.  flags must be 0.  Everything else is lh_integrate_heat_dense's, with
+ * lh_integrate_layered_coupled_series' refusals in front (a coupled context without a class map is
+ * pointed to lh_integrate_dense). */
+int lh_integrate_layered_coupled_dense(lh_ctx*, lh_state* Y, const lh_state* Ya, const lh_bc_series* series, double t0,
+                                       double t1, double dt, double abstol, double abstol_e, double reltol,
+                                       uint32_t flags, void* dt_cols_device_ft, int32_t nsave,
+                                       const double* save_times, lh_state* const* snapshots);
+
 /* Build-defined stable step (the reference uses a fixed user dt):
  * courant*dz^2 / max over owned faces of the face diffusivities
  * ((K_lo+K_hi)/2 * max dpsi/dvl, (kappa_lo+kappa_hi)/2 / min rho_c_s; boundary

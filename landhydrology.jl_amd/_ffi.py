@@ -157,6 +157,11 @@ SIGNATURES = {
                                            C.c_uint32, _P]),
     "lh_integrate_layered_coupled_series": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
                                                       C.c_double, C.c_double, C.c_uint32, _P]),
+    "lh_integrate_heat_dense": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          C.c_uint32, _P, C.c_int32, _DP, C.POINTER(_P)]),
+    "lh_integrate_layered_coupled_dense": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                     C.c_double, C.c_double, C.c_uint32, _P, C.c_int32, _DP,
+                                                     C.POINTER(_P)]),
     "lh_step_heat_implicit": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, C.c_uint32,
                                         C.POINTER(C.c_double)]),
     "lh_step_layered_heat_implicit": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, C.c_uint32,

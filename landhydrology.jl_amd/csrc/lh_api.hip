@@ -15,6 +15,8 @@
 #include "lh_series_heat.hpp"
 #include "lh_series_layered_coupled.hpp"
 #include "lh_dense.hpp"
+#include "lh_dense_heat.hpp"
+#include "lh_dense_layered_coupled.hpp"
 #include "lh_fastmath.hpp"
 #include "lh_closures.hpp"
 
@@ -2768,6 +2770,89 @@ static void series_own_values(const lh_ctx* c, double bcv[8]) {
     for (int k = 0; k < 8; ++k) bcv[k] = c->hp.bc_value[(k >> 1) & 1][k & 1];
 }
 
+// ---- the output of the dense calls (lh_dense.hpp; DESIGN sections 4.29 and 4.30): what lh_integrate_dense,
+// lh_integrate_heat_dense and lh_integrate_layered_coupled_dense add to the series call they wrap
+
+#define LH_DENSE_MAX_SAVES 65536
+struct DenseCall {
+    int32_t nsave;
+    const double* times;       // host, [nsave]
+    lh_state* const* snapshots; // host, [nsave]
+};
+
+static bool state_of(const lh_ctx* c, const lh_state* s) {
+    for (const lh_state* k : c->states)
+        if (k == s) return true;
+    return false;
+}
+
+// Its checks, behind those of the call it wraps; `vars`: the planes the call writes
+static int dense_refusals(lh_ctx* c, const char* who, const DenseCall& dc, const lh_state* Y, const lh_state* Ya, double t0,
+                          double t1, uint32_t vars) {
+    if (dc.nsave < 0 || dc.nsave > LH_DENSE_MAX_SAVES)
+        return fail(c, LH_EINVAL, "%s: nsave = %d is outside [0, %d]", who, int(dc.nsave), LH_DENSE_MAX_SAVES);
+    if (dc.nsave > 0 && (!dc.times || !dc.snapshots))
+        return fail(c, LH_EINVAL, "%s: nsave = %d with a NULL %s array", who, int(dc.nsave), dc.times ? "snapshots" : "save_times");
+    for (int k = 0; k < dc.nsave; ++k) {
+        const double s = dc.times[k];
+        if (!std::isfinite(s)) return fail(c, LH_EINVAL, "%s: save time %d is not finite", who, k);
+        if (k > 0 && !(s > dc.times[k - 1]))
+            return fail(c, LH_EINVAL, "%s: save time %d = %g is not above save time %d = %g (strictly increasing)", who, k, s, k - 1,
+                        dc.times[k - 1]);
+        if (s < t0 || s > t1) return fail(c, LH_EINVAL, "%s: save time %d = %g is outside [t0, t1] = [%g, %g]", who, k, s, t0, t1);
+    }
+    for (int k = 0; k < dc.nsave; ++k) {
+        const lh_state* const sn = dc.snapshots[k];
+        if (!sn) return fail(c, LH_EINVAL, "%s: snapshot %d is NULL", who, k);
+        if (!state_of(c, sn)) return fail(c, LH_EINVAL, "%s: snapshot %d is not a state of this context", who, k);
+        if (sn == Y || sn == Ya) return fail(c, LH_EINVAL, "%s: snapshot %d is %s", who, k, sn == Y ? "Y" : "Ya");
+        for (int j = 0; j < k; ++j)
+            if (dc.snapshots[j] == sn) return fail(c, LH_EINVAL, "%s: snapshot %d is snapshot %d again", who, k, j);
+        if ((sn->mask & vars) != vars)
+            return fail(c, LH_EINVAL, "%s: snapshot %d lacks a plane the call writes (has mask 0x%x, needs 0x%x)", who, k, sn->mask, vars);
+    }
+    return LH_OK;
+}
+
+// `bytes` of host memory into a transient device buffer
+static int upload_bytes(lh_ctx* c, const void* host, size_t bytes, DeviceBuffer& buf, const char* what) {
+    if (int rc = named_status(c, hipMalloc(&buf.p, bytes), "hipMalloc(&%s, %s)", what, "nsave")) return rc;
+    hipError_t e = hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (pageable host memory)
+    return e == hipSuccess ? LH_OK : fail(c, LH_ENODEVICE, "%s upload failed: %s", what, hipGetErrorString(e));
+}
+
+// The save times and the snapshots' plane tables ([nsave] pointers per written variable) on the device, for the
+// launch's lifetime: the caller keeps the three buffers alive until launch_error(c, d_times) has waited.  `vars`: the
+// planes the call writes -- the first of them (vartheta_l, or the heat-only call's rhoe_int) goes to d_first, rhoe_int
+// behind vartheta_l to d_e
+static int upload_dense_tables(lh_ctx* c, const DenseCall& dc, uint32_t vars, DeviceBuffer& d_times, DeviceBuffer& d_first,
+                               DeviceBuffer& d_e) {
+    if (dc.nsave == 0) return LH_OK;
+    const size_t n = size_t(dc.nsave);
+    const bool water = (vars & LH_MASK(LH_VAR_VARTHETA_L)) != 0, energy = (vars & LH_MASK(LH_VAR_RHOE_INT)) != 0;
+    std::vector<void*> planes(n);
+    if (int rc = upload_bytes(c, dc.times, n * sizeof(double), d_times, "d_save_times")) return rc;
+    for (size_t k = 0; k < n; ++k) planes[k] = dc.snapshots[k]->plane[water ? LH_VAR_VARTHETA_L : LH_VAR_RHOE_INT];
+    if (int rc = upload_bytes(c, planes.data(), n * sizeof(void*), d_first, "d_snapshot_planes")) return rc;
+    if (!(water && energy)) return LH_OK;
+    for (size_t k = 0; k < n; ++k) planes[k] = dc.snapshots[k]->plane[LH_VAR_RHOE_INT];
+    return upload_bytes(c, planes.data(), n * sizeof(void*), d_e, "d_snapshot_planes");
+}
+
+// t1 == t0: nothing to integrate; the one save time there can be is t0, Y as passed
+static int dense_at_t0(lh_ctx* c, const DenseCall& dc, lh_state* Y, uint32_t vars) {
+    if (dc.nsave == 0) return LH_OK;
+    if (int rc = materialize(c, Y, vars)) return rc;
+    const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
+    for (int i = 0; i < LH_NVARS; ++i)
+        if (vars >> i & 1u) {
+            LH_HIP(c, hipMemcpyAsync(dc.snapshots[0]->plane[i], Y->plane[i], pl * c->esize, hipMemcpyDeviceToDevice, c->stream));
+            mark_written(dc.snapshots[0], 1u << i);
+        }
+    return LH_OK;
+}
+
 // What lh_integrate_heat_series and lh_integrate_layered_coupled_series add to the call they wrap (heat_trbdf2,
 // coupled_trbdf2 below): the series as the caller passed it.  Its checks come behind the wrapped call's own
 struct SeriesCall {
@@ -2782,9 +2867,11 @@ static int series_call_refusals(lh_ctx* c, const char* who, const SeriesCall& sc
 // The adaptive coupled call exists twice as well (lh_coupled_trbdf2.hpp, lh_layered_coupled_trbdf2.hpp; DESIGN section
 // 4.26), on the same ten scratch planes and statistics block.  One body; the layered flavour is coupled_implicit_steps'.
 // `sc`: NULL, or the series of lh_integrate_layered_coupled_series (bcv is NULL then: one launch for the chain of calls).
+// `dc`: NULL, or the output of lh_integrate_layered_coupled_dense (a layered flavour; bcv is NULL), whose checks come
+// last and whose series may be NULL: one sub-interval, no table, the plain call with bcv = NULL.
 static int coupled_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
                           double abstol, double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv,
-                          const SeriesCall* sc = nullptr) {
+                          const SeriesCall* sc = nullptr, const DenseCall* dc = nullptr) {
     if (!c) return LH_EINVAL;
     const char* const who = fl.who;
     int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
@@ -2793,20 +2880,27 @@ static int coupled_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, con
     Range r_(fl.range);
     if ((rc = implicit_refusals(c, who, Y, Ya, LH_MODEL_COUPLED, COUPLED_MODELS, fl.scalar))) return rc;
     if (sc && (rc = series_call_refusals(c, who, *sc, t0, t1))) return rc;
+    const uint32_t written = LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT);
+    if (dc && (rc = dense_refusals(c, who, *dc, Y, Ya, t0, t1, written))) return rc;
     trbdf2_tolerance_defaults(abstol, reltol);
     // (the energy's own default is that of 1e-6 K in water)
     if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
     if ((rc = ensure_scratch(c, &c->d_cpl_ad, 10 * pl * c->esize, "c->d_cpl_ad", "10 * plane"))) return rc;
     if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
-    if (t1 == t0) return LH_OK;
+    if (t1 == t0) return dc ? dense_at_t0(c, *dc, Y, written) : LH_OK;
     double own[8];
+    SeriesArgs S{}; // (no table: one sub-interval)
+    S.nsub = 1;
     if (sc) {
         if ((rc = series_proposals(c, &dt_cols_device_ft))) return rc;
         series_own_values(c, own);
         bcv = own;
+        S = series_args(c, sc->sr, t0, t1);
     }
     if ((rc = materialize(c, Y, ~0u))) return rc;
+    DeviceBuffer d_times, d_snap_y, d_snap_e; // (dc: read by the launch)
+    if (dc && (rc = upload_dense_tables(c, *dc, written, d_times, d_snap_y, d_snap_e))) return rc;
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
@@ -2817,14 +2911,18 @@ static int coupled_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, con
         carve_planes<FT>(c->d_cpl_ad, pl, {&A.yn, &A.fn, &A.yg, &A.w, &A.cp, &A.dp, &A.en, &A.fe, &A.eg, &A.we});
         fill_trbdf2_args<FT>(c, A, t0, t1, dt, abstol, reltol, dt_cols_device_ft, bcv);
         A.abstol_e = abstol_e;
-        if (sc) // (a layered flavour: the series of a context without a map is lh_integrate_series')
-            launch_series_layered_coupled_trbdf2<FT>(P, layered_heat_args<FT>(c), A, series_args(c, sc->sr, t0, t1), implicit_noice(c, Y),
-                                                     c->stream);
+        if (dc) { // (a layered flavour)
+            const DenseArgs<FT> D = {static_cast<const double*>(d_times.p), static_cast<FT* const*>(d_snap_y.p),
+                                     static_cast<FT* const*>(d_snap_e.p), dc->nsave};
+            launch_dense_layered_coupled_trbdf2<FT>(P, layered_heat_args<FT>(c), A, S, D, implicit_noice(c, Y), c->stream);
+        } else if (sc) // (a layered flavour: the series of a context without a map is lh_integrate_series')
+            launch_series_layered_coupled_trbdf2<FT>(P, layered_heat_args<FT>(c), A, S, implicit_noice(c, Y), c->stream);
         else if (fl.layered()) launch_layered_coupled_trbdf2<FT>(P, layered_heat_args<FT>(c), A, implicit_noice(c, Y), c->stream);
         else launch_coupled_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
     });
-    mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L) | LH_MASK(LH_VAR_RHOE_INT));
-    return launch_status(c, hipGetLastError(), fl.launch);
+    mark_written(Y, written);
+    for (int k = 0; dc && k < dc->nsave; ++k) mark_written(dc->snapshots[k], written);
+    return launch_status(c, launch_error(c, d_times), fl.launch); // (waits only where tables were uploaded: nsave > 0)
 }
 
 int lh_integrate_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
@@ -2845,9 +2943,11 @@ int lh_integrate_layered_coupled_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* 
 // 4.27), on the same twelve scratch planes and lh_integrate_trbdf2's statistics block.  One body: lh_integrate_trbdf2's
 // argument checks, then heat_implicit_steps' refusals in its order; the layered flavour is heat_implicit_steps'.
 // `sc`: NULL, or the series of lh_integrate_heat_series (bcv is NULL then: one launch for the chain of calls).
+// `dc`: NULL, or the output of lh_integrate_heat_dense (bcv is NULL), whose checks come last and whose series may be
+// NULL: one sub-interval, no table, the plain call with bcv = NULL.  Only rhoe_int is written, also of a snapshot.
 static int heat_trbdf2(lh_ctx* c, const HeatFlavour& fl, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt,
                        double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv,
-                       const SeriesCall* sc = nullptr) {
+                       const SeriesCall* sc = nullptr, const DenseCall* dc = nullptr) {
     if (!c) return LH_EINVAL;
     const char* const who = fl.who;
     int rc = zero_stats(c, c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat");
@@ -2865,21 +2965,28 @@ static int heat_trbdf2(lh_ctx* c, const HeatFlavour& fl, lh_state* Y, const lh_s
         if ((rc = layered_check(c, who))) return rc;
     }
     if (sc && (rc = series_call_refusals(c, who, *sc, t0, t1))) return rc;
+    const uint32_t written = LH_MASK(LH_VAR_RHOE_INT);
+    if (dc && (rc = dense_refusals(c, who, *dc, Y, Ya, t0, t1, written))) return rc;
     if (!(reltol > 0)) reltol = LH_TRBDF2_RELTOL_DEFAULT;
     // (lh_integrate_coupled_trbdf2's default for the energy: that of 1e-6 K in water)
     if (!(abstol_e > 0)) abstol_e = LH_TRBDF2_ABSTOL_DEFAULT * (c->hp.earth.cp_l * c->hp.earth.rho_liq);
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
     if ((rc = ensure_scratch(c, &c->d_heat_ad, 12 * pl * c->esize, "c->d_heat_ad", "12 * plane"))) return rc;
     if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
-    if (t1 == t0) return LH_OK;
+    if (t1 == t0) return dc ? dense_at_t0(c, *dc, Y, written) : LH_OK;
     double own[8];
+    SeriesArgs S{}; // (no table: one sub-interval)
+    S.nsub = 1;
     if (sc) {
         if ((rc = series_proposals(c, &dt_cols_device_ft))) return rc;
         series_own_values(c, own);
         bcv = own;
+        S = series_args(c, sc->sr, t0, t1);
     }
     // (level-uniform variables of Ya become planes: the prologue reads each cell once)
     if ((rc = materialize(c, Y, ~0u)) || (rc = materialize(c, Ya, ~0u))) return rc;
+    DeviceBuffer d_times, d_snap_e, d_unused; // (dc: read by the launch)
+    if (dc && (rc = upload_dense_tables(c, *dc, written, d_times, d_snap_e, d_unused))) return rc;
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
@@ -2898,15 +3005,19 @@ static int heat_trbdf2(lh_ctx* c, const HeatFlavour& fl, lh_state* Y, const lh_s
         A.has_bcv = bcv != nullptr;
         for (int k = 0; k < 8; ++k) A.bcv[k] = bcv ? bcv[k] : 0.0;
         A.stats = static_cast<unsigned long long*>(c->d_tr_stats);
-        if (sc) {
-            const SeriesArgs S = series_args(c, sc->sr, t0, t1);
+        if (dc) { // (the snapshots' rhoe_int planes in the functor's one table)
+            const DenseArgs<FT> D = {static_cast<const double*>(d_times.p), static_cast<FT* const*>(d_snap_e.p), nullptr, dc->nsave};
+            if (fl.layered()) launch_dense_layered_heat_trbdf2<FT>(P, layered_heat_args<FT>(c), A, S, D, c->stream);
+            else launch_dense_heat_trbdf2<FT>(P, A, S, D, any_percol(c), c->math, c->stream);
+        } else if (sc) {
             if (fl.layered()) launch_series_layered_heat_trbdf2<FT>(P, layered_heat_args<FT>(c), A, S, c->stream);
             else launch_series_heat_trbdf2<FT>(P, A, S, any_percol(c), c->math, c->stream);
         } else if (fl.layered()) launch_layered_heat_trbdf2<FT>(P, layered_heat_args<FT>(c), A, c->stream);
         else launch_heat_trbdf2<FT>(P, A, any_percol(c), c->math, c->stream);
     });
-    mark_written(Y, LH_MASK(LH_VAR_RHOE_INT));
-    return launch_status(c, hipGetLastError(), fl.launch);
+    mark_written(Y, written);
+    for (int k = 0; dc && k < dc->nsave; ++k) mark_written(dc->snapshots[k], written);
+    return launch_status(c, launch_error(c, d_times), fl.launch); // (waits only where tables were uploaded: nsave > 0)
 }
 
 int lh_integrate_heat_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol_e,
@@ -3001,70 +3112,7 @@ int lh_bc_series_destroy(lh_ctx* c, lh_bc_series* s) {
     return LH_OK;
 }
 
-// ---- lh_integrate_dense's output (lh_dense.hpp): what it adds to lh_integrate_series' call
-
-#define LH_DENSE_MAX_SAVES 65536
-struct DenseCall {
-    int32_t nsave;
-    const double* times;       // host, [nsave]
-    lh_state* const* snapshots; // host, [nsave]
-};
-
-static bool state_of(const lh_ctx* c, const lh_state* s) {
-    for (const lh_state* k : c->states)
-        if (k == s) return true;
-    return false;
-}
-
-// Its checks, behind those of the call it wraps; `vars`: the planes the call writes
-static int dense_refusals(lh_ctx* c, const char* who, const DenseCall& dc, const lh_state* Y, const lh_state* Ya, double t0,
-                          double t1, uint32_t vars) {
-    if (dc.nsave < 0 || dc.nsave > LH_DENSE_MAX_SAVES)
-        return fail(c, LH_EINVAL, "%s: nsave = %d is outside [0, %d]", who, int(dc.nsave), LH_DENSE_MAX_SAVES);
-    if (dc.nsave > 0 && (!dc.times || !dc.snapshots))
-        return fail(c, LH_EINVAL, "%s: nsave = %d with a NULL %s array", who, int(dc.nsave), dc.times ? "snapshots" : "save_times");
-    for (int k = 0; k < dc.nsave; ++k) {
-        const double s = dc.times[k];
-        if (!std::isfinite(s)) return fail(c, LH_EINVAL, "%s: save time %d is not finite", who, k);
-        if (k > 0 && !(s > dc.times[k - 1]))
-            return fail(c, LH_EINVAL, "%s: save time %d = %g is not above save time %d = %g (strictly increasing)", who, k, s, k - 1,
-                        dc.times[k - 1]);
-        if (s < t0 || s > t1) return fail(c, LH_EINVAL, "%s: save time %d = %g is outside [t0, t1] = [%g, %g]", who, k, s, t0, t1);
-    }
-    for (int k = 0; k < dc.nsave; ++k) {
-        const lh_state* const sn = dc.snapshots[k];
-        if (!sn) return fail(c, LH_EINVAL, "%s: snapshot %d is NULL", who, k);
-        if (!state_of(c, sn)) return fail(c, LH_EINVAL, "%s: snapshot %d is not a state of this context", who, k);
-        if (sn == Y || sn == Ya) return fail(c, LH_EINVAL, "%s: snapshot %d is %s", who, k, sn == Y ? "Y" : "Ya");
-        for (int j = 0; j < k; ++j)
-            if (dc.snapshots[j] == sn) return fail(c, LH_EINVAL, "%s: snapshot %d is snapshot %d again", who, k, j);
-        if ((sn->mask & vars) != vars)
-            return fail(c, LH_EINVAL, "%s: snapshot %d lacks a plane the call writes (has mask 0x%x, needs 0x%x)", who, k, sn->mask, vars);
-    }
-    return LH_OK;
-}
-
-// `bytes` of host memory into a transient device buffer
-static int upload_bytes(lh_ctx* c, const void* host, size_t bytes, DeviceBuffer& buf, const char* what) {
-    if (int rc = named_status(c, hipMalloc(&buf.p, bytes), "hipMalloc(&%s, %s)", what, "nsave")) return rc;
-    hipError_t e = hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (pageable host memory)
-    return e == hipSuccess ? LH_OK : fail(c, LH_ENODEVICE, "%s upload failed: %s", what, hipGetErrorString(e));
-}
-
-// The save times and the snapshots' plane tables ([nsave] pointers per written variable) on the device, for the
-// launch's lifetime: the caller keeps the three buffers alive until launch_error(c, d_times) has waited
-static int upload_dense_tables(lh_ctx* c, const DenseCall& dc, bool coupled, DeviceBuffer& d_times, DeviceBuffer& d_y, DeviceBuffer& d_e) {
-    if (dc.nsave == 0) return LH_OK;
-    const size_t n = size_t(dc.nsave);
-    std::vector<void*> planes(n);
-    if (int rc = upload_bytes(c, dc.times, n * sizeof(double), d_times, "d_save_times")) return rc;
-    for (size_t k = 0; k < n; ++k) planes[k] = dc.snapshots[k]->plane[LH_VAR_VARTHETA_L];
-    if (int rc = upload_bytes(c, planes.data(), n * sizeof(void*), d_y, "d_snapshot_planes")) return rc;
-    if (!coupled) return LH_OK;
-    for (size_t k = 0; k < n; ++k) planes[k] = dc.snapshots[k]->plane[LH_VAR_RHOE_INT];
-    return upload_bytes(c, planes.data(), n * sizeof(void*), d_e, "d_snapshot_planes");
-}
+// ---- lh_integrate_series and lh_integrate_dense (lh_series.hpp, lh_dense.hpp; DESIGN sections 4.21 and 4.29)
 
 // One launch for the chain of lh_integrate_trbdf2 / lh_integrate_layered_trbdf2 / lh_integrate_coupled_trbdf2 calls
 // over the sub-intervals of [t0, t1] between the knots: the refusals, the defaults, the scratch and the launch
@@ -3105,16 +3153,7 @@ static int integrate_series(lh_ctx* c, const char* who, const char* range, const
     } else if ((rc = ensure_scratch(c, &c->d_tr, 6 * pl * c->esize, "c->d_tr", "6 * plane")))
         return rc;
     if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
-    if (t1 == t0) { // (nothing to integrate; the one save time there can be is t0: Y as passed)
-        if (!dc || dc->nsave == 0) return LH_OK;
-        if ((rc = materialize(c, Y, written))) return rc;
-        for (int i = 0; i < LH_NVARS; ++i)
-            if (written >> i & 1u) {
-                LH_HIP(c, hipMemcpyAsync(dc->snapshots[0]->plane[i], Y->plane[i], pl * c->esize, hipMemcpyDeviceToDevice, c->stream));
-                mark_written(dc->snapshots[0], 1u << i);
-            }
-        return LH_OK;
-    }
+    if (t1 == t0) return dc ? dense_at_t0(c, *dc, Y, written) : LH_OK;
     if (tabled && (rc = series_proposals(c, &dt_cols_device_ft))) return rc;
     if ((rc = materialize(c, Y, ~0u))) return rc;
     SeriesArgs S{}; // (no table: one sub-interval)
@@ -3127,7 +3166,7 @@ static int integrate_series(lh_ctx* c, const char* who, const char* range, const
         bcv = own;
     }
     DeviceBuffer d_times, d_snap_y, d_snap_e; // (dc: read by the launch)
-    if (dc && (rc = upload_dense_tables(c, *dc, coupled, d_times, d_snap_y, d_snap_e))) return rc;
+    if (dc && (rc = upload_dense_tables(c, *dc, written, d_times, d_snap_y, d_snap_e))) return rc;
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
@@ -3198,6 +3237,36 @@ int lh_integrate_layered_coupled_series(lh_ctx* c, lh_state* Y, const lh_state* 
                                        "lh:integrate_layered_coupled_series", "layered coupled series TR-BDF2"};
     const SeriesCall sc = {sr};
     return coupled_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, flags, dt_cols_device_ft, nullptr, &sc);
+}
+
+// lh_integrate_heat_series with output at save times, interpolated in the launch from the accepted steps
+// (lh_dense_heat.hpp).  Without a series: lh_integrate_heat_trbdf2 or, with a class map,
+// lh_integrate_layered_heat_trbdf2 with bcv = NULL
+int lh_integrate_heat_dense(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_series* sr, double t0, double t1, double dt,
+                            double abstol_e, double reltol, uint32_t flags, void* dt_cols_device_ft, int32_t nsave,
+                            const double* save_times, lh_state* const* snapshots) {
+    if (!c) return LH_EINVAL;
+    static const char* const who = "lh_integrate_heat_dense";
+    static const HeatFlavour scalar = {who, nullptr, "lh:integrate_heat_dense", "heat dense TR-BDF2"};
+    static const HeatFlavour lay = {who, who, "lh:integrate_heat_dense", "layered heat dense TR-BDF2"};
+    const SeriesCall sc = {sr};
+    const DenseCall dc = {nsave, save_times, snapshots};
+    return heat_trbdf2(c, layered(c) ? lay : scalar, Y, Ya, t0, t1, dt, abstol_e, reltol, flags, dt_cols_device_ft, nullptr,
+                       sr ? &sc : nullptr, &dc);
+}
+
+// ... and lh_integrate_layered_coupled_series; without a series lh_integrate_layered_coupled_trbdf2 with bcv = NULL.
+// A coupled context without a class map is lh_integrate_dense's
+int lh_integrate_layered_coupled_dense(lh_ctx* c, lh_state* Y, const lh_state* Ya, const lh_bc_series* sr, double t0, double t1,
+                                       double dt, double abstol, double abstol_e, double reltol, uint32_t flags,
+                                       void* dt_cols_device_ft, int32_t nsave, const double* save_times,
+                                       lh_state* const* snapshots) {
+    static const RichardsFlavour fl = {"lh_integrate_layered_coupled_dense", "lh_integrate_dense",
+                                       "lh:integrate_layered_coupled_dense", "layered coupled dense TR-BDF2"};
+    const SeriesCall sc = {sr};
+    const DenseCall dc = {nsave, save_times, snapshots};
+    return coupled_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, flags, dt_cols_device_ft, nullptr, sr ? &sc : nullptr,
+                          &dc);
 }
 
 int lh_stable_dt_device(lh_ctx* c, const lh_state* Y, const lh_state* Ya, double courant, void* d_out) {

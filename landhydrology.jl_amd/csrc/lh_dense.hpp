@@ -10,8 +10,11 @@
 // through the whole call, across the sub-intervals of a series; without a series there is one sub-interval and no
 // table (lh_integrate_trbdf2 / lh_integrate_layered_trbdf2 / lh_integrate_coupled_trbdf2 with bcv = NULL).
 //
-// The first part (the launch argument and the launchers' declarations) is what lh_api.hip includes; the kernels follow
-// under LH_DENSE_TU, which only lh_kernels_f64_dense.hip / lh_kernels_f32_dense.hip define (with LH_SERIES_TU).
+// The first part (the launch argument and the launchers' declarations) is what lh_api.hip includes.  The per-lane
+// pieces (HermiteCoefficients, DenseOutput, dense_walk) follow under LH_DENSE_OUTPUT_TU, which the dense translation
+// units of the other families define too (lh_dense_heat.hpp, lh_dense_layered_coupled.hpp);
+// the kernels follow under LH_DENSE_TU, which only lh_kernels_f64_dense.hip / lh_kernels_f32_dense.hip define (with
+// LH_SERIES_TU).
 #pragma once
 #include "lh_series.hpp" // SeriesArgs; with it lh_layered_implicit.hpp (LayeredArgs) and lh_device.hpp
 
@@ -40,7 +43,10 @@ void launch_dense_coupled_trbdf2(const DevParams<FT>& P, const CoupledTrbdf2Args
 
 } // namespace lh
 
-#ifdef LH_DENSE_TU
+#if defined(LH_DENSE_TU) || defined(LH_DENSE_OUTPUT_TU)
+#ifndef LH_SERIES_TU
+#error "lh_dense.hpp's per-lane pieces need lh_series.hpp's (define LH_SERIES_TU first)"
+#endif
 
 namespace lh {
 
@@ -154,6 +160,13 @@ __device__ __forceinline__ void dense_walk(const DevParams<FT>& P, const ARGS& A
     }
     if (tot.failed) out.store_state(double(INFINITY));
 }
+
+} // namespace lh
+#endif // LH_DENSE_TU || LH_DENSE_OUTPUT_TU
+
+#ifdef LH_DENSE_TU
+
+namespace lh {
 
 template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF>
 __global__ void __launch_bounds__(implicit_threads<M>())

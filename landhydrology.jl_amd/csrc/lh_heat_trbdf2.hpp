@@ -79,9 +79,10 @@ namespace lh {
 
 // One column (lane) from t0 to t1.  CELLS: cell(id, alpha, beta, kappa, rho_c_s) of one cell and face_kappa(face, id),
 // kappa of a Dirichlet energy face's state (0 for the other kinds).  nonfinite: an accepted result was not finite.
-template <typename FT, typename CELLS>
+// output: the accepted-step functor (NoStepOutput in lh_implicit.hpp; lh_dense_heat.hpp's launches pass a DenseOutput).
+template <typename FT, typename CELLS, typename OUT = NoStepOutput>
 __device__ __forceinline__ void heat_trbdf2_column(const DevParams<FT>& P0, const HeatTrbdf2Args<FT>& A, const CELLS& C,
-                                                   int64_t col, Trbdf2ColStats& st, bool& nonfinite) {
+                                                   int64_t col, Trbdf2ColStats& st, bool& nonfinite, OUT output = OUT()) {
     DevParams<FT> P = P0; // (the lane's own: its boundary values are those of its own stage times)
     const int n = P.nlev;
     const int64_t stride = P.stride;
@@ -270,6 +271,7 @@ __device__ __forceinline__ void heat_trbdf2_column(const DevParams<FT>& P0, cons
         const bool accept = trbdf2_control(sqrt(sum / n), fac);
         if (accept) {
             ++st.accepted;
+            output(t, clip ? A.t1 : t + hh, hh); // (before t moves and f_n is overwritten: w is still w2)
             t = clip ? A.t1 : t + hh; // (assigned: the column lands on t1 exactly)
             h = trbdf2_next_step(h, hh, fac, clip);
             // the accepted result's finiteness and f_n+1 = z_1 / hh where a next step follows

@@ -363,8 +363,9 @@ __device__ __forceinline__ double trbdf2_next_step(double h, double hh, double f
     return (clip && fac >= 1.0) ? fmax(hh * fac, h) : hh * fac;
 }
 
-// What the column routines (here, lh_layered_implicit.hpp, lh_coupled_trbdf2.hpp) hand an accepted step t -> t_new of
-// size hh to, before f_n is overwritten: nothing, for every launch but lh_integrate_dense's (lh_dense.hpp), whose
+// What the column routines (here, lh_layered_implicit.hpp, lh_coupled_trbdf2.hpp, lh_heat_trbdf2.hpp,
+// lh_layered_coupled_trbdf2.hpp) hand an accepted step t -> t_new of size hh to, before f_n is overwritten: nothing,
+// for every launch but those of the dense calls (lh_dense.hpp, lh_dense_heat.hpp, lh_dense_layered_coupled.hpp), whose
 // functor interpolates the output that falls into the step
 struct NoStepOutput {
     __device__ __forceinline__ void operator()(double, double, double) const {}

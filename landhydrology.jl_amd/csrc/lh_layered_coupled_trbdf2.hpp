@@ -39,11 +39,12 @@ void launch_layered_coupled_trbdf2(const DevParams<FT>& P, const LayeredHeatArgs
 namespace lh {
 
 // One column (lane) from t0 to t1: coupled_trbdf2_column with per-cell constants.  nonfinite: an accepted result
-// was not finite.
-template <typename FT, typename M, bool NOICE, bool VGF>
+// was not finite.  output: the accepted-step functor, as coupled_trbdf2_column's.
+template <typename FT, typename M, bool NOICE, bool VGF, typename OUT = NoStepOutput>
 __device__ __forceinline__ void layered_coupled_trbdf2_column(const M& mm, const DevParams<FT>& P0, const ClassView<FT>& C,
                                                               const ThermTable<FT>& H, const CoupledTrbdf2Args<FT>& A,
-                                                              int64_t col, Trbdf2ColStats& st, bool& nonfinite) {
+                                                              int64_t col, Trbdf2ColStats& st, bool& nonfinite,
+                                                              OUT output = OUT()) {
     DevParams<FT> P = P0; // (the lane's own: its boundary values are those of its own stage times)
     const int n = P.nlev;
     const int64_t stride = P.stride;
@@ -218,6 +219,7 @@ __device__ __forceinline__ void layered_coupled_trbdf2_column(const M& mm, const
         }
         if (accept) {
             ++st.accepted;
+            output(t, clip ? A.t1 : t + hh, hh); // (before t moves and f_n, f_e are overwritten)
             t = clip ? A.t1 : t + hh; // (assigned: the column lands on t1 exactly)
             h = trbdf2_next_step(h, hh, fac, clip);
             // the accepted result's finiteness and, as layered_trbdf2_column, f_n+1 = z_1 / h where a next step follows

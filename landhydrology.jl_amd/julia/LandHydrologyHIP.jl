@@ -947,6 +947,62 @@ function integrate_layered_coupled_series!(ens::ColumnEnsemble, Y::DeviceState, 
 end
 
 """
+    integrate_heat_dense!(ens, Y, Ya, t0, t1, dt, saveat, snapshots; series = nothing, abstol_e = 0.0, reltol = 0.0,
+                          dt_cols = C_NULL) -> stats
+
+`integrate_heat_series!` (with `series = nothing`: `integrate_heat_trbdf2!` or, with soil classes,
+`integrate_layered_heat_trbdf2!` under the boundary values of `t0`) with `ρe_int` at the times `saveat` written into
+`snapshots`, one `DeviceState` of `ens` per save time (lh_integrate_heat_dense).  The integration is bitwise that
+call's, whatever `saveat` holds; every snapshot is the cubic Hermite interpolant of the accepted step that contains its
+time, as `integrate_dense!`'s.  Returns the 7 counters of lh_trbdf2_stats over the whole call.
+"""
+function integrate_heat_dense!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, t1, dt, saveat, snapshots::Vector{DeviceState};
+                               series = nothing, abstol_e = 0.0, reltol = 0.0, dt_cols = C_NULL)
+    s = convert(Vector{Float64}, saveat)
+    length(s) == length(snapshots) || throw(ArgumentError("one snapshot state per save time"))
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    sr = series === nothing ? C_NULL : series.handle
+    handles = Ptr{Cvoid}[x.handle for x in snapshots]
+    GC.@preserve snapshots check(ens.ctx, ccall((:lh_integrate_heat_dense, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, UInt32,
+                          Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Ptr{Cvoid}}),
+                         ens.ctx, Y.handle, ya, sr, t0, t1, dt, abstol_e, reltol, UInt32(0), dt_cols, Int32(length(s)), s,
+                         handles))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
+    integrate_layered_coupled_dense!(ens, Y, Ya, t0, t1, dt, saveat, snapshots; series = nothing, abstol = 0.0,
+                                     abstol_e = 0.0, reltol = 0.0, dt_cols = C_NULL) -> stats
+
+`integrate_dense!` for a coupled ensemble with soil classes, their thermal supplement and a class map
+(lh_integrate_layered_coupled_dense): the integration of `integrate_layered_coupled_series!` (with
+`series = nothing`: of `integrate_layered_coupled_trbdf2!`), bitwise, with `ϑ_l` and `ρe_int` at the times `saveat`
+written into `snapshots`.  Returns the 7 counters of lh_trbdf2_stats over the whole call.
+"""
+function integrate_layered_coupled_dense!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, t1, dt, saveat,
+                                          snapshots::Vector{DeviceState}; series = nothing, abstol = 0.0, abstol_e = 0.0,
+                                          reltol = 0.0, dt_cols = C_NULL)
+    s = convert(Vector{Float64}, saveat)
+    length(s) == length(snapshots) || throw(ArgumentError("one snapshot state per save time"))
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    sr = series === nothing ? C_NULL : series.handle
+    handles = Ptr{Cvoid}[x.handle for x in snapshots]
+    GC.@preserve snapshots check(ens.ctx, ccall((:lh_integrate_layered_coupled_dense, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64,
+                          UInt32, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Ptr{Cvoid}}),
+                         ens.ctx, Y.handle, ya, sr, t0, t1, dt, abstol, abstol_e, reltol, UInt32(0), dt_cols,
+                         Int32(length(s)), s, handles))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
     tune_placement!(ens, Y, Ya, dY = nothing; max_candidates = 0, move_input = true)
 
 Let the library place the state written by `rhs!` (`dY` given) or the SSPRK33 stage state

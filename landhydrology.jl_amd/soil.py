@@ -1628,6 +1628,11 @@ _INTEGRATE_HEAT_SERIES_LAYERED = _Adaptive("lh_integrate_heat_series", "heat",
                                            ("LayeredHeatSeriesTRBDF2", _HEAT_ADAPTIVE, True), "required")
 _INTEGRATE_COUPLED_SERIES_LAYERED = _Adaptive("lh_integrate_layered_coupled_series", "coupled",
                                               ("LayeredCoupledSeriesTRBDF2", _COUPLED, True, "lh_integrate_series"), "required")
+# (the dense twins of the three above: their scope checks, the series optional)
+_INTEGRATE_HEAT_DENSE = _Adaptive("lh_integrate_heat_dense", "heat", _INTEGRATE_HEAT_SERIES.scope, "optional")
+_INTEGRATE_HEAT_DENSE_LAYERED = _Adaptive("lh_integrate_heat_dense", "heat", _INTEGRATE_HEAT_SERIES_LAYERED.scope, "optional")
+_INTEGRATE_COUPLED_DENSE_LAYERED = _Adaptive("lh_integrate_layered_coupled_dense", "coupled",
+                                             ("LayeredCoupledSeriesTRBDF2", _COUPLED, True, "lh_integrate_dense"), "optional")
 
 
 def _integrate(fl, model, Y, Ya, t0, t1, dt, abstol=None, abstol_e=None, reltol=None, adaptive=True, dt_cols=None,
@@ -1840,21 +1845,21 @@ def integrate_series(model: SoilModel, Y: "FieldVector", Ya, series: BoundarySer
     return _integrate(_INTEGRATE_SERIES, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, adaptive, dt_cols, series)
 
 
-def _check_saveat(saveat, t0, t1):
-    """integrate_dense's save times as a Float64 array: finite, strictly increasing, inside [t0, t1] (ValueError),
-    with the library's own rules and before any library call."""
+def _check_saveat(saveat, t0, t1, name="integrate_dense"):
+    """The save times of a dense call (`name`, in the messages) as a Float64 array: finite, strictly increasing, inside
+    [t0, t1] (ValueError), with the library's own rules and before any library call."""
     s = np.array(saveat, dtype=np.float64)
     if s.ndim != 1:
-        raise ValueError("integrate_dense: saveat must be a sequence of times")
+        raise ValueError(f"{name}: saveat must be a sequence of times")
     if s.size > 65536:
-        raise ValueError("integrate_dense: at most 65536 save times")
+        raise ValueError(f"{name}: at most 65536 save times")
     for k in range(s.size):
         if not np.isfinite(s[k]):
-            raise ValueError(f"integrate_dense: save time {k} is not finite")
+            raise ValueError(f"{name}: save time {k} is not finite")
         if k > 0 and not s[k] > s[k - 1]:
-            raise ValueError(f"integrate_dense: save time {k} is not after save time {k - 1} (saveat must increase strictly)")
+            raise ValueError(f"{name}: save time {k} is not after save time {k - 1} (saveat must increase strictly)")
         if s[k] < t0 or s[k] > t1:
-            raise ValueError(f"integrate_dense: save time {k} = {s[k]} is outside [t0, t1] = [{t0}, {t1}]")
+            raise ValueError(f"{name}: save time {k} = {s[k]} is outside [t0, t1] = [{t0}, {t1}]")
     return np.ascontiguousarray(s)
 
 
@@ -1889,6 +1894,29 @@ def integrate_layered_coupled_series(model: SoilModel, Y: "FieldVector", Ya, ser
     Arguments and the result as integrate_series' (no `adaptive`)."""
     return _integrate(_INTEGRATE_COUPLED_SERIES_LAYERED, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, True, dt_cols,
                       series)
+
+
+def integrate_heat_dense(model: SoilModel, Y: "FieldVector", Ya, t0: float, t1: float, dt: float, saveat, series=None,
+                         abstol_e=None, reltol=None, dt_cols=None):
+    """Build extension: integrate_dense for a heat-only model, with or without soil_classes (lh_integrate_heat_dense):
+    the integration is that of integrate_heat_series (or, with series=None, of integrate_heat_trbdf2 /
+    integrate_layered_heat_trbdf2 under the model's boundary values of t0), bitwise, whatever `saveat` holds; each
+    snapshot is the cubic Hermite interpolant of the accepted step that contains its time.  Returns (lh_trbdf2_stats as
+    a dict, [one FieldVector like Y per save time]); only ρe_int of a snapshot is written."""
+    s = _check_saveat(saveat, t0, t1, "integrate_heat_dense")
+    fl = _INTEGRATE_HEAT_DENSE_LAYERED if getattr(model, "soil_classes", None) is not None else _INTEGRATE_HEAT_DENSE
+    return _integrate(fl, model, Y, Ya, t0, t1, dt, None, abstol_e, reltol, True, dt_cols, series, s)
+
+
+def integrate_layered_coupled_dense(model: SoilModel, Y: "FieldVector", Ya, t0: float, t1: float, dt: float, saveat,
+                                    series=None, abstol=None, abstol_e=None, reltol=None, dt_cols=None):
+    """Build extension: integrate_dense for a coupled model with soil_classes (lh_integrate_layered_coupled_dense): the
+    integration is that of integrate_layered_coupled_series (or, with series=None, of integrate_layered_coupled_trbdf2
+    under the model's boundary values of t0), bitwise.  Returns (lh_trbdf2_stats as a dict, [one FieldVector like Y per
+    save time]); ϑ_l and ρe_int of a snapshot are written."""
+    s = _check_saveat(saveat, t0, t1, "integrate_layered_coupled_dense")
+    return _integrate(_INTEGRATE_COUPLED_DENSE_LAYERED, model, Y, Ya, t0, t1, dt, abstol, abstol_e, reltol, True, dt_cols,
+                      series, s)
 
 
 def _advance_trbdf2(sim, t1):
