@@ -811,6 +811,35 @@ int lh_integrate_layered_coupled_series(lh_ctx*, lh_state* Y, const lh_state* Ya
                                         double t1, double dt, double abstol, double abstol_e, double reltol,
                                         uint32_t flags, void* dt_cols_device_ft);
 
+/* lh_step_ssprk33 under a per-column boundary-value series (no counterpart in the
+ * reference): nsteps fixed-dt SSPRK33 steps from t.  Y and the status word are those of lh_step_ssprk33;
+ * the one difference is where the boundary values come from.  A (face, component) for which the series holds
+ * a table has, in every column, its value sampled from that column's own piecewise-linear table at every
+ * stage time; it reads neither lh_set_bc's value nor its per-column array (the kind stays lh_set_bc's).  A
+ * component without a series keeps its value, or its per-column array, for the whole call.
+ * Stage times, in double: t_k = t + dt * (double)k; the stages of step k are at t_k, t_k + dt, t_k + dt / 2.
+ * The value at a stage time tau is lh_integrate_series' (above): with k the largest index that has
+ * T_k <= tau, capped at nknots - 2, exactly v_k or v_k+1 on a knot, v_k + (v_k+1 - v_k) ((tau - T_k) /
+ * (T_k+1 - T_k)) in double otherwise, rounded once to the working type.  For a uniform series the call is
+ * BITWISE lh_step_ssprk33 with bc_stage_values holding those samples; a column's result depends on its own
+ * table only.  The context's boundary state is not modified.
+ * Refusals, in this order: lh_step_ssprk33's own, in its order and words under this call's name; a t that
+ * is not finite (LH_EINVAL); the series' checks as lh_integrate_series makes them (a NULL series or one of
+ * another context, LH_EINVAL; a series on a component the model does not have or whose lh_set_bc kind reads
+ * no value, LH_EMODEL); a stage time of the call outside [T_0, T_last] (LH_EINVAL, the message names the
+ * time).  nsteps == 0 does nothing after the first three.  Asynchronous.
+ * lh_step_series_engine: LH_ENGINE_COLUMN_STEPPER (ONE launch, the wave stepper samples the series itself) for
+ * a context without a class map and nlev <= 128 where lh_step_engine(ctx, nsteps, 1) answers the stepper and the
+ * ensemble is small (ncols x nlev rounded up to 64 at most 2^20) or the tuning says persist=2;
+ * LH_ENGINE_FUSED_STAGES otherwise (columns of more than 128 levels, every context with a class map,
+ * a prescribed atmosphere, persist=0, large ensembles under the default tuning): one small launch per step writes the three stages' sampled values
+ * per column, and the three fused-stage launches take them where lh_set_bc's per-column arrays go.  The
+ * answer is what lh_step_ssprk33_series does in every case; a negative LH_E* for a NULL context or
+ * nsteps < 0. */
+int lh_step_ssprk33_series(lh_ctx*, lh_state* Y, const lh_state* Ya, const lh_bc_series*, double t, double dt,
+                           int64_t nsteps);
+int lh_step_series_engine(const lh_ctx*, int64_t nsteps);
+
 /* Dense output for the adaptive TR-BDF2 integrators (OrdinaryDiffEq's saveat): the
  * integration of lh_integrate_series -- same three families (Richards, Richards with a class map, coupled
  * without one), same arguments, defaults and flags -- with nsave snapshots of the state at save_times,

@@ -18,14 +18,14 @@ from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplici
                    PrescribedAtmosForcing,
                    PrescribedHydrologyModel, PrescribedTemperatureModel, Simulation, SoilColumnBC,
                    SoilClass, SoilClasses, SoilComponentBC, SoilEnergyModel, SoilHydrologyModel, SoilModel, SoilParams,
-                   SoilThermal, SSPRK33,
+                   SoilThermal, SeriesSSPRK33, SSPRK33,
                    TemperatureDependentViscosity, TRBDF2, VerticalFlux, boundary_fluxes,
                    compute_turbulent_surface_fluxes, coordinates, default_initial_conditions,
                    initialize_states, integrate_coupled_trbdf2, integrate_dense, integrate_heat_dense, integrate_heat_series,
                    integrate_heat_trbdf2, integrate_layered_coupled_dense, integrate_layered_coupled_series,
                    integrate_layered_coupled_trbdf2, integrate_layered_heat_trbdf2, integrate_layered_trbdf2, integrate_series, integrate_trbdf2,
                    make_function_space, make_rhs, make_update_aux, run, set_tuning, stable_dt, step, step_adaptive,
-                   step_engine, step_implicit,
+                   step_engine, step_implicit, step_series, step_series_engine,
                    step_implicit_coupled, step_implicit_heat, step_implicit_layered, step_implicit_layered_coupled,
                    step_implicit_layered_heat,
                    tune_placement, vanGenuchten)

@@ -157,6 +157,8 @@ SIGNATURES = {
                                            C.c_uint32, _P]),
     "lh_integrate_layered_coupled_series": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
                                                       C.c_double, C.c_double, C.c_uint32, _P]),
+    "lh_step_ssprk33_series": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_int64]),
+    "lh_step_series_engine": (C.c_int, [_P, C.c_int64]),
     "lh_integrate_heat_dense": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                           C.c_uint32, _P, C.c_int32, _DP, C.POINTER(_P)]),
     "lh_integrate_layered_coupled_dense": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,

@@ -947,6 +947,37 @@ function integrate_layered_coupled_series!(ens::ColumnEnsemble, Y::DeviceState, 
 end
 
 """
+    step_ssprk33_series!(ens, Y, Ya, series, t, dt, nsteps) -> Y
+
+`nsteps` SSPRK33 steps of `dt` from `t` under a `BoundarySeries` in one call (lh_step_ssprk33_series): the result of
+`step_ssprk33!`, with the boundary value of every (face, component) of the series sampled per column at every stage
+time `t_k`, `t_k + dt`, `t_k + dt / 2` (`t_k = t + dt k`).  A component without a series keeps the ensemble's boundary
+value of `t` for the whole call.  Every model `step_ssprk33!` steps: conductivity factors, ice and a
+prescribed-atmosphere top (bottom series) included.  Every stage time must lie within the knots.  Asynchronous.
+"""
+function step_ssprk33_series!(ens::ColumnEnsemble, Y::DeviceState, Ya, series::BoundarySeries, t, dt, nsteps::Integer)
+    set_bcs!(ens, t)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    check(ens.ctx, ccall((:lh_step_ssprk33_series, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Int64),
+                         ens.ctx, Y.handle, ya, series.handle, t, dt, Int64(nsteps)))
+    return Y
+end
+
+"""
+    step_series_engine(ens, nsteps)
+
+`:column_stepper` (one launch, every column's wave samples its own series) or `:fused_stages` (one sampling launch and
+three stage launches per step): the engine `lh_step_ssprk33_series` runs such a call with (the results do not depend
+on it).
+"""
+function step_series_engine(ens::ColumnEnsemble, nsteps::Integer)
+    e = ccall((:lh_step_series_engine, lib), Cint, (Ptr{Cvoid}, Int64), ens.ctx, Int64(nsteps))
+    e < 0 && check(ens.ctx, e)
+    return e == 1 ? :column_stepper : :fused_stages
+end
+
+"""
     integrate_heat_dense!(ens, Y, Ya, t0, t1, dt, saveat, snapshots; series = nothing, abstol_e = 0.0, reltol = 0.0,
                           dt_cols = C_NULL) -> stats
 

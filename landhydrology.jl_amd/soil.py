@@ -1057,6 +1057,39 @@ def step_engine(model: SoilModel, nsteps: int, per_stage_boundary_values: bool =
     return rc
 
 
+def step_series_engine(model: SoilModel, nsteps: int) -> int:
+    """Build extension: what a step_series call of `nsteps` steps on the model's context would run
+    (lh_step_series_engine): _ffi.LH_ENGINE_COLUMN_STEPPER, one launch in which every column's wave samples its own
+    series, or _ffi.LH_ENGINE_FUSED_STAGES, three launches per step behind one that samples the step's values."""
+    be = model._backend()
+    rc = F.lib().lh_step_series_engine(be.ctx, int(nsteps))
+    if rc < 0:
+        F.check(rc, be.ctx)
+    return rc
+
+
+def step_series(model: SoilModel, Y: "FieldVector", Ya, series: "BoundarySeries", t: float, dt: float, nsteps: int):
+    """Build extension: `nsteps` SSPRK33 steps of `dt` from `t` under a BoundarySeries in one library call
+    (lh_step_ssprk33_series): the result of lh_step_ssprk33, with the boundary value of every (face, component) of the
+    series sampled per column at every stage time t_k, t_k + dt, t_k + dt / 2 (t_k = t + dt k).  A component without a
+    series keeps the model's boundary value of `t` for the whole call (closures are not sampled at the stage times).
+    Every stage time must lie within the knots (ValueError).  Asynchronous; returns the time reached."""
+    if not isinstance(series, BoundarySeries):
+        raise TypeError("step_series: series must be a BoundarySeries")
+    nsteps, t, dt = int(nsteps), float(t), float(dt)
+    if nsteps < 0 or not dt > 0:
+        raise ValueError("step_series: need nsteps >= 0 and dt > 0")
+    if not np.isfinite(t):
+        raise ValueError("step_series: t is not finite")
+    if nsteps:
+        times = _stage_times(t, dt, nsteps)
+        series._check_span(float(times.min()), float(times.max()))
+    be = model._backend()
+    be.set_bcs(model, t)
+    F.check(F.lib().lh_step_ssprk33_series(be.ctx, Y.handle, _handle(Ya), series._device(model), t, dt, nsteps), be.ctx)
+    return t + nsteps * dt
+
+
 def step_adaptive(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, courant: float = 0.5,
                   nsteps: int = 1, dt_max: float = 0.0, profiles_constant: bool = False, hold: int = None):
     """Build extension: `nsteps` adaptive SSPRK33 steps of `Y` with nothing leaving the device
@@ -1201,6 +1234,25 @@ class SSPRK33:
 
     def advance(self, sim, nsteps):
         return _advance_ssprk33(sim, nsteps)
+
+
+class SeriesSSPRK33(SSPRK33):
+    """SSPRK33 under a BoundarySeries (lh_step_ssprk33_series): every advance is set_bcs at the chunk's start and ONE
+    step_series call for the chunk, every column with its own boundary values at every stage time.  forcing: the
+    BoundarySeries (required); its values replace the model's on its (face, component)s, a time-dependent closure on
+    the same component included (Dirichlet closures are not sampled, as under TRBDF2(forcing=...)).  Every model
+    SSPRK33 steps, conductivity factors and a prescribed-atmosphere top included.  Prescribed profiles the device
+    reads must not change over a chunk: that case is SSPRK33's stage-by-stage path, which takes no series.
+    (A marker of its own rather than SSPRK33(forcing=...): SSPRK33's constructor is pinned without arguments.)"""
+
+    def __init__(self, forcing):
+        self.forcing = _series_forcing(type(self).__name__, forcing)
+
+    def check_scope(self, model):
+        _series_forcing(type(self).__name__, self.forcing)
+
+    def advance(self, sim, nsteps):
+        return _advance_ssprk33_series(sim, nsteps)
 
 
 class ImplicitEuler:
@@ -2105,6 +2157,26 @@ def _advance_ssprk33(sim: Simulation, nsteps: int):
         F.check(L.lh_tune_placement(be.ctx, it.u.handle, ya, None, 0, 0, None, None), be.ctx)
     F.check(L.lh_step_ssprk33(be.ctx, it.u.handle, ya, it.t, it.dt, nsteps, _dptr(bcv)), be.ctx)
     return it.t + nsteps * it.dt
+
+
+def _advance_ssprk33_series(sim: Simulation, nsteps: int):
+    """lh_step_ssprk33_series over `nsteps` steps: the model's boundary state of the chunk's start, then one call.
+    Returns the time reached."""
+    it, model = sim.integrator, sim.model
+    be = model._backend()
+    if _device_reads_aux(model, it.p):
+        for done in range(0, nsteps, _PROBE_STEPS):   # (every stage time is probed, _PROBE_STEPS steps at a time)
+            if not _aux_constant_over(model, it.p, it.t + done * it.dt, it.dt, min(_PROBE_STEPS, nsteps - done)):
+                raise ValueError(f"{type(sim.method).__name__}: the prescribed profiles the device reads change over the "
+                                 "chunk, which SSPRK33 steps stage by stage (_advance_refreshing_aux); that path takes no "
+                                 "forcing")
+    if _aux_mask(be.kind, model):
+        _refresh_prescribed(model, it.p, it.t)
+    if not getattr(it, "_placed", False) and _placement_tuning_wanted(model):   # (once per Simulation, as _advance_ssprk33)
+        it._placed = True
+        be.set_bcs(model, it.t)
+        F.check(F.lib().lh_tune_placement(be.ctx, it.u.handle, _handle(it.p), None, 0, 0, None, None), be.ctx)
+    return step_series(model, it.u, it.p, sim.method.forcing, it.t, it.dt, nsteps)   # (set_bcs at it.t, then the call)
 
 
 def _advance(sim: Simulation, nsteps: int):
