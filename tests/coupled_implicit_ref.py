@@ -24,6 +24,10 @@ stage 2 and v_0 for f_0.  Per-column values of the model take precedence.
 tol: None iterates Newton to round-off; a number stops it by the device's rule, max_i |delta_i| <=
 tol max(|Y_i|, nu) on the Newton step, within max_iter iterations.
 
+The Newton iteration with its stopping rules, the coloured bands and the sampling of bcv are integrator_core's
+(newton_stage, fd_bands, sample); this module supplies the oracle's coupled tendencies, the exact energy bands and
+the two methods' stage sequence.
+
 Test infrastructure (tests/test_coupled_implicit_reference.py, tests/test_gpu_coupled_implicit.py)."""
 from __future__ import annotations
 
@@ -33,11 +37,11 @@ import numpy as np
 
 import case_model as M
 import implicit_ref as R
+import integrator_core as core
 import parity_cases as pc
 
 O = pc.O
-GAMMA = 2.0 - np.sqrt(2.0)
-D = GAMMA / 2.0
+GAMMA, D, _sample = core.GAMMA, core.D, core.sample
 _c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
 
 
@@ -70,65 +74,22 @@ def with_bc(om, sample):
 def _fd_jacobian(om, vl, ti, coef, f0):
     """Bands (a, b, c) of J = I - coef d f_w / d vl by coloured forward differences (implicit_ref.fd_jacobian
     on the coupled water tendency)."""
-    ncols, n = vl.shape
-    nu = R._col_param(om, ncols, "nu", om.soil.nu)[:, None]
-    a, b, c = np.zeros_like(vl), np.ones_like(vl), np.zeros_like(vl)
-    for k in range(3):
-        mask = (np.arange(n) % 3 == k)[None, :]
-        h = np.sqrt(np.finfo(vl.dtype).eps) * np.maximum(np.abs(vl), nu)
-        h = np.where(vl >= nu, -h, h) * mask
-        df = water_tendency(om, vl + h, ti) - f0
-        for i in range(k, n, 3):
-            hi = h[:, i]
-            b[:, i] -= coef * df[:, i] / hi
-            if i > 0:
-                c[:, i - 1] = -coef * df[:, i - 1] / hi
-            if i + 1 < n:
-                a[:, i + 1] = -coef * df[:, i + 1] / hi
-    return a, b, c
+    nu = R._col_param(om, vl.shape[0], "nu", om.soil.nu)[:, None]
+    return core.fd_bands(lambda v: water_tendency(om, v, ti), vl, coef, f0, nu)
+
+
+def safeguard(om, ncols):
+    """(nu, theta_r) of the Newton stage's safeguard, one per column: [ncols, 1]"""
+    return R._col_param(om, ncols, "nu", om.soil.nu)[:, None], R._col_param(om, ncols, "vg_theta_r", om.vg.theta_r)[:, None]
 
 
 def newton_stage(om, y, w, ti, coef, tol=None, max_iter=None):
     """The water stage Y - w - coef f_w(Y) = 0 from the guess y.  Returns (Y, iterations [ncols],
     converged [ncols])."""
-    vl = np.array(y, dtype=np.float64)
     ti = _c(ti)
-    ncols = vl.shape[0]
-    if max_iter is None:
-        max_iter = 120 if tol is None else 50
-    nu = R._col_param(om, ncols, "nu", om.soil.nu)[:, None]
-    tr = R._col_param(om, ncols, "vg_theta_r", om.vg.theta_r)[:, None]
-    dmax = R.DMAX_FRAC * (nu - tr)
-    iters = np.zeros(ncols, dtype=np.int64)
-    conv = np.zeros(ncols, dtype=bool)
-    active = np.ones(ncols, dtype=bool)
-    prev = np.full(ncols, np.inf)
-    lam = np.ones((ncols, 1))
-    for it in range(max_iter):
-        f0 = water_tendency(om, vl, ti)
-        Rv = vl - w - coef * f0
-        a, b, c = _fd_jacobian(om, vl, ti, coef, f0)
-        d = R.thomas(a, b, c, -Rv)
-        new = vl + np.clip(lam * d, -dmax, dmax)
-        floor = tr + 0.5 * (vl - tr)
-        new = np.where(vl > tr, np.maximum(new, floor), np.maximum(new, vl))
-        nue = nu - ti
-        new = np.where((vl < nue) & (new > nue), nue, new)
-        step = np.max(np.abs(d), axis=1)
-        vl = np.where(active[:, None], new, vl)
-        iters[active] = it + 1
-        if tol is None:   # round-off: the update is zero or has stopped shrinking (after having become small)
-            done = (step == 0) | ((step >= 0.5 * prev) & (step < 1e-12))
-        else:             # the device's rule, on the Newton step itself
-            done = np.all(np.abs(d) <= tol * np.maximum(np.abs(new), nu), axis=1)
-        conv |= active & done
-        stall = (step > R.STALL * prev)[:, None]
-        lam = np.where(stall, np.maximum(0.5 * lam, 1.0 / 16), np.minimum(2.0 * lam, 1.0))
-        prev = np.where(active, step, prev)
-        active &= ~done
-        if not active.any():
-            break
-    return vl, iters, conv
+    stop, cap = (core.round_off, 120) if tol is None else (core.fixed_step_rule(tol), 50)
+    nu, tr = safeguard(om, np.shape(y)[0])
+    return core.newton_stage(lambda v: water_tendency(om, v, ti), nu, tr, ti, coef, y, w, stop, cap if max_iter is None else max_iter)
 
 
 def energy_bands(om, vl, ti):
@@ -156,13 +117,6 @@ def energy_stage(om, vl, ti, w, coef):
     """The energy stage Y - w - coef f_e(Y) = 0 at the water state vl: (I - coef A) Y = w + coef f0."""
     (lo, di, up), f0 = energy_bands(om, vl, ti)
     return R.thomas(-coef * lo, 1.0 - coef * di, -coef * up, w + coef * f0)
-
-
-def _sample(bcv, k, w=None):
-    if bcv is None:
-        return None
-    b = np.asarray(bcv, dtype=np.float64)
-    return b[k] if w is None else (1.0 - w) * b[k] + w * b[k + 1]
 
 
 def coupled_implicit(om, vl, ti, rhoe, dt, nsteps, method="euler", bcv=None, tol=None, max_iter=None, round_to=None):

@@ -5,7 +5,7 @@ With vartheta_l and theta_i prescribed the tendency is affine in rhoe_int: f(Y, 
 only b depends on the boundary values.  A is built by applying the oracle's tendency to unit vectors,
 A[:, j] = f(e_j) - f(0) (three coloured evaluations: f_i reads cells i-1, i, i+1 only), no closure is
 restated here.  A stage Y - w - c f(Y) = 0 is the tridiagonal system (I - c A) Y = w + c b, solved in
-Float64 with Thomas (no pivoting: I - c A is a column-diagonally-dominant M-matrix).
+Float64 with Thomas (integrator_core.thomas; no pivoting: I - c A is a column-diagonally-dominant M-matrix).
 
 Methods of lh_step_heat_implicit, fixed step h:
   backward Euler:  (I - h A) Y_1 = Y_n + h b(t + h)
@@ -25,11 +25,11 @@ import copy
 import numpy as np
 
 import case_model as M
+import integrator_core as core
 import parity_cases as pc
 
 O = pc.O
-GAMMA = 2.0 - np.sqrt(2.0)
-D = GAMMA / 2.0
+GAMMA, D, thomas, _sample = core.GAMMA, core.D, core.thomas, core.sample
 
 
 def tendency(om, vl, ti, rhoe):
@@ -91,33 +91,9 @@ def cond_inf(bands, coef):
     return np.array([np.linalg.cond(m, np.inf) for m in Mx])
 
 
-def thomas(a, b, c, d):
-    """Solve a_i x_{i-1} + b_i x_i + c_i x_{i+1} = d_i, one system per row."""
-    n = b.shape[1]
-    cp, dp = np.zeros_like(b), np.zeros_like(b)
-    cp[:, 0] = c[:, 0] / b[:, 0]
-    dp[:, 0] = d[:, 0] / b[:, 0]
-    for i in range(1, n):
-        den = b[:, i] - a[:, i] * cp[:, i - 1]
-        cp[:, i] = c[:, i] / den
-        dp[:, i] = (d[:, i] - a[:, i] * dp[:, i - 1]) / den
-    x = np.zeros_like(b)
-    x[:, -1] = dp[:, -1]
-    for i in range(n - 2, -1, -1):
-        x[:, i] = dp[:, i] - cp[:, i] * x[:, i + 1]
-    return x
-
-
 def stage_solve(bands, coef, rhs):
     lo, di, up = bands
     return thomas(-coef * lo, 1.0 - coef * di, -coef * up, rhs)
-
-
-def _sample(bcv, k, w=None):
-    if bcv is None:
-        return None
-    b = np.asarray(bcv, dtype=np.float64)
-    return b[k] if w is None else (1.0 - w) * b[k] + w * b[k + 1]
 
 
 def heat_implicit(om, vl, ti, rhoe, dt, nsteps, method="euler", bcv=None):

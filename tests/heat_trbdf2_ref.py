@@ -19,6 +19,9 @@ ft: None, or the type to which everything the device keeps in an FT plane is rou
 the boundary values, the tolerances and the step proposals handed out.  (r' of the device's forward sweeps is a plane
 too; it is internal to the solve and has no counterpart in the Thomas solve here.)
 
+The controller and the accept / reject loop are integrator_core's (step_factor, adaptive_loop, here with max_steps
+failing the column); this module supplies the linear attempt, the boundary values and the FT rounding.
+
 Test infrastructure (tests/test_heat_trbdf2_reference.py, tests/test_gpu_heat_trbdf2.py)."""
 from __future__ import annotations
 
@@ -26,7 +29,8 @@ import numpy as np
 
 import case_model as M
 import heat_implicit_ref as H
-from trbdf2_ref import B, D, GAMMA, HMIN_FRAC
+import integrator_core as core
+from integrator_core import B, D, GAMMA, HMIN_FRAC
 
 MAX_STEPS = 100000   # LH_TRBDF2_MAX_STEPS
 RELTOL = 1e-3
@@ -81,8 +85,7 @@ def problem(case):
     return Problem(case.om, lambda y, smp: H.tendency(H.with_energy_bc(case.om, smp), vl, ti, y), bands, vl.shape)
 
 
-def _rounder(ft):
-    return (lambda a: a) if ft is None else (lambda a: np.asarray(a).astype(ft).astype(np.float64))
+_rounder = core.rounder
 
 
 def fresh_tendency(P, y, bcv, ft=None):
@@ -110,60 +113,34 @@ def attempt(P, y, fn, t, hh, bcv=None, t0=0.0, t1=1.0, ft=None):
 
 
 def error_norm(e, yn, y1, abstol_e, reltol):
-    q = e / (abstol_e + reltol * np.maximum(np.abs(yn), np.abs(y1)))
-    return np.sqrt(np.mean(q ** 2, axis=1))
+    return core.error_norm(e, yn, y1, abstol_e, reltol)
 
 
-def step_factor(E):
-    """The controller's h_new / h: clamp(0.9 E^(-1/3), 0.2, 5), 0.2 for a NaN."""
-    with np.errstate(divide="ignore", invalid="ignore"):
-        fac = 0.9 * np.asarray(E, dtype=np.float64) ** (-1.0 / 3.0)
-    return np.where(np.isnan(fac), 0.2, np.clip(fac, 0.2, 5.0))
+step_factor = core.step_factor
 
 
 def integrate(P, rhoe, t0, t1, dt, abstol_e=None, reltol=RELTOL, bcv=None, h0=None, ft=None, max_steps=MAX_STEPS):
     """Integrate the [ncols, nlev] state from t0 to t1, every column with its own t and h from h0 (default, and where
     h0 <= 0: dt).  Returns (rhoe, info), info = dict(t, h, accepted, rejected, failed, dt_cols) per column; a failed
-    column keeps its last accepted state and dt_cols 0."""
+    column (h below the floor, or max_steps attempts) keeps its last accepted state and dt_cols 0."""
     rnd = _rounder(ft)
     y = rnd(np.array(rhoe, dtype=np.float64))
     ncols = y.shape[0]
     abstol_e = float(rnd(abstol_e_default(P.om) if not abstol_e else abstol_e))
     reltol = float(rnd(RELTOL if not reltol else reltol))
-    t = np.full(ncols, float(t0))
     h = np.full(ncols, float(dt))
     if h0 is not None:
         h = np.where(np.asarray(h0, dtype=np.float64) > 0, np.asarray(h0, dtype=np.float64), h)
-    acc = np.zeros(ncols, dtype=np.int64)
-    rej = np.zeros(ncols, dtype=np.int64)
-    failed = np.zeros(ncols, dtype=bool)
     if not t1 > t0:
-        return y, dict(t=t, h=h, accepted=acc, rejected=rej, failed=failed, dt_cols=rnd(h))
-    fn = rnd(fresh_tendency(P, y, bcv, ft))
-    hmin = HMIN_FRAC * (t1 - t0)
-    while True:
-        failed |= (t < t1) & (acc + rej >= max_steps)
-        act = (t < t1) & ~failed
-        if not act.any():
-            break
-        clip = t + h * (1.0 + 1e-10) >= t1
-        hh = np.where(clip, t1 - t, h)
-        hh = np.where(act, hh, hh[act][0])   # (inactive columns: an active column's step, not committed)
-        ta = np.where(act, t, t[act][0])
-        r = attempt(P, y, fn, ta, hh, bcv, t0, t1, ft)
-        E = error_norm(r["e"], y, r["y1"], abstol_e, reltol)
-        fac = step_factor(E)
-        ok = E <= 1.0
-        good, bad = act & ok, act & ~ok
-        g = good[:, None]
-        y, fn = np.where(g, r["y1"], y), np.where(g, r["fn1"], fn)
-        t = np.where(good, np.where(clip, t1, t + hh), t)
-        hn = np.where(clip & (fac >= 1.0) & ok, np.maximum(hh * fac, h), hh * fac)
-        h = np.where(act, hn, h)
-        acc += good
-        rej += bad
-        failed |= bad & ~(h >= hmin)
-    return y, dict(t=t, h=h, accepted=acc, rejected=rej, failed=failed, dt_cols=np.where(failed, 0.0, rnd(h)))
+        none = np.zeros(ncols, dtype=np.int64)
+        return y, dict(t=np.full(ncols, float(t0)), h=h, accepted=none, rejected=none.copy(), failed=np.zeros(ncols, dtype=bool), dt_cols=rnd(h))
+
+    def one(state, f, t, hh):
+        r = attempt(P, state[0], f[0], t, hh, bcv, t0, t1, ft)
+        return (r["y1"],), (r["fn1"],), error_norm(r["e"], state[0], r["y1"], abstol_e, reltol), None
+
+    (y,), info = core.adaptive_loop(one, (y,), (rnd(fresh_tendency(P, y, bcv, ft)),), t0, t1, h, max_steps, cap_fails=True)
+    return y, dict(info, dt_cols=np.where(info["failed"], 0.0, rnd(info["h"])))
 
 
 def fixed_trbdf2(P, rhoe, t0, t1, nsteps, bcv=None):

@@ -10,7 +10,9 @@ rhoe_int at fixed vartheta_l, theta_i.  So the stage is solved exactly by
   energy: the bands of the affine f_e at the new water state from three coloured evaluations, then
           implicit_ref.thomas.
 Backward Euler and TR-BDF2 (gamma = 2 - sqrt 2), the sampling of bcv (coupled_implicit_ref._sample, with_bc) and the
-options tol= and round_to= are coupled_implicit_ref.coupled_implicit's.  Needs neither the oracle nor the library.
+options tol= and round_to= are coupled_implicit_ref.coupled_implicit's.  The Newton iteration, the coloured bands
+and the sampling of bcv are integrator_core's; this module supplies the layered tendencies, the exact energy bands,
+every cell's own nu, theta_r, theta_i and the two methods' stage sequence.  Needs neither the oracle nor the library.
 
 Test infrastructure (tests/test_layered_coupled_implicit_reference.py, tests/test_gpu_layered_coupled_implicit.py)."""
 from __future__ import annotations
@@ -23,17 +25,10 @@ import numpy as np
 import case_model as M
 import layered_heat_ref as LH
 import layered_ref as R
-from implicit_ref import DMAX_FRAC, STALL, thomas
+import integrator_core as core
+from integrator_core import DMAX_FRAC, STALL, thomas
 
-GAMMA = 2.0 - np.sqrt(2.0)
-D = GAMMA / 2.0
-
-
-def _sample(bcv, k, w=None):   # (coupled_implicit_ref._sample, which imports the oracle)
-    if bcv is None:
-        return None
-    b = np.asarray(bcv, dtype=np.float64)
-    return b[k] if w is None else (1.0 - w) * b[k] + w * b[k + 1]
+GAMMA, D, _sample = core.GAMMA, core.D, core.sample
 
 
 def with_bc(lay, sample):
@@ -62,65 +57,20 @@ def water_tendency(l64, vl):
 
 def _fd_jacobian(l64, vl, coef, f0, nu):
     """layered_implicit_ref.fd_jacobian on the coupled water tendency"""
-    n = vl.shape[1]
-    a, b, c = np.zeros_like(vl), np.ones_like(vl), np.zeros_like(vl)
-    for k in range(3):
-        mask = (np.arange(n) % 3 == k)[None, :]
-        h = np.sqrt(np.finfo(vl.dtype).eps) * np.maximum(np.abs(vl), nu)
-        h = np.where(vl >= nu, -h, h) * mask
-        df = water_tendency(l64, vl + h) - f0
-        for i in range(k, n, 3):
-            hi = h[:, i]
-            b[:, i] -= coef * df[:, i] / hi
-            if i > 0:
-                c[:, i - 1] = -coef * df[:, i - 1] / hi
-            if i + 1 < n:
-                a[:, i + 1] = -coef * df[:, i + 1] / hi
-    return a, b, c
+    return core.fd_bands(lambda v: water_tendency(l64, v), vl, coef, f0, nu)
+
+
+def safeguard(l64):
+    """(nu, theta_r, theta_i) of the Newton stage's safeguard, every cell's own: [ncols, nlev]"""
+    p = R.cell_params(l64)
+    return p["nu"].astype(np.float64), p["theta_r"].astype(np.float64), np.asarray(l64.case.ti, dtype=np.float64)
 
 
 def newton_stage(l64, y, w, coef, tol=None, max_iter=None):
-    """The water stage Y - w - coef f_w(Y) = 0 from the guess y: layered_implicit_ref.stage_solve's iteration (the
-    safeguard with every cell's own nu, theta_r) with coupled_implicit_ref.newton_stage's two stopping rules.
-    Returns (Y, iterations [ncols], converged [ncols])."""
-    vl = np.array(y, dtype=np.float64)
-    ncols = vl.shape[0]
-    if max_iter is None:
-        max_iter = 120 if tol is None else 50
-    p = R.cell_params(l64)
-    nu, tr = p["nu"].astype(np.float64), p["theta_r"].astype(np.float64)
-    ti = np.asarray(l64.case.ti, dtype=np.float64)
-    dmax = DMAX_FRAC * (nu - tr)
-    iters = np.zeros(ncols, dtype=np.int64)
-    conv = np.zeros(ncols, dtype=bool)
-    active = np.ones(ncols, dtype=bool)
-    prev = np.full(ncols, np.inf)
-    lam = np.ones((ncols, 1))
-    for it in range(max_iter):
-        f0 = water_tendency(l64, vl)
-        Rv = vl - w - coef * f0
-        a, b, c = _fd_jacobian(l64, vl, coef, f0, nu)
-        d = thomas(a, b, c, -Rv)
-        new = vl + np.clip(lam * d, -dmax, dmax)
-        floor = tr + 0.5 * (vl - tr)
-        new = np.where(vl > tr, np.maximum(new, floor), np.maximum(new, vl))
-        nue = nu - ti
-        new = np.where((vl < nue) & (new > nue), nue, new)
-        step = np.max(np.abs(d), axis=1)
-        vl = np.where(active[:, None], new, vl)
-        iters[active] = it + 1
-        if tol is None:   # round-off: the update is zero or has stopped shrinking (after having become small)
-            done = (step == 0) | ((step >= 0.5 * prev) & (step < 1e-12))
-        else:             # the device's rule, on the Newton step itself, with the cell's own nu
-            done = np.all(np.abs(d) <= tol * np.maximum(np.abs(new), nu), axis=1)
-        conv |= active & done
-        stall = (step > STALL * prev)[:, None]
-        lam = np.where(stall, np.maximum(0.5 * lam, 1.0 / 16), np.minimum(2.0 * lam, 1.0))
-        prev = np.where(active, step, prev)
-        active &= ~done
-        if not active.any():
-            break
-    return vl, iters, conv
+    """The water stage Y - w - coef f_w(Y) = 0 from the guess y: the safeguard with every cell's own nu, theta_r and
+    coupled_implicit_ref.newton_stage's two stopping rules.  Returns (Y, iterations [ncols], converged [ncols])."""
+    stop, cap = (core.round_off, 120) if tol is None else (core.fixed_step_rule(tol), 50)
+    return core.newton_stage(lambda v: water_tendency(l64, v), *safeguard(l64), coef, y, w, stop, cap if max_iter is None else max_iter)
 
 
 def energy_bands(l64, vl):

@@ -16,7 +16,9 @@ time; where the columns' stage times differ only Dirichlet values may change in 
 newton: None iterates the water stages to round-off; (kappa, abstol, reltol, cap) stops them by the device's rule,
 max_i |delta_i| / (abstol + reltol |Y_i|) <= kappa within cap iterations.  round_to: coupled_trbdf2_ref.attempt's.
 
-Pure NumPy: imports neither the oracle nor the library's kernels.
+The attempt, the error norm, the energy solve, the controller and the accept / reject loop are integrator_core's,
+shared with coupled_trbdf2_ref, over the provider below: the layered tendencies, bands and boundary values and
+every cell's own safeguard.  Pure NumPy: imports neither the oracle nor the library's kernels.
 
 Test infrastructure (tests/test_layered_coupled_trbdf2_reference.py, tests/test_gpu_layered_coupled_trbdf2.py)."""
 from __future__ import annotations
@@ -29,13 +31,9 @@ import numpy as np
 import case_model as M
 import layered_coupled_implicit_ref as LC
 import layered_heat_ref as LH
-import layered_ref as R
-from implicit_ref import DMAX_FRAC, STALL, thomas
+import integrator_core as core
 
-GAMMA = LC.GAMMA
-D = LC.D
-B = ((1.0 - np.sqrt(2.0)) / 3.0, 1.0 / 3.0, (np.sqrt(2.0) - 2.0) / 3.0)
-HMIN_FRAC = 1e-10
+GAMMA, D, B, HMIN_FRAC = core.GAMMA, core.D, core.B, core.HMIN_FRAC
 ABSTOL, RELTOL = 1e-6, 1e-3
 NEWTON_KAPPA, NEWTON_MAX = 0.01, 10   # the library's stage Newton test
 
@@ -71,116 +69,32 @@ def with_bc(lay, bcv, t0, t1, t):
     return LH.LayeredHeat(dataclasses.replace(l64.case, om=om), l64.classes, l64.thermal, l64.class_map)
 
 
+def provider(lay):
+    """integrator_core.CoupledProblem of the layered case `lay`: a stage's model is its Float64 twin under with_bc's
+    boundary values."""
+    return core.CoupledProblem(at=lambda bcv, t0, t1, t: with_bc(lay, bcv, t0, t1, t), water_tendency=LC.water_tendency,
+                               tendencies=LC.tendencies, energy_bands=LC.energy_bands, safeguard=LC.safeguard)
+
+
+error_norm, step_factor = core.coupled_error_norm, core.step_factor
+
+
 def water_stage(l64, y0, w, coef, newton=None):
-    """The water stage Y - w - coef f_w(Y) = 0 from the guess y0, coef one per column:
-    layered_coupled_implicit_ref.newton_stage's iteration (the safeguard with every cell's own nu, theta_r) with
-    coupled_trbdf2_ref.water_stage's two stopping rules.  Returns (Y, iterations [ncols], converged [ncols])."""
-    vl = np.array(y0, dtype=np.float64)
-    ncols = vl.shape[0]
-    coef = np.broadcast_to(np.asarray(coef, dtype=np.float64), (ncols,)).copy()
-    max_iter = 120 if newton is None else newton[3]
-    p = R.cell_params(l64)
-    nu, tr = p["nu"].astype(np.float64), p["theta_r"].astype(np.float64)
-    ti = np.asarray(l64.case.ti, dtype=np.float64)
-    dmax = DMAX_FRAC * (nu - tr)
-    iters = np.zeros(ncols, dtype=np.int64)
-    conv = np.zeros(ncols, dtype=bool)
-    active = np.ones(ncols, dtype=bool)
-    prev = np.full(ncols, np.inf)
-    lam = np.ones((ncols, 1))
-    for it in range(max_iter):
-        f0 = LC.water_tendency(l64, vl)
-        Rv = vl - w - coef[:, None] * f0
-        a, b, c = LC._fd_jacobian(l64, vl, coef, f0, nu)
-        d = thomas(a, b, c, -Rv)
-        new = vl + np.clip(lam * d, -dmax, dmax)
-        floor = tr + 0.5 * (vl - tr)
-        new = np.where(vl > tr, np.maximum(new, floor), np.maximum(new, vl))
-        nue = nu - ti
-        new = np.where((vl < nue) & (new > nue), nue, new)
-        step = np.max(np.abs(d), axis=1)
-        vl = np.where(active[:, None], new, vl)
-        iters[active] = it + 1
-        if newton is None:
-            done = (step == 0) | ((step >= 0.5 * prev) & (step < 1e-12))
-        else:
-            kappa, atol, rtol, _ = newton
-            done = np.all(np.abs(d) <= kappa * (atol + rtol * np.abs(new)), axis=1)
-        conv |= active & done
-        stall = (step > STALL * prev)[:, None]
-        lam = np.where(stall, np.maximum(0.5 * lam, 1.0 / 16), np.minimum(2.0 * lam, 1.0))
-        prev = np.where(active, step, prev)
-        active &= ~done
-        if not active.any():
-            break
-    return vl, iters, conv
+    """The water stage Y - w - coef f_w(Y) = 0 from the guess y0, coef one per column, with every cell's own nu,
+    theta_r and coupled_trbdf2_ref.water_stage's two stopping rules.  Returns (Y, iterations [ncols], converged [ncols])."""
+    return core.water_stage(provider(l64), l64, y0, w, coef, newton)
 
 
 def energy_solve(l64, vl, rhs, coef, homogeneous=False):
     """(I - coef A) x = rhs + coef f0 at the water state vl, f_e(rhoe) = A rhoe + f0 (coef one per column);
     homogeneous: (I - coef A) x = rhs."""
-    (lo, di, up), f0 = LC.energy_bands(l64, vl)
-    c = np.broadcast_to(np.asarray(coef, dtype=np.float64), (vl.shape[0],))[:, None]
-    return thomas(-c * lo, 1.0 - c * di, -c * up, rhs if homogeneous else rhs + c * f0)
+    return core.energy_solve(provider(l64), l64, vl, rhs, coef, homogeneous)
 
 
 def attempt(lay, vn, en, fvn, fen, t, h, bcv=None, t0=0.0, t1=1.0, newton=None, block="diagonal", round_to=None):
     """One TR-BDF2 step of every column from (vn, en) with tendencies (fvn, fen) at times t with steps h (scalars
     or one per column): coupled_trbdf2_ref.attempt's formulas, arguments (theta_i is the case's) and result."""
-    ncols = vn.shape[0]
-    rnd = (lambda a: a) if round_to is None else (lambda a: a.astype(round_to).astype(np.float64))
-    h = np.broadcast_to(np.asarray(h, dtype=np.float64), (ncols,)).copy()
-    t = np.broadcast_to(np.asarray(t, dtype=np.float64), (ncols,)).copy()
-    if np.all(t == t[0]) and np.all(h == h[0]):
-        tg, te = float(t[0] + GAMMA * h[0]), float(t[0] + h[0])   # (scalar boundary values where the columns agree)
-    else:
-        tg, te = t + GAMMA * h, t + h
-    dh = rnd(D * h)
-    c = dh[:, None]
-    og = with_bc(lay, bcv, t0, t1, tg)
-    w1v = rnd(vn + rnd(c * fvn))
-    vg, i1, c1 = water_stage(og, vn, w1v, dh, newton)
-    vg = rnd(vg)
-    w1e = rnd(en + rnd(c * fen))
-    eg = rnd(energy_solve(og, vg, w1e, dh))
-    k2 = 1.0 / (GAMMA * (2.0 - GAMMA))
-    wv = rnd(rnd(vg - rnd((1.0 - GAMMA) ** 2 * vn)) * k2)
-    we = rnd(rnd(eg - rnd((1.0 - GAMMA) ** 2 * en)) * k2)
-    o1 = og if bcv is None else with_bc(lay, bcv, t0, t1, te)
-    v1, i2, c2 = water_stage(o1, vg, wv, dh, newton)
-    v1 = rnd(v1)
-    e1 = rnd(energy_solve(o1, v1, we, dh))
-    hc = h[:, None]
-    rv = B[0] * (hc * fvn) + B[1] * (vg - w1v) / D + B[2] * (v1 - wv) / D
-    re = B[0] * (hc * fen) + B[1] * (eg - w1e) / D + B[2] * (e1 - we) / D
-    f1 = LC.water_tendency(o1, v1)
-    nu = R.cell_params(o1)["nu"].astype(np.float64)
-    a, b, cc = LC._fd_jacobian(o1, v1, dh, f1, nu)
-    ev = thomas(a, b, cc, rv)
-    rhs_e = re
-    if block == "full":   # + d h J_ew e_w: f_e along e_w at (v1, e1), central difference
-        s = 1e-3 * np.max(np.abs(v1)) / max(float(np.max(np.abs(ev))), 1e-300)
-        s = min(s, 1.0)
-        jew = (LC.tendencies(o1, v1 + s * ev, e1)[1] - LC.tendencies(o1, v1 - s * ev, e1)[1]) / (2.0 * s)
-        rhs_e = re + c * jew
-    else:
-        assert block == "diagonal"
-    ee = energy_solve(o1, v1, rhs_e, dh, homogeneous=True)
-    return dict(v1=v1, e1=e1, fv1=rnd(rnd(v1 - wv) / c), fe1=rnd(rnd(e1 - we) / c), ev=ev, ee=ee, rv=rv, re=re, iters=i1 + i2,
-                conv=c1 & c2)
-
-
-def error_norm(ev, ee, vn, v1, en, e1, abstol, abstol_e, reltol):
-    qw = ev / (abstol + reltol * np.maximum(np.abs(vn), np.abs(v1)))
-    qe = ee / (abstol_e + reltol * np.maximum(np.abs(en), np.abs(e1)))
-    return np.sqrt((np.sum(qw ** 2, axis=1) + np.sum(qe ** 2, axis=1)) / (2 * ev.shape[1]))
-
-
-def step_factor(E):
-    """The controller's h_new / h: clamp(0.9 E^(-1/3), 0.2, 5), 0.2 for a NaN."""
-    with np.errstate(divide="ignore", invalid="ignore"):
-        fac = 0.9 * np.asarray(E, dtype=np.float64) ** (-1.0 / 3.0)
-    return np.where(np.isnan(fac), 0.2, np.clip(fac, 0.2, 5.0))
+    return core.coupled_attempt(provider(lay), vn, en, fvn, fen, t, h, bcv, t0, t1, newton, block, round_to)
 
 
 def first_attempt(lay, h, bcv=None, newton=None, block="diagonal", round_to=None, abstol=ABSTOL, abstol_e=None, reltol=RELTOL):
@@ -197,41 +111,8 @@ def integrate(lay, vl, rhoe, t0, t1, dt, abstol=ABSTOL, abstol_e=None, reltol=RE
               round_to=None, max_steps=100000):
     """Integrate the [ncols, nlev] state (vl, rhoe) of `lay` from t0 to t1, every column with its own t and h from h0
     (default dt).  Returns (vl, rhoe, info), info = dict(t, h, accepted, rejected, failed) per column."""
-    v, e = np.array(vl, dtype=np.float64), np.array(rhoe, dtype=np.float64)
-    ncols = v.shape[0]
-    if abstol_e is None:
-        abstol_e = abstol_e_default(lay)
-    rnd = (lambda a: a) if round_to is None else (lambda a: a.astype(round_to).astype(np.float64))
-    fv, fe = (rnd(f) for f in LC.tendencies(with_bc(lay, bcv, t0, t1, float(t0)), v, e))
-    t = np.full(ncols, float(t0))
-    h = np.full(ncols, float(dt)) if h0 is None else np.array(h0, dtype=np.float64)
-    acc = np.zeros(ncols, dtype=np.int64)
-    rej = np.zeros(ncols, dtype=np.int64)
-    failed = np.zeros(ncols, dtype=bool)
-    hmin = HMIN_FRAC * (t1 - t0)
-    for _ in range(max_steps):
-        act = (t < t1) & ~failed
-        if not act.any():
-            break
-        clip = t + h * (1.0 + 1e-10) >= t1
-        hh = np.where(clip, t1 - t, h)
-        hh = np.where(act, hh, hh[act][0])   # (inactive columns: an active column's step, not committed)
-        ta = np.where(act, t, t[act][0])
-        r = attempt(lay, v, e, fv, fe, ta, hh, bcv, t0, t1, newton, round_to=round_to)
-        E = error_norm(r["ev"], r["ee"], v, r["v1"], e, r["e1"], abstol, abstol_e, reltol)
-        fac = np.where(r["conv"], step_factor(E), 0.25)
-        ok = r["conv"] & (E <= 1.0)
-        good, bad = act & ok, act & ~ok
-        g = good[:, None]
-        v, e = np.where(g, r["v1"], v), np.where(g, r["e1"], e)
-        fv, fe = np.where(g, r["fv1"], fv), np.where(g, r["fe1"], fe)
-        t = np.where(good, np.where(clip, t1, t + hh), t)
-        hn = np.where(clip & (fac >= 1.0) & ok, np.maximum(hh * fac, h), hh * fac)
-        h = np.where(act, hn, h)
-        acc += good
-        rej += bad
-        failed |= bad & ~(h >= hmin)
-    return v, e, dict(t=t, h=h, accepted=acc, rejected=rej, failed=failed)
+    return core.coupled_integrate(provider(lay), vl, rhoe, t0, t1, dt, abstol, abstol_e_default(lay) if abstol_e is None else abstol_e,
+                                  reltol, bcv, h0, newton, round_to, max_steps)
 
 
 # ------------------------------------------------------------------ cases shared by the two test files
