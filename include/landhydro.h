@@ -576,6 +576,30 @@ int lh_integrate_layered_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double
                                 double dt, double abstol, double reltol, uint32_t flags,
                                 void* dt_cols_device_ft, const double* bcv);
 
+/* lh_step_implicit_euler and lh_integrate_trbdf2 for a Richards context whose hydrology has a
+ * conductivity factor other than NoEffect (lh_set_conductivity_factors: TemperatureDependentViscosity
+ * and / or IceImpedance): the same arguments, defaults, bcv layouts, flags
+ * (LH_TRBDF2_FIXED, dt_cols), statistics (lh_implicit_stats / lh_implicit_iterations, lh_trbdf2_stats),
+ * scratch planes and status bits 3 and 4; status bit 0 where a Newton step is not finite (a cell with
+ * theta_l + theta_i = 0 under the impedance factor has K = NaN, as in the reference).
+ * f is lh_rhs's tendency of the same context, K = visc(T) imp(vartheta_l, theta_i) K_NoEffect.  T is
+ * whatever Ya holds at the call (a plane, or a level-uniform profile from lh_upload_profile) and is
+ * held through the call, as every stepping call holds the prescribed fields; theta_i is constant
+ * through the call.  The viscosity factor is then a constant of every cell and the impedance factor a
+ * function of the cell's own vartheta_l, so the Newton Jacobian stays tridiagonal:
+ *   dK/dvartheta_l = visc imp dK_NoEffect/dvartheta_l + K Omega ln10 theta_i / (theta_l + theta_i)^2,
+ * the second term only where vartheta_l < nu - theta_i.  Per-column parameter arrays and LH_MATH_LIBM
+ * are served as the plain calls serve them.
+ * LH_EINVAL as the plain calls, checked first.  Then LH_EMODEL, in this order: any model but
+ * LH_MODEL_RICHARDS, a class map, a context whose factors are both NoEffect (use the call without
+ * `factors`), a prescribed atmosphere.  Boundary-value series and dense output do not take these
+ * contexts.  Asynchronous. */
+int lh_step_factors_implicit_euler(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
+                                   int64_t nsteps, const double* bcv, double tol, int32_t max_iter);
+int lh_integrate_factors_trbdf2(lh_ctx*, lh_state* Y, const lh_state* Ya, double t0, double t1,
+                                double dt, double abstol, double reltol, uint32_t flags,
+                                void* dt_cols_device_ft, const double* bcv);
+
 /* Implicit steps of the heat-only model, SoilEnergyModel + PrescribedHydrologyModel
  * (right_hand_side.jl:192-263).  With vartheta_l and theta_i prescribed the
  * tendency is affine in rhoe_int, so a stage Y - w - c f(Y) = 0 is one tridiagonal solve, exact up to

@@ -138,6 +138,10 @@ SIGNATURES = {
                                                  C.c_int32]),
     "lh_integrate_layered_trbdf2": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
                                               C.c_double, C.c_uint32, _P, _DP]),
+    "lh_step_factors_implicit_euler": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, _DP, C.c_double,
+                                                 C.c_int32]),
+    "lh_integrate_factors_trbdf2": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
+                                              C.c_double, C.c_uint32, _P, _DP]),
     "lh_integrate_coupled_trbdf2": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
                                               C.c_double, C.c_double, C.c_uint32, _P, _DP]),
     "lh_integrate_layered_coupled_trbdf2": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,

@@ -5,6 +5,7 @@
 #include "lh_launch.hpp"
 #include "lh_layered.hpp"
 #include "lh_layered_implicit.hpp"
+#include "lh_factors_implicit.hpp"
 #include "lh_layered_heat.hpp"
 #include "lh_layered_heat_implicit.hpp"
 #include "lh_layered_heat_trbdf2.hpp"
@@ -2282,6 +2283,19 @@ static int implicit_refusals(lh_ctx* c, const char* who, const lh_state* Y, cons
     return stepping_preamble(c, Y, Ya);
 }
 
+// The two calls for a Richards context WITH conductivity factors refuse, in this order: any other
+// model, a class map, a context whose factors are both NoEffect (`plain` serves it, as the layered calls send a context
+// without a map to the scalar call), a prescribed atmosphere, and what stepping_preamble refuses
+static int factors_implicit_refusals(lh_ctx* c, const char* who, const char* plain, const lh_state* Y, const lh_state* Ya) {
+    if (c->cfg.model != LH_MODEL_RICHARDS) return fail(c, LH_EMODEL, "%s: %s", who, RICHARDS_MODELS);
+    if (int rc = layered_unsupported(c, who)) return rc;
+    if (c->hp.viscosity_kind == LH_FACTOR_NONE && c->hp.impedance_kind == LH_FACTOR_NONE)
+        return fail(c, LH_EMODEL, "%s: the context has no conductivity factor other than NoEffect (lh_set_conductivity_factors); "
+                                  "%s steps a model without conductivity factors", who, plain);
+    if (c->hp.atmos_on) return fail(c, LH_EMODEL, "%s: a prescribed-atmosphere top is not supported", who);
+    return stepping_preamble(c, Y, Ya);
+}
+
 // ---- adaptive SSPRK33 for layered Richards soils: the BOUND flavour of the layered column
 // stepper is their one engine, so they do not consult `persist` -- that key chooses where there are two engines
 
@@ -2414,17 +2428,37 @@ static int launch_status(lh_ctx* c, hipError_t e, const char* launch) {
     return e == hipSuccess ? LH_OK : fail(c, LH_ENODEVICE, "%s launch failed: %s", launch, hipGetErrorString(e));
 }
 
-// The two Richards calls exist twice, for contexts without and with a class map (lh_implicit.hpp,
-// lh_layered_implicit.hpp), on the same scratch and statistics blocks.  One body each; what a
+// The two Richards calls exist three times, for contexts without and with a class map (lh_implicit.hpp,
+// lh_layered_implicit.hpp) and for contexts with conductivity factors (lh_factors_implicit.hpp;
+// DESIGN section 4.32), on the same scratch and statistics blocks.  One body each; what a
 // layered entry point words or does differently is its flavour: besides the names below, implicit_refusals' list for
-// a context that must hold a map, layered_params, and the launcher that takes layered_args.
+// a context that must hold a map, layered_params, and the launcher that takes layered_args.  The factors flavour has
+// its own refusals (factors_implicit_refusals), hands the kernels Ya's prescribed T (factors_temperature) and takes
+// lh_factors_implicit.hpp's launchers.
 struct RichardsFlavour {
     const char* who;    // the entry point, for lh_last_error
     const char* scalar; // a layered call: the call for a context without a class map; NULL for that call itself
     const char* range;  // the roctx range
     const char* launch; // the launch, in the words of its failure message
+    const char* plain = nullptr; // a factors call: the call for a context whose factors are both NoEffect
     bool layered() const { return scalar != nullptr; }
+    bool factors() const { return plain != nullptr; }
 };
+static int richards_refusals(lh_ctx* c, const RichardsFlavour& fl, const lh_state* Y, const lh_state* Ya) {
+    if (fl.factors()) return factors_implicit_refusals(c, fl.who, fl.plain, Y, Ya);
+    return implicit_refusals(c, fl.who, Y, Ya, LH_MODEL_RICHARDS, RICHARDS_MODELS, fl.scalar);
+}
+// The prescribed T a factors launch reads: Ya's planes made current but for a T that comes as a level-uniform profile
+// (which goes to the kernel as it is, set_aux_profiles); nothing where no viscosity factor reads a temperature
+static int factors_temperature(lh_ctx* c, const lh_state* Ya) {
+    if (c->hp.viscosity_kind == LH_FACTOR_NONE) return LH_OK;
+    return materialize(c, Ya, ~aux_profile_vars(c, Ya));
+}
+// ... and its plane: NULL where a profile stands for it (set_aux_profiles hands that over) or nothing reads it
+static const void* factors_temperature_plane(const lh_ctx* c, const lh_state* Ya) {
+    if (c->hp.viscosity_kind == LH_FACTOR_NONE || (aux_profile_vars(c, Ya) & LH_MASK(LH_VAR_T))) return nullptr;
+    return Ya->plane[LH_VAR_T];
+}
 
 static int richards_implicit_euler(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, const lh_state* Ya, double dt,
                                    int64_t nsteps, const double* bcv, double tol, int32_t max_iter) {
@@ -2433,13 +2467,14 @@ static int richards_implicit_euler(lh_ctx* c, const RichardsFlavour& fl, lh_stat
     if (rc) return rc;
     if (nsteps < 0 || !(dt > 0)) return fail(c, LH_EINVAL, "%s: need nsteps >= 0 and dt > 0", fl.who);
     Range r_(fl.range);
-    if ((rc = implicit_refusals(c, fl.who, Y, Ya, LH_MODEL_RICHARDS, RICHARDS_MODELS, fl.scalar))) return rc;
+    if ((rc = richards_refusals(c, fl, Y, Ya))) return rc;
     newton_defaults(c, tol, max_iter);
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
     if ((rc = ensure_scratch(c, &c->d_imp, 3 * pl * c->esize, "c->d_imp", "3 * plane"))) return rc;
     if ((rc = ensure_scratch(c, &c->d_imp_stats, sizeof(ImplicitStats), "c->d_imp_stats", "24", true))) return rc;
     if (nsteps == 0) return LH_OK;
     if ((rc = materialize(c, Y, ~0u))) return rc;
+    if (fl.factors() && (rc = factors_temperature(c, Ya))) return rc;
     DeviceBuffer d_bcv; // [nsteps][2][2] doubles -> FT on the device
     if (bcv && (rc = upload_boundary_values(c, bcv, size_t(nsteps) * 4, d_bcv))) return rc;
     with_ft(c, [&](auto ft) {
@@ -2455,7 +2490,11 @@ static int richards_implicit_euler(lh_ctx* c, const RichardsFlavour& fl, lh_stat
         A.max_iter = max_iter;
         A.nsteps = nsteps;
         point_at_newton_stats(c, A);
-        if (fl.layered()) launch_layered_implicit_euler<FT>(P, layered_args<FT>(c), A, implicit_noice(c, Y), c->stream);
+        if (fl.factors()) {
+            set_aux_profiles<FT>(c, Ya, P);
+            launch_factors_implicit_euler<FT>(P, A, static_cast<const FT*>(factors_temperature_plane(c, Ya)), any_percol(c), c->math,
+                                              c->stream);
+        } else if (fl.layered()) launch_layered_implicit_euler<FT>(P, layered_args<FT>(c), A, implicit_noice(c, Y), c->stream);
         else launch_implicit_euler<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
@@ -2474,6 +2513,14 @@ int lh_step_layered_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, d
     (void)t; // as for lh_step_implicit_euler
     static const RichardsFlavour fl = {"lh_step_layered_implicit_euler", "lh_step_implicit_euler",
                                        "lh:step_layered_implicit_euler", "layered implicit Euler"};
+    return richards_implicit_euler(c, fl, Y, Ya, dt, nsteps, bcv, tol, max_iter);
+}
+
+int lh_step_factors_implicit_euler(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                                   const double* bcv, double tol, int32_t max_iter) {
+    (void)t; // as for lh_step_implicit_euler
+    static const RichardsFlavour fl = {"lh_step_factors_implicit_euler", nullptr, "lh:step_factors_implicit_euler",
+                                       "factors implicit Euler", "lh_step_implicit_euler"};
     return richards_implicit_euler(c, fl, Y, Ya, dt, nsteps, bcv, tol, max_iter);
 }
 
@@ -2523,7 +2570,7 @@ static int richards_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, co
     if (rc) return rc;
     if ((rc = trbdf2_argument_refusals(c, fl.who, t0, t1, dt, {abstol, reltol}, flags, LH_TRBDF2_FIXED, bcv))) return rc;
     Range r_(fl.range);
-    if ((rc = implicit_refusals(c, fl.who, Y, Ya, LH_MODEL_RICHARDS, RICHARDS_MODELS, fl.scalar))) return rc;
+    if ((rc = richards_refusals(c, fl, Y, Ya))) return rc;
     trbdf2_tolerance_defaults(abstol, reltol);
     double tol = 0; // (fixed mode: lh_step_implicit_euler's defaults)
     int32_t max_iter = 0;
@@ -2533,6 +2580,7 @@ static int richards_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, co
     if ((rc = ensure_scratch(c, &c->d_tr_stats, TRBDF2_STATS_BYTES, "c->d_tr_stats", "nstat", true))) return rc;
     if (t1 == t0) return LH_OK;
     if ((rc = materialize(c, Y, ~0u))) return rc;
+    if (fl.factors() && (rc = factors_temperature(c, Ya))) return rc;
     with_ft(c, [&](auto ft) {
         using FT = decltype(ft);
         DevParams<FT> P = make_params<FT>(c);
@@ -2544,7 +2592,10 @@ static int richards_trbdf2(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, co
         A.fixed = (flags & LH_TRBDF2_FIXED) != 0;
         A.tol = FT(tol);
         A.max_iter = max_iter;
-        if (fl.layered()) launch_layered_trbdf2<FT>(P, layered_args<FT>(c), A, implicit_noice(c, Y), c->stream);
+        if (fl.factors()) {
+            set_aux_profiles<FT>(c, Ya, P);
+            launch_factors_trbdf2<FT>(P, A, static_cast<const FT*>(factors_temperature_plane(c, Ya)), any_percol(c), c->math, c->stream);
+        } else if (fl.layered()) launch_layered_trbdf2<FT>(P, layered_args<FT>(c), A, implicit_noice(c, Y), c->stream);
         else launch_trbdf2<FT>(P, A, any_percol(c), implicit_noice(c, Y), c->math, c->stream);
     });
     mark_written(Y, LH_MASK(LH_VAR_VARTHETA_L));
@@ -2561,6 +2612,13 @@ int lh_integrate_layered_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, doub
                                 double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
     static const RichardsFlavour fl = {"lh_integrate_layered_trbdf2", "lh_integrate_trbdf2", "lh:integrate_layered_trbdf2",
                                        "layered TR-BDF2"};
+    return richards_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol, reltol, flags, dt_cols_device_ft, bcv);
+}
+
+int lh_integrate_factors_trbdf2(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t0, double t1, double dt, double abstol,
+                                double reltol, uint32_t flags, void* dt_cols_device_ft, const double* bcv) {
+    static const RichardsFlavour fl = {"lh_integrate_factors_trbdf2", nullptr, "lh:integrate_factors_trbdf2", "factors TR-BDF2",
+                                       "lh_integrate_trbdf2"};
     return richards_trbdf2(c, fl, Y, Ya, t0, t1, dt, abstol, reltol, flags, dt_cols_device_ft, bcv);
 }
 

@@ -617,6 +617,54 @@ function integrate_layered_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, 
 end
 
 """
+    step_factors_implicit_euler!(ens, Y, Ya, t, dt, nsteps; bcv = nothing, tol = 0.0, max_iter = 0) -> (max_iters, unconverged, iterations)
+
+`step_implicit_euler!` for a Richards ensemble with a conductivity factor other than NoEffect
+(the model's `viscosity_factor` / `impedance_factor`; lh_step_factors_implicit_euler): the factors in the tendency, their slope in
+the Jacobian.  The prescribed T is the one `Ya` holds, held through the call.  Arguments and return value
+as `step_implicit_euler!`.
+"""
+function step_factors_implicit_euler!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt, nsteps;
+                                      bcv = nothing, tol = 0.0, max_iter = 0)
+    set_bcs!(ens, t)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    check(ens.ctx, ccall((:lh_step_factors_implicit_euler, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Int64, Ptr{Float64}, Float64, Int32),
+                         ens.ctx, Y.handle, ya, t, dt, nsteps, vals, tol, max_iter))
+    mi = Ref{Int32}(0)
+    nu = Ref{Int64}(0)
+    check(ens.ctx, ccall((:lh_implicit_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}),
+                         ens.ctx, mi, nu))
+    total = Ref{Int64}(0)
+    check(ens.ctx, ccall((:lh_implicit_iterations, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, total))
+    return (mi[], nu[], total[])
+end
+
+"""
+    integrate_factors_trbdf2!(ens, Y, Ya, t0, t1, dt; abstol = 0.0, reltol = 0.0, adaptive = true,
+                              dt_cols = C_NULL, bcv = nothing) -> stats
+
+`integrate_trbdf2!` for a Richards ensemble with a conductivity factor other than NoEffect
+(lh_integrate_factors_trbdf2).
+Arguments and return value as `integrate_trbdf2!`.
+"""
+function integrate_factors_trbdf2!(ens::ColumnEnsemble, Y::DeviceState, Ya, t0, t1, dt; abstol = 0.0, reltol = 0.0,
+                                   adaptive = true, dt_cols = C_NULL, bcv = nothing)
+    set_bcs!(ens, t0)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    flags = adaptive ? UInt32(0) : UInt32(1)
+    check(ens.ctx, ccall((:lh_integrate_factors_trbdf2, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, UInt32,
+                          Ptr{Cvoid}, Ptr{Float64}),
+                         ens.ctx, Y.handle, ya, t0, t1, dt, abstol, reltol, flags, dt_cols, vals))
+    stats = zeros(Int64, 7)
+    check(ens.ctx, ccall((:lh_trbdf2_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, stats))
+    return stats
+end
+
+"""
     step_heat_implicit!(ens, Y, Ya, t, dt, nsteps; method = :euler, bcv = nothing)
 
 `nsteps` implicit steps of a heat-only ensemble, SoilEnergyModel + PrescribedHydrologyModel

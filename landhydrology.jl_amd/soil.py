@@ -1167,6 +1167,7 @@ class _Scope:
     no_classes: str                # a layered call on a model without soil classes ({scalar}: the call that serves it)
     factors: Optional[str] = None  # conductivity factors other than NoEffect (None: not refused)
     atmos: Optional[str] = None    # a prescribed-atmosphere top (None: not refused)
+    no_factors: Optional[str] = None  # a factors call on a model whose factors are both NoEffect (None: not refused)
 
 
 _RICHARDS = _Scope(      # lh_step_[layered_]implicit_euler, lh_integrate_[layered_]trbdf2
@@ -1175,6 +1176,10 @@ _RICHARDS = _Scope(      # lh_step_[layered_]implicit_euler, lh_integrate_[layer
     "{name} is provided for models with soil_classes (without them: ImplicitEuler, TRBDF2)",
     "{name} supports the NoEffect conductivity factors only",
     "{name} does not support a prescribed-atmosphere top")
+_RICHARDS_FACTORS = _Scope(   # lh_step_factors_implicit_euler, lh_integrate_factors_trbdf2
+    PrescribedTemperatureModel, SoilHydrologyModel,
+    _RICHARDS.pair, _RICHARDS.no_classes, None, _RICHARDS.atmos,
+    "{name} is provided for models with a conductivity factor other than NoEffect (without one: ImplicitEuler, TRBDF2)")
 _HEAT_FIXED = _Scope(    # lh_step_[layered_]heat_implicit
     SoilEnergyModel, PrescribedHydrologyModel,
     "{name} is provided for heat-only models only (SoilEnergyModel + PrescribedHydrologyModel)",
@@ -1194,7 +1199,8 @@ _COUPLED = _Scope(       # lh_step_[layered_]coupled_implicit, lh_integrate_[lay
 
 def _check_scope(model, name, scope, layered=False, scalar=None):
     """NotImplementedError for what the library calls of `scope` refuse with LH_EMODEL, in their order: the model
-    pair, the class map (layered: its absence), conductivity factors, an atmosphere top."""
+    pair, the class map (layered: its absence), conductivity factors (a factors call: their absence), an atmosphere
+    top."""
     if not (isinstance(model.energy_model, scope.energy) and isinstance(model.hydrology_model, scope.hydrology)):
         raise NotImplementedError(scope.pair.format(name=name))
     if not layered:
@@ -1202,6 +1208,8 @@ def _check_scope(model, name, scope, layered=False, scalar=None):
     elif getattr(model, "soil_classes", None) is None:
         raise NotImplementedError(scope.no_classes.format(name=name, scalar=scalar))
     hm, bcs = model.hydrology_model, model.boundary_conditions
+    if scope.no_factors and isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect):
+        raise NotImplementedError(scope.no_factors.format(name=name))
     if scope.factors and not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
         raise NotImplementedError(scope.factors.format(name=name))
     if scope.atmos and bcs is not None and isinstance(bcs.top, PrescribedAtmosForcing):
@@ -1313,6 +1321,41 @@ class LayeredTRBDF2(TRBDF2):
     """TRBDF2 for a Richards model with soil_classes (lh_integrate_layered_trbdf2): the same stages, error
     estimate and per-column controller over LayeredImplicitEuler's Newton."""
     _layered = True
+
+
+class FactorsImplicitEuler(ImplicitEuler):
+    """ImplicitEuler for a Richards model whose hydrology has a conductivity factor other than NoEffect
+    (TemperatureDependentViscosity and / or IceImpedance; lh_step_factors_implicit_euler): the same Newton, with the
+    factors in the tendency and their slope in the Jacobian.  A model with soil_classes, one whose factors are both
+    NoEffect (ImplicitEuler serves it) and a prescribed-atmosphere top are refused.  Simulation refreshes the
+    prescribed profiles between library calls and a call holds them: with a time-dependent T_profile the viscosity
+    factor is piecewise constant over a saveat chunk (over the run without saveat)."""
+    _scope = _RICHARDS_FACTORS
+
+    def advance(self, sim, nsteps):
+        it = sim.integrator
+        _refresh_prescribed(sim.model, it.p, it.t)   # (held through the chunk)
+        step_implicit_factors(sim.model, it.u, it.p, it.t, it.dt, nsteps, self.tol, self.max_iter)
+
+
+class FactorsTRBDF2(TRBDF2):
+    """TRBDF2 for a Richards model whose hydrology has a conductivity factor other than NoEffect
+    (lh_integrate_factors_trbdf2): the same stages, error estimate and per-column controller over
+    FactorsImplicitEuler's Newton; scope as FactorsImplicitEuler.  No forcing: boundary-value series do not take
+    these models.  Simulation refreshes the prescribed profiles at the start of every saveat chunk and the chunk
+    holds them: with a time-dependent T_profile the viscosity factor is piecewise constant over a saveat chunk."""
+    _scope = _RICHARDS_FACTORS
+
+    def __init__(self, abstol=None, reltol=None, adaptive=True):
+        super().__init__(abstol, reltol, adaptive)
+
+    def advance(self, sim, nsteps):
+        it = sim.integrator
+        _refresh_prescribed(sim.model, it.p, it.t)   # (held through the chunk)
+        return _advance_trbdf2(sim, _chunk_end(it, nsteps))
+
+    def integrate(self, model, Y, Ya, t0, t1, dt, dt_cols):
+        return integrate_factors_trbdf2(model, Y, Ya, t0, t1, dt, self.abstol, self.reltol, self.adaptive, dt_cols)
 
 
 class HeatImplicitEuler:
@@ -1526,6 +1569,7 @@ class _FixedStep:
 
 _STEP_IMPLICIT = _FixedStep("lh_step_implicit_euler", ("ImplicitEuler", _RICHARDS), None, True)
 _STEP_IMPLICIT_LAYERED = _FixedStep("lh_step_layered_implicit_euler", ("LayeredImplicitEuler", _RICHARDS, True), None, True)
+_STEP_IMPLICIT_FACTORS = _FixedStep("lh_step_factors_implicit_euler", ("FactorsImplicitEuler", _RICHARDS_FACTORS), None, True)
 _STEP_HEAT = _FixedStep("lh_step_heat_implicit", ("step_implicit_heat", _HEAT_FIXED), F.LH_HEAT_TRBDF2, False)
 _STEP_HEAT_LAYERED = _FixedStep("lh_step_layered_heat_implicit", ("step_implicit_layered_heat", _HEAT_FIXED, True),
                                 F.LH_HEAT_TRBDF2, False)
@@ -1631,6 +1675,14 @@ def step_implicit_layered(model: SoilModel, Y: "FieldVector", Ya=None, t: float 
     return _step_fixed(_STEP_IMPLICIT_LAYERED, model, Y, Ya, t, dt, nsteps, None, tol, max_iter)
 
 
+def step_implicit_factors(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0, nsteps: int = 1,
+                          tol=None, max_iter=None):
+    """Build extension: step_implicit for a Richards model with a conductivity factor other than NoEffect
+    (lh_step_factors_implicit_euler); arguments and return value as step_implicit.  The prescribed T is the one `Ya`
+    holds: it is held at these values through the call."""
+    return _step_fixed(_STEP_IMPLICIT_FACTORS, model, Y, Ya, t, dt, nsteps, None, tol, max_iter)
+
+
 TRBDF2_ABSTOL, TRBDF2_RELTOL = 1e-6, 1e-3   # OrdinaryDiffEq's defaults (the library's for a 0)
 
 
@@ -1667,6 +1719,7 @@ class _Adaptive:
 
 _INTEGRATE = _Adaptive("lh_integrate_trbdf2", "richards", ("TRBDF2", _RICHARDS))
 _INTEGRATE_LAYERED = _Adaptive("lh_integrate_layered_trbdf2", "richards", ("LayeredTRBDF2", _RICHARDS, True))
+_INTEGRATE_FACTORS = _Adaptive("lh_integrate_factors_trbdf2", "richards", ("FactorsTRBDF2", _RICHARDS_FACTORS))
 _INTEGRATE_COUPLED = _Adaptive("lh_integrate_coupled_trbdf2", "coupled", ("CoupledAdaptiveTRBDF2", _COUPLED))
 _INTEGRATE_COUPLED_LAYERED = _Adaptive("lh_integrate_layered_coupled_trbdf2", "coupled",
                                        ("LayeredCoupledAdaptiveTRBDF2", _COUPLED, True, "lh_integrate_coupled_trbdf2"))
@@ -1735,6 +1788,14 @@ def integrate_layered_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: fl
     """Build extension: integrate_trbdf2 for a Richards model with soil_classes (lh_integrate_layered_trbdf2);
     arguments and return value as integrate_trbdf2."""
     return _integrate(_INTEGRATE_LAYERED, model, Y, Ya, t0, t1, dt, abstol, None, reltol, adaptive, dt_cols)
+
+
+def integrate_factors_trbdf2(model: SoilModel, Y: "FieldVector", Ya=None, t0: float = 0.0, t1: float = 1.0,
+                             dt: float = 1.0, abstol=None, reltol=None, adaptive=True, dt_cols=None):
+    """Build extension: integrate_trbdf2 for a Richards model with a conductivity factor other than NoEffect
+    (lh_integrate_factors_trbdf2); arguments and return value as integrate_trbdf2.  The prescribed T is the one `Ya`
+    holds: it is held at these values through the call."""
+    return _integrate(_INTEGRATE_FACTORS, model, Y, Ya, t0, t1, dt, abstol, None, reltol, adaptive, dt_cols)
 
 
 def _dt_cols_pointer(model, dt_cols):
