@@ -681,6 +681,26 @@ int lh_step_layered_coupled_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, d
                                      int64_t nsteps, uint32_t flags, const double* bcv, double tol,
                                      int32_t max_iter);
 
+/* lh_step_coupled_implicit for a coupled context whose hydrology has the IceImpedance factor and no
+ * viscosity factor (lh_set_conductivity_factors): the same arguments, flags
+ * (0 or LH_COUPLED_TRBDF2), bcv layout and sampling, tol / max_iter defaults, status bits 0 and 3,
+ * lh_implicit_stats / lh_implicit_iterations, scratch planes and asynchrony.  theta_i is constant and no
+ * closure of the water reads T, so the water tendency still does not read rhoe_int and the energy
+ * tendency is still affine in it: the impedance scales K, in the water's fluxes and in the advected
+ * energy, and the stage Jacobian stays block lower-triangular.  The water stage is
+ * lh_step_factors_implicit_euler's Newton (vartheta_l after a backward-Euler step is bitwise that call's
+ * on a Richards context with the same hydrology, ice and factor); the energy stage is one tridiagonal
+ * solve at the new water state, matrix and right-hand side formed with the same K: f is lh_rhs's
+ * tendency of the same context.  Per-column parameter arrays and LH_MATH_LIBM are served as the plain
+ * call serves them.
+ * LH_EINVAL as lh_step_coupled_implicit, checked first.  Then LH_EMODEL, in this order: any model but
+ * LH_MODEL_COUPLED, a class map, a viscosity factor other than NoEffect (the water then reads the unknown
+ * T and the stage is no longer block triangular), a context without the impedance factor
+ * (lh_step_coupled_implicit steps it), a prescribed-atmosphere top.  nsteps == 0 does nothing. */
+int lh_step_coupled_factors_implicit(lh_ctx*, lh_state* Y, const lh_state* Ya, double t, double dt,
+                                     int64_t nsteps, uint32_t flags, const double* bcv, double tol,
+                                     int32_t max_iter);
+
 /* TR-BDF2 of the coupled model from t0 to t1 with per-column error control:
  * lh_integrate_trbdf2's method and controller over both components, every stage solved as
  * lh_step_coupled_implicit solves it (the water by the safeguarded Newton with lh_integrate_trbdf2's

@@ -9,7 +9,8 @@ this package is the host-side mirror of the reference's Julia interface.
 from . import _ffi, case_model, parameterizations, partition, workloads
 from ._ffi import LandHydroError, ModelError
 from .parameterizations import *  # noqa: F401,F403
-from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplicitEuler, CoupledTRBDF2, Dirichlet,
+from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledFactorsImplicitEuler, CoupledFactorsTRBDF2,
+                   CoupledImplicitEuler, CoupledTRBDF2, Dirichlet,
                    EarthParameterSet, FactorsImplicitEuler, FactorsTRBDF2, FieldVector, Float32, Float64, FreeDrainage, HeatAdaptiveTRBDF2, HeatImplicitEuler,
                    HeatSeriesTRBDF2, HeatTRBDF2, IceImpedance, ImplicitEuler, LayeredCoupledAdaptiveTRBDF2,
                    LayeredCoupledImplicitEuler, LayeredCoupledSeriesTRBDF2, LayeredCoupledTRBDF2,
@@ -26,7 +27,7 @@ from .soil import (BoundarySeries, Column, CoupledAdaptiveTRBDF2, CoupledImplici
                    integrate_layered_coupled_trbdf2, integrate_layered_heat_trbdf2, integrate_layered_trbdf2, integrate_series, integrate_trbdf2,
                    make_function_space, make_rhs, make_update_aux, run, set_tuning, stable_dt, step, step_adaptive,
                    step_engine, step_implicit, step_series, step_series_engine,
-                   step_implicit_coupled, step_implicit_factors, step_implicit_heat, step_implicit_layered, step_implicit_layered_coupled,
+                   step_implicit_coupled, step_implicit_coupled_factors, step_implicit_factors, step_implicit_heat, step_implicit_layered, step_implicit_layered_coupled,
                    step_implicit_layered_heat,
                    tune_placement, vanGenuchten)
 

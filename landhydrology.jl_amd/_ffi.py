@@ -176,6 +176,8 @@ SIGNATURES = {
                                            C.POINTER(C.c_double), C.c_double, C.c_int32]),
     "lh_step_layered_coupled_implicit": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, C.c_uint32,
                                                    C.POINTER(C.c_double), C.c_double, C.c_int32]),
+    "lh_step_coupled_factors_implicit": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_int64, C.c_uint32,
+                                                   C.POINTER(C.c_double), C.c_double, C.c_int32]),
     "lh_tune_placement": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_uint32, C.POINTER(C.c_float),
                                     C.POINTER(C.c_float)]),
     "lh_stable_dt": (C.c_int, [_P, _P, _P, C.c_double, _DP]),

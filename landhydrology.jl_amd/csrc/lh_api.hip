@@ -6,6 +6,7 @@
 #include "lh_layered.hpp"
 #include "lh_layered_implicit.hpp"
 #include "lh_factors_implicit.hpp"
+#include "lh_coupled_factors_implicit.hpp"
 #include "lh_layered_heat.hpp"
 #include "lh_layered_heat_implicit.hpp"
 #include "lh_layered_heat_trbdf2.hpp"
@@ -2296,6 +2297,22 @@ static int factors_implicit_refusals(lh_ctx* c, const char* who, const char* pla
     return stepping_preamble(c, Y, Ya);
 }
 
+// The call for a coupled context WITH the impedance factor refuses, in this order: any other model,
+// a class map, a viscosity factor (the water would read the unknown T), a context without the impedance factor (`plain`
+// serves it), a prescribed atmosphere, and what stepping_preamble refuses
+static int coupled_factors_implicit_refusals(lh_ctx* c, const char* who, const char* plain, const lh_state* Y, const lh_state* Ya) {
+    if (c->cfg.model != LH_MODEL_COUPLED) return fail(c, LH_EMODEL, "%s: %s", who, COUPLED_MODELS);
+    if (int rc = layered_unsupported(c, who)) return rc;
+    if (c->hp.viscosity_kind != LH_FACTOR_NONE)
+        return fail(c, LH_EMODEL, "%s: a viscosity factor other than NoEffect is not supported: the water then reads the unknown T "
+                                  "and the stage is no longer block triangular", who);
+    if (c->hp.impedance_kind == LH_FACTOR_NONE)
+        return fail(c, LH_EMODEL, "%s: the context has no impedance factor (lh_set_conductivity_factors); "
+                                  "%s steps a model without conductivity factors", who, plain);
+    if (c->hp.atmos_on) return fail(c, LH_EMODEL, "%s: a prescribed-atmosphere top is not supported", who);
+    return stepping_preamble(c, Y, Ya);
+}
+
 // ---- adaptive SSPRK33 for layered Richards soils: the BOUND flavour of the layered column
 // stepper is their one engine, so they do not consult `persist` -- that key chooses where there are two engines
 
@@ -2697,11 +2714,13 @@ int lh_step_layered_heat_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, do
     return heat_implicit_steps(c, fl, Y, Ya, dt, nsteps, flags, bcv);
 }
 
-// The coupled call exists twice, for contexts without and with a class map (lh_coupled_implicit.hpp,
-// lh_layered_coupled_implicit.hpp), on the same scratch planes, statistics block and table of
+// The coupled call exists three times, for contexts without and with a class map (lh_coupled_implicit.hpp,
+// lh_layered_coupled_implicit.hpp) and for contexts with the impedance factor
+// (lh_coupled_factors_implicit.hpp), on the same scratch planes, statistics block and table of
 // boundary values.  One body; what the layered entry point words or does differently is its flavour (a RichardsFlavour:
 // the fields are the same): implicit_refusals' list for a context that must hold a map, layered_params, and the launcher
-// that takes layered_heat_args.
+// that takes layered_heat_args.  The factors flavour has its own refusals (coupled_factors_implicit_refusals) and its
+// own launcher, which has no NOICE variant.
 static int coupled_implicit_steps(lh_ctx* c, const RichardsFlavour& fl, lh_state* Y, const lh_state* Ya, double dt,
                                   int64_t nsteps, uint32_t flags, const double* bcv, double tol, int32_t max_iter) {
     if (!c) return LH_EINVAL;
@@ -2711,7 +2730,9 @@ static int coupled_implicit_steps(lh_ctx* c, const RichardsFlavour& fl, lh_state
     if ((rc = fixed_step_argument_refusals(c, who, nsteps, dt, flags, LH_COUPLED_TRBDF2))) return rc;
     Range r_(fl.range);
     // (with a viscosity factor the water reads T: the Jacobian is no longer block triangular)
-    if ((rc = implicit_refusals(c, who, Y, Ya, LH_MODEL_COUPLED, COUPLED_MODELS, fl.scalar))) return rc;
+    if ((rc = fl.factors() ? coupled_factors_implicit_refusals(c, who, fl.plain, Y, Ya)
+                           : implicit_refusals(c, who, Y, Ya, LH_MODEL_COUPLED, COUPLED_MODELS, fl.scalar)))
+        return rc;
     newton_defaults(c, tol, max_iter);
     const bool trbdf2 = (flags & LH_COUPLED_TRBDF2) != 0;
     const size_t pl = size_t(c->cfg.nlev) * size_t(c->stride);
@@ -2738,7 +2759,9 @@ static int coupled_implicit_steps(lh_ctx* c, const RichardsFlavour& fl, lh_state
         A.max_iter = max_iter;
         A.nsteps = nsteps;
         point_at_newton_stats(c, A);
-        if (fl.layered())
+        if (fl.factors())
+            launch_coupled_factors_implicit<FT>(P, A, any_percol(c), trbdf2, c->math, c->stream);
+        else if (fl.layered())
             launch_layered_coupled_implicit<FT>(P, layered_heat_args<FT>(c), A, implicit_noice(c, Y), trbdf2, c->stream);
         else
             launch_coupled_implicit<FT>(P, A, any_percol(c), implicit_noice(c, Y), trbdf2, c->math, c->stream);
@@ -2759,6 +2782,14 @@ int lh_step_layered_coupled_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya,
     (void)t; // as for lh_step_coupled_implicit
     static const RichardsFlavour fl = {"lh_step_layered_coupled_implicit", "lh_step_coupled_implicit",
                                       "lh:step_layered_coupled_implicit", "layered coupled implicit"};
+    return coupled_implicit_steps(c, fl, Y, Ya, dt, nsteps, flags, bcv, tol, max_iter);
+}
+
+int lh_step_coupled_factors_implicit(lh_ctx* c, lh_state* Y, const lh_state* Ya, double t, double dt, int64_t nsteps,
+                                     uint32_t flags, const double* bcv, double tol, int32_t max_iter) {
+    (void)t; // as for lh_step_coupled_implicit
+    static const RichardsFlavour fl = {"lh_step_coupled_factors_implicit", nullptr, "lh:step_coupled_factors_implicit",
+                                       "coupled factors implicit", "lh_step_coupled_implicit"};
     return coupled_implicit_steps(c, fl, Y, Ya, dt, nsteps, flags, bcv, tol, max_iter);
 }
 

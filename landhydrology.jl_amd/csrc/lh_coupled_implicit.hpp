@@ -33,12 +33,36 @@
 
 namespace lh {
 
+// The water stage of a context with the impedance factor (coupled_implicit_column<FACTORS = true>): defined in
+// lh_factors_implicit.hpp, which lh_coupled_factors_implicit.hpp includes before this header; declared here so that
+// the one stage sequence below can name them.  No other translation unit instantiates that branch.
+template <typename FT>
+struct PrescribedT;
+template <typename FT, typename M, bool PERCOL, bool VGF>
+__device__ __forceinline__ void factors_face_states(const M& mm, const DevParams<FT>& P,
+                                                    const ColumnSolve<FT, M, PERCOL, false>& S, int64_t col, FT ti_b,
+                                                    FT ti_t, FT T_b, FT T_t, FaceState<FT>& fsb, FaceState<FT>& fst);
+template <typename FT, typename M, bool PERCOL, bool VGF, bool WFIRST, bool ADAPT>
+__device__ __forceinline__ int factors_newton_stage(const M& mm, const DevParams<FT>& P,
+                                                    const ColumnSolve<FT, M, PERCOL, false>& S, const FaceState<FT>& fsb,
+                                                    const FaceState<FT>& fst, int64_t col, FT* y, const FT* ti,
+                                                    const PrescribedT<FT>& Tp, FT* w, FT* cp, FT* dp, FT coef, FT tol,
+                                                    FT atol, FT rtol, int max_iter, bool& conv, bool& nonfinite, FT kappa);
+template <typename FT, typename M, bool PERCOL, bool VGF, bool JAC, typename Row>
+__device__ __forceinline__ void factors_sweep_up(const M& mm, const DevParams<FT>& P,
+                                                 const ColumnSolve<FT, M, PERCOL, false>& S, const FaceState<FT>& fsb,
+                                                 const FaceState<FT>& fst, int64_t col, const FT* y, const FT* ti,
+                                                 const PrescribedT<FT>& Tp, FT coef, FT* cp, FT* dp, Row&& row);
+
 // One upward sweep of the energy equation over a column at the water state y (a rolling window of two
 // cells' closures).  SOLVE: row i of the stage matrix and r_i = in(i, idx) + coef f_e,i(T = beta), eliminated
 // forward; cp, dp receive the back substitution's Y_i = dp_i + cp_i Y_i+1.  Otherwise in(i, idx) is rhoe_int
 // and out(idx, f_e,i) receives the tendency.  SOLVE with HOMOG: the same matrix against r_i = in(i, idx) alone (no
-// tendency at T = beta, no boundary offset): the error filter of lh_coupled_trbdf2.hpp.
-template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool SOLVE, bool HOMOG = false, typename In, typename Out>
+// tendency at T = beta, no boundary offset): the error filter of lh_coupled_trbdf2.hpp.  FACTORS: K with the
+// conductivity factors (the impedance; no viscosity, so no closure reads T), in the matrix's advective entries and
+// in the right-hand side alike (lh_coupled_factors_implicit.hpp).
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool SOLVE, bool HOMOG = false, bool FACTORS = false,
+          typename In, typename Out>
 __device__ __forceinline__ void energy_sweep_up(const M& mm, const DevParams<FT>& P,
                                                 const ColumnSolve<FT, M, PERCOL, NOICE>& S, const FaceState<FT>& fsb,
                                                 const FaceState<FT>& fst, int64_t col, const FT* y, const FT* ti,
@@ -54,7 +78,7 @@ __device__ __forceinline__ void energy_sweep_up(const M& mm, const DevParams<FT>
         const FT v = y[id];
         const FT tiv = NOICE ? FT(0) : ti[id];
         nf_acc = fma_ft(v, FT(0), nf_acc);
-        water_closures<FT, M, false, true, false, NOICE, RELK, false, true>(mm, P, c, v, tiv, FT(288), K, np, nullptr, vgf);
+        water_closures<FT, M, FACTORS, true, false, NOICE, RELK, false, true>(mm, P, c, v, tiv, FT(288), K, np, nullptr, vgf);
         be = temperature_closure<FT, M, NOICE>(mm, P, c, v, tiv, FT(0), rcs);
         al = M::is_production ? mm.rcp(rcs) : FT(1) / rcs;
         kap = kappa_closure<FT, M, NOICE>(mm, P, c, v, tiv);
@@ -131,8 +155,10 @@ __device__ __forceinline__ void energy_sweep_up(const M& mm, const DevParams<FT>
 }
 
 // One column (lane) through all steps of the call.  my_max, unconv, total: the water stages' Newton statistics;
-// nf_acc becomes NaN once a result is non-finite.
-template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool TRBDF2>
+// nf_acc becomes NaN once a result is non-finite.  FACTORS (with NOICE = false): the context has the impedance factor
+// and no viscosity factor -- the water stage is lh_factors_implicit.hpp's, K of the energy stage
+// carries the factor, and the stage sequence is this one.
+template <typename FT, typename M, bool PERCOL, bool NOICE, bool VGF, bool TRBDF2, bool FACTORS = false>
 __device__ __forceinline__ void coupled_implicit_column(const M& mm, DevParams<FT> P, const CoupledImplicitArgs<FT>& A,
                                                         int64_t col, int& my_max, unsigned long long& unconv,
                                                         unsigned long long& total, FT& nf_acc) {
@@ -141,7 +167,8 @@ __device__ __forceinline__ void coupled_implicit_column(const M& mm, DevParams<F
     const int n = P.nlev;
     const int64_t stride = P.stride;
     const int64_t top = int64_t(n - 1) * stride + col;
-    const FT T = FT(288); // (read by nothing: no conductivity factors on this path)
+    static_assert(!(FACTORS && NOICE), "the impedance factor reads theta_i: no NOICE variant");
+    const FT T = FT(288); // (read by nothing: no viscosity factor on either path)
     const FT coef = A.coef; // dt, or d dt of both TR-BDF2 stages
     FT* const y = A.y;
     FT* const e = A.e;
@@ -150,15 +177,31 @@ __device__ __forceinline__ void coupled_implicit_column(const M& mm, DevParams<F
     // the water stage Y - w - coef f_w(Y) = 0 at the boundary values P holds: newton_stage, as implicit_column
     // the Richards face states at the boundary values P holds, as implicit_column
     auto water_faces = [&](FaceState<FT>& fsb, FaceState<FT>& fst) {
-        fsb = face_state<FT, M, MODEL_RICHARDS, false, NOICE>(mm, P, S.c, FACE_BOTTOM, col, FT(0), ti_b, T, vgf);
-        fst = face_state<FT, M, MODEL_RICHARDS, false, NOICE>(mm, P, S.c, FACE_TOP, col, FT(0), ti_t, T, vgf);
+        if constexpr (FACTORS) {
+            factors_face_states<FT, M, PERCOL, VGF>(mm, P, S, col, ti_b, ti_t, T, T, fsb, fst);
+        } else {
+            fsb = face_state<FT, M, MODEL_RICHARDS, false, NOICE>(mm, P, S.c, FACE_BOTTOM, col, FT(0), ti_b, T, vgf);
+            fst = face_state<FT, M, MODEL_RICHARDS, false, NOICE>(mm, P, S.c, FACE_TOP, col, FT(0), ti_t, T, vgf);
+        }
     };
     auto water_stage = [&](auto wfirst) {
         FaceState<FT> fsb, fst;
         water_faces(fsb, fst);
         bool conv;
-        const int it = newton_stage<FT, M, PERCOL, NOICE, VGF, decltype(wfirst)::value, false>(
-            mm, P, S, fsb, fst, col, y, A.ti, ti_b, A.w, A.cp, A.dp, coef, A.tol, FT(0), FT(0), A.max_iter, conv);
+        int it;
+        if constexpr (FACTORS) {
+            // (PrescribedT::need is false: at() returns before it reads a pointer.  The plane it is given is one the
+            // kernel holds anyway, not a literal NULL: a constant null base behind `need` crashes the optimizer of
+            // ROCm 7.2's clang in SimplifyCFG.)
+            const PrescribedT<FT> Tp(P, A.ti);
+            bool nonfinite = false;
+            it = factors_newton_stage<FT, M, PERCOL, VGF, decltype(wfirst)::value, false>(
+                mm, P, S, fsb, fst, col, y, A.ti, Tp, A.w, A.cp, A.dp, coef, A.tol, FT(0), FT(0), A.max_iter, conv, nonfinite, FT(0));
+            if (nonfinite) nf_acc = FT(NAN);
+        } else {
+            it = newton_stage<FT, M, PERCOL, NOICE, VGF, decltype(wfirst)::value, false>(
+                mm, P, S, fsb, fst, col, y, A.ti, ti_b, A.w, A.cp, A.dp, coef, A.tol, FT(0), FT(0), A.max_iter, conv);
+        }
         my_max = it > my_max ? it : my_max;
         total += unsigned(it);
         if (!conv) ++unconv;
@@ -168,15 +211,15 @@ __device__ __forceinline__ void coupled_implicit_column(const M& mm, DevParams<F
     // (face_state<MODEL_COUPLED> also evaluates the water closure of a Dirichlet hydrology face, which the energy does
     // not read; face_state<MODEL_HEAT> on a hand-picked vartheta_l avoids that and cost 8-24 bytes of scratch per lane)
     auto energy_faces = [&](FaceState<FT>& fsb, FaceState<FT>& fst) {
-        fsb = face_state<FT, M, MODEL_COUPLED, false, NOICE>(mm, P, S.c, FACE_BOTTOM, col, y[col], ti_b, FT(0), vgf);
-        fst = face_state<FT, M, MODEL_COUPLED, false, NOICE>(mm, P, S.c, FACE_TOP, col, y[top], ti_t, FT(0), vgf);
+        fsb = face_state<FT, M, MODEL_COUPLED, FACTORS, NOICE>(mm, P, S.c, FACE_BOTTOM, col, y[col], ti_b, FT(0), vgf);
+        fst = face_state<FT, M, MODEL_COUPLED, FACTORS, NOICE>(mm, P, S.c, FACE_TOP, col, y[top], ti_t, FT(0), vgf);
     };
     // the energy stage Y - w - coef f_e(Y) = 0 at the water state y: w = in(i, idx), out(idx, Y_i) top down
     auto energy_stage = [&](auto&& in, auto&& out) {
         FaceState<FT> fsb, fst;
         energy_faces(fsb, fst);
-        energy_sweep_up<FT, M, PERCOL, NOICE, VGF, true>(mm, P, S, fsb, fst, col, y, A.ti, coef, A.cp, A.dp, nf_acc, in,
-                                                          [](int64_t, FT) {});
+        energy_sweep_up<FT, M, PERCOL, NOICE, VGF, true, false, FACTORS>(mm, P, S, fsb, fst, col, y, A.ti, coef, A.cp, A.dp,
+                                                                         nf_acc, in, [](int64_t, FT) {});
         FT xnext = FT(0);
         int64_t idx = top;
         for (int i = n - 1; i >= 0; --i) {
@@ -215,13 +258,18 @@ __device__ __forceinline__ void coupled_implicit_column(const M& mm, DevParams<F
             if (bv) set_stage_boundary_values(P, bv);
             FaceState<FT> fsb, fst;
             water_faces(fsb, fst);
-            column_sweep_up<FT, M, PERCOL, NOICE, VGF, false>(mm, P, S, fsb, fst, col, y, A.ti, ti_b, FT(0), nullptr, nullptr,
-                                                              [&](int64_t idx, FT, FT f) { fn[idx] = f; return FT(0); });
+            auto to_fn = [&](int64_t idx, FT, FT f) { fn[idx] = f; return FT(0); };
+            if constexpr (FACTORS)
+                factors_sweep_up<FT, M, PERCOL, VGF, false>(mm, P, S, fsb, fst, col, y, A.ti, PrescribedT<FT>(P, A.ti), FT(0),
+                                                            nullptr, nullptr, to_fn);
+            else
+                column_sweep_up<FT, M, PERCOL, NOICE, VGF, false>(mm, P, S, fsb, fst, col, y, A.ti, ti_b, FT(0), nullptr, nullptr,
+                                                                  to_fn);
             FaceState<FT> eb, et;
             energy_faces(eb, et);
-            energy_sweep_up<FT, M, PERCOL, NOICE, VGF, false>(mm, P, S, eb, et, col, y, A.ti, coef, nullptr, nullptr, nf_acc,
-                                                               [&](int, int64_t idx) { return e[idx]; },
-                                                               [&](int64_t idx, FT f) { fe[idx] = f; });
+            energy_sweep_up<FT, M, PERCOL, NOICE, VGF, false, false, FACTORS>(mm, P, S, eb, et, col, y, A.ti, coef, nullptr, nullptr,
+                                                                              nf_acc, [&](int, int64_t idx) { return e[idx]; },
+                                                                              [&](int64_t idx, FT f) { fe[idx] = f; });
         }
         for (int64_t s = 0; s < A.nsteps; ++s) {
             // stage 1: the water's Y_n and w1 (the guess is Y_n); boundary values (1 - gamma) v_k + gamma v_k+1

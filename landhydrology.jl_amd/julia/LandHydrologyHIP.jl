@@ -765,6 +765,34 @@ function step_layered_coupled_implicit!(ens::ColumnEnsemble, Y::DeviceState, Ya,
 end
 
 """
+    step_coupled_factors_implicit!(ens, Y, Ya, t, dt, nsteps; method = :euler, bcv = nothing, tol = 0.0, max_iter = 0) -> (max_iters, unconverged, iterations)
+
+`step_coupled_implicit!` for a coupled ensemble whose hydrology has the IceImpedance factor and no viscosity
+factor (lh_step_coupled_factors_implicit): the water stage by `step_factors_implicit_euler!`'s Newton, the energy
+stage by one tridiagonal solve whose advected energy carries the same `K` -- `θ_i` is constant and no closure of
+the water reads `T`, so this is still the monolithic implicit stage.  Arguments and result as
+`step_coupled_implicit!`.
+"""
+function step_coupled_factors_implicit!(ens::ColumnEnsemble, Y::DeviceState, Ya, t, dt, nsteps; method = :euler,
+                                        bcv = nothing, tol = 0.0, max_iter = 0)
+    method in (:euler, :trbdf2) || throw(ArgumentError("method must be :euler or :trbdf2"))
+    set_bcs!(ens, t)
+    ya = Ya === nothing ? C_NULL : Ya.handle
+    vals = bcv === nothing ? C_NULL : convert(Vector{Float64}, bcv)
+    flags = method === :trbdf2 ? UInt32(1) : UInt32(0)
+    check(ens.ctx, ccall((:lh_step_coupled_factors_implicit, lib), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Int64, UInt32, Ptr{Float64}, Float64, Int32),
+                         ens.ctx, Y.handle, ya, t, dt, Int64(nsteps), flags, vals, tol, max_iter))
+    mi = Ref{Int32}(0)
+    nu = Ref{Int64}(0)
+    check(ens.ctx, ccall((:lh_implicit_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}),
+                         ens.ctx, mi, nu))
+    total = Ref{Int64}(0)
+    check(ens.ctx, ccall((:lh_implicit_iterations, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ens.ctx, total))
+    return (mi[], nu[], total[])
+end
+
+"""
     integrate_coupled_trbdf2!(ens, Y, Ya, t0, t1, dt; abstol = 0.0, abstol_e = 0.0, reltol = 0.0,
                               dt_cols = C_NULL, bcv = nothing) -> stats
 

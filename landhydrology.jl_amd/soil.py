@@ -1168,6 +1168,8 @@ class _Scope:
     factors: Optional[str] = None  # conductivity factors other than NoEffect (None: not refused)
     atmos: Optional[str] = None    # a prescribed-atmosphere top (None: not refused)
     no_factors: Optional[str] = None  # a factors call on a model whose factors are both NoEffect (None: not refused)
+    viscosity: Optional[str] = None   # a viscosity factor other than NoEffect, refused on its own (None: not refused)
+    no_impedance: Optional[str] = None  # an impedance call on a model whose impedance factor is NoEffect (None: not refused)
 
 
 _RICHARDS = _Scope(      # lh_step_[layered_]implicit_euler, lh_integrate_[layered_]trbdf2
@@ -1195,12 +1197,19 @@ _COUPLED = _Scope(       # lh_step_[layered_]coupled_implicit, lh_integrate_[lay
     "{name}: the context has no class map (lh_set_soil_class_map); {scalar} steps a model without soil classes",
     "{name}: conductivity factors other than NoEffect are not supported",
     "{name}: a prescribed-atmosphere top is not supported")
+_COUPLED_FACTORS = _Scope(   # lh_step_coupled_factors_implicit
+    SoilEnergyModel, SoilHydrologyModel,
+    _COUPLED.pair, _COUPLED.no_classes, None, _COUPLED.atmos, None,
+    "{name}: a viscosity factor other than NoEffect is not supported: the water then reads the unknown T and the stage is "
+    "no longer block triangular",
+    "{name}: the context has no impedance factor (lh_set_conductivity_factors); lh_step_coupled_implicit steps a model "
+    "without conductivity factors")
 
 
 def _check_scope(model, name, scope, layered=False, scalar=None):
     """NotImplementedError for what the library calls of `scope` refuse with LH_EMODEL, in their order: the model
-    pair, the class map (layered: its absence), conductivity factors (a factors call: their absence), an atmosphere
-    top."""
+    pair, the class map (layered: its absence), conductivity factors (a factors call: their absence; an impedance
+    call: a viscosity factor, then the impedance factor's absence), an atmosphere top."""
     if not (isinstance(model.energy_model, scope.energy) and isinstance(model.hydrology_model, scope.hydrology)):
         raise NotImplementedError(scope.pair.format(name=name))
     if not layered:
@@ -1208,6 +1217,10 @@ def _check_scope(model, name, scope, layered=False, scalar=None):
     elif getattr(model, "soil_classes", None) is None:
         raise NotImplementedError(scope.no_classes.format(name=name, scalar=scalar))
     hm, bcs = model.hydrology_model, model.boundary_conditions
+    if scope.viscosity and not isinstance(hm.viscosity_factor, NoEffect):
+        raise NotImplementedError(scope.viscosity.format(name=name))
+    if scope.no_impedance and isinstance(hm.impedance_factor, NoEffect):
+        raise NotImplementedError(scope.no_impedance.format(name=name))
     if scope.no_factors and isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect):
         raise NotImplementedError(scope.no_factors.format(name=name))
     if scope.factors and not (isinstance(hm.viscosity_factor, NoEffect) and isinstance(hm.impedance_factor, NoEffect)):
@@ -1503,6 +1516,25 @@ class LayeredCoupledTRBDF2(LayeredCoupledImplicitEuler):
     method = "trbdf2"
 
 
+class CoupledFactorsImplicitEuler(CoupledImplicitEuler):
+    """CoupledImplicitEuler for a coupled model whose hydrology has the IceImpedance factor and no viscosity factor
+    (lh_step_coupled_factors_implicit): the water stage by FactorsImplicitEuler's Newton, the energy stage by one
+    tridiagonal solve whose advected energy carries the same K -- θ_i is constant and no closure of the water reads T,
+    so this is still exactly the monolithic implicit step.  A model with soil_classes, a viscosity factor, a model
+    without the impedance factor (CoupledImplicitEuler serves it) and a prescribed-atmosphere top are refused.  Calls
+    and arguments as CoupledImplicitEuler."""
+    _scope = _COUPLED_FACTORS
+
+    def step(self, model, Y, Ya, t, dt, nsteps):
+        return step_implicit_coupled_factors(model, Y, Ya, t, dt, nsteps, self.method, self.tol, self.max_iter)
+
+
+class CoupledFactorsTRBDF2(CoupledFactorsImplicitEuler):
+    """CoupledTRBDF2 for a coupled model with the IceImpedance factor (lh_step_coupled_factors_implicit with
+    LH_COUPLED_TRBDF2); scope as CoupledFactorsImplicitEuler."""
+    method = "trbdf2"
+
+
 class CoupledAdaptiveTRBDF2:
     """TR-BDF2 of the coupled model with per-column error control over both components
     (lh_integrate_coupled_trbdf2): CoupledTRBDF2's stages, TRBDF2's controller.  abstol (on ϑ_l), abstol_e (on
@@ -1560,7 +1592,7 @@ class LayeredCoupledSeriesTRBDF2(LayeredCoupledAdaptiveTRBDF2):
 
 @dataclass(frozen=True)
 class _FixedStep:
-    """What differs between the six fixed-step entry points; _step_fixed is their one body."""
+    """What differs between the fixed-step entry points; _step_fixed is their one body."""
     symbol: str            # the library call
     scope: tuple           # _check_scope's arguments after the model: the name in the refusals, the family, layered, scalar
     flag: Optional[int]    # the flag of method "trbdf2"; None: no `method`, backward Euler with boundary values at t_{n+1}
@@ -1576,6 +1608,8 @@ _STEP_HEAT_LAYERED = _FixedStep("lh_step_layered_heat_implicit", ("step_implicit
 _STEP_COUPLED = _FixedStep("lh_step_coupled_implicit", ("step_implicit_coupled", _COUPLED), F.LH_COUPLED_TRBDF2, True)
 _STEP_COUPLED_LAYERED = _FixedStep("lh_step_layered_coupled_implicit",
                                    ("step_implicit_layered_coupled", _COUPLED, True, "lh_step_coupled_implicit"),
+                                   F.LH_COUPLED_TRBDF2, True)
+_STEP_COUPLED_FACTORS = _FixedStep("lh_step_coupled_factors_implicit", ("step_implicit_coupled_factors", _COUPLED_FACTORS),
                                    F.LH_COUPLED_TRBDF2, True)
 
 
@@ -1620,6 +1654,14 @@ def step_implicit_layered_coupled(model: SoilModel, Y: "FieldVector", Ya=None, t
     (lh_step_layered_coupled_implicit); arguments, sampling of the boundary values and the result as
     step_implicit_coupled."""
     return _step_fixed(_STEP_COUPLED_LAYERED, model, Y, Ya, t, dt, nsteps, method, tol, max_iter)
+
+
+def step_implicit_coupled_factors(model: SoilModel, Y: "FieldVector", Ya=None, t: float = 0.0, dt: float = 1.0,
+                                  nsteps: int = 1, method: str = "euler", tol=None, max_iter=None):
+    """Build extension: step_implicit_coupled for a coupled model whose hydrology has the IceImpedance factor and no
+    viscosity factor (lh_step_coupled_factors_implicit); arguments, sampling of the boundary values and the result as
+    step_implicit_coupled."""
+    return _step_fixed(_STEP_COUPLED_FACTORS, model, Y, Ya, t, dt, nsteps, method, tol, max_iter)
 
 
 def _sampled_bcv(model, times, base_t):
